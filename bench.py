@@ -7,7 +7,11 @@ synthetic batch whose inputs are already resident in HBM.  Default workload = th
 headline: 1000 synthetic blocks x 64 sequences x 5 kbp, default convex scores 1,4,6,2,26,1,
 local alignment (the reference's defaults, src/main.cpp:322-327,487).
 
-    python bench.py --gpus N --steps K --warmup W [--workload ns|c2|c3|tiny] [--mode sw|nw]
+    python bench.py --gpus N --steps K --warmup W [--workload ns|c2|c3|tiny] [--mode sw|nw] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (plus the last step's outputs with --dump-outputs);
+--full adds what the headline figure does not need: the check of the timed batch against the committed fixtures, the
+copy bandwidth, the end-to-end iteration and the CPU baseline.
 
 N>1: launched by torch.distributed.run, one rank per GPU; blocks are independent, so each
 rank owns its own 1000 blocks (weak scaling; --scaling strong deals ONE workload by LPT) and the
@@ -327,6 +331,54 @@ def verify_against_fixture(res, workload, mode, first_block, prm, order="spoa"):
     return True, done, "scores of all sequences, cells, node/edge counts and SHA-256 of nodes, ranks, groups, edges, weights, paths == tests/golden/fullshape_oracle.json"
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_BLOCKS, DUMP_SEED = 8, 0
+
+
+def save_dump(d, arrays):
+    """Writes {name: array} as d/<name>.npy; refuses to write more than DUMP_MAX_BYTES in all."""
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: what a caller of the timed path receives from its last step (sxg_poa_batch_download), so that two builds
+    can be compared output for output.  Whole batch: status, node and edge counts per block, score and DP cells per sequence
+    (float64, exact).  A fixed seeded sample of DUMP_SAMPLE_BLOCKS blocks (the same ids for the same batch size): their
+    graphs (node code / rank / group, edge tail / head / weight) and per-base node paths, concatenated in sample order, with
+    float64 offsets; float32, exact for the values below 2^24 these hold (checked)."""
+    nb = len(res)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).permutation(nb)[:min(DUMP_SAMPLE_BLOCKS, nb)])
+    out = {"status": np.asarray([r.status for r in res], np.float64),
+           "n_nodes": np.asarray([len(r.node_code) for r in res], np.float64),
+           "n_edges": np.asarray([len(r.edge_tail) for r in res], np.float64),
+           "scores": np.concatenate([np.asarray(r.scores, np.float64) for r in res]) if nb else np.zeros(0),
+           "cells": np.concatenate([np.asarray(r.cells, np.float64) for r in res]) if nb else np.zeros(0),
+           "sample_blocks": pick.astype(np.float64)}
+
+    def paths(r):
+        return np.concatenate([np.asarray(q, np.int64) for q in r.paths]) if r.paths else np.zeros(0, np.int64)
+    fields = (("node_code", lambda r: r.node_code, "node"), ("node_rank", lambda r: r.node_rank, "node"),
+              ("node_group", lambda r: r.node_group, "node"), ("edge_tail", lambda r: r.edge_tail, "edge"),
+              ("edge_head", lambda r: r.edge_head, "edge"), ("edge_weight", lambda r: r.edge_weight, "edge"), ("paths", paths, "path"))
+    offs = {"node": [0], "edge": [0], "path": [0]}
+    for name, get, kind in fields:
+        parts = [np.asarray(get(res[b]), np.int64) for b in pick]
+        v = np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        if len(v) and int(np.abs(v).max()) >= (1 << 24):
+            raise SystemExit("--dump-outputs: %s holds values float32 cannot represent exactly" % name)
+        out["sample_" + name] = v.astype(np.float32)
+        if len(offs[kind]) == 1:
+            offs[kind] += np.cumsum([len(p) for p in parts]).tolist()
+    for kind, o in offs.items():
+        out["sample_%s_off" % kind] = np.asarray(o, np.float64)
+    save_dump(d, out)
+
+
 def bench_drb1(a, local_rank):
     """Configs 1 / 5 as the reference's ctest runs them (CMakeLists.txt:565): THREE chained smoothing iterations
     (-l 700,900,1100 -j 5k -e 5k -r 12) on test/data's DRB1-3123 seqwish GFA (committed as tests/golden/DRB1-3123.seqwish.gfa),
@@ -343,8 +395,11 @@ def bench_drb1(a, local_rank):
     eng = S.PoaEngine(local_rank)
     prov = SM.gpu_provider(eng)
 
+    texts = []   # the GFA of every iteration of the last chain (--dump-outputs)
+
     def chain():
         text, per, shas, kms, blocks = text0, [], [], [], []
+        del texts[:]
         for it, tl in enumerate((700, 900, 1100)):
             t0 = time.perf_counter()
             sm = SM.Smoother(text, discover=dict(target_poa_length=tl, n_haps=12, max_path_jump=5000, max_edge_jump=5000))
@@ -354,14 +409,18 @@ def bench_drb1(a, local_rank):
             per.append(time.perf_counter() - t0)
             kms.append(eng.stats()["kernel_ms"])
             shas.append(hashlib.sha256(text.encode()).hexdigest())
+            texts.append(text)
         return per, shas, kms, blocks
     for _ in range(a.warmup):
         chain()
     t0 = time.perf_counter()
     runs = [chain() for _ in range(a.steps)]
     dt = time.perf_counter() - t0
-    ok = all(r[1] == [g["sha256"] for g in gold] for r in runs)
-    if not ok:
+    if a.dump_outputs:
+        # the GFA text of each iteration as its byte values (float32: exact)
+        save_dump(a.dump_outputs, {"gfa_iteration%d" % k: np.frombuffer(t.encode(), np.uint8).astype(np.float32) for k, t in enumerate(texts)})
+    ok = all(r[1] == [g["sha256"] for g in gold] for r in runs) if a.full else None
+    if ok is False:
         raise SystemExit("bench verification failed: a DRB1 iteration's GFA differs from tests/golden/drb1_chain.json")
     per = [sum(r[0][k] for r in runs) / len(runs) for k in range(3)]
     kms = [sum(r[2][k] for r in runs) / len(runs) for k in range(3)]
@@ -370,7 +429,8 @@ def bench_drb1(a, local_rank):
            "vs_baseline": None, "dtype": "int16", "data": "tests/golden/DRB1-3123.seqwish.gfa (the reference's test/data input)",
            "config": {"workload": WORKLOADS["drb1"][4], "blocks_per_iteration": runs[0][3], "mode": "sw"},
            "iteration_seconds": per, "iteration_kernel_ms": kms,
-           "verified": True, "verified_what": "SHA-256 of every iteration's GFA == tests/golden/drb1_chain.json (oracle stack)",
+           "verified": ok, "verified_what": "SHA-256 of every iteration's GFA == tests/golden/drb1_chain.json (oracle stack)" if a.full
+           else "not checked (a plain run; --full checks it)",
            "reference_published": "23.4-25.5 s wall for the reference's whole run of this input on a Ryzen 7 3700X (test/performance/check.md:7-28; "
                                   "includes MAF output and the consensus graph, which are outside this path)",
            "roofline": None, "cpu_baseline": None}
@@ -404,6 +464,13 @@ def main():
                     help="start the ranks through torch.distributed.run even for --gpus 1 (what --gpus N > 1 does by itself when no launcher "
                          "started this process): the one-rank job then runs the multi-rank path -- RCCL communicator on the engine handle, "
                          "sxg_poa_batch_execute_sharded per step, `exchange` on the line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the timed batch against the committed fixtures, "
+                         "the copy bandwidth, the rank-0 reassembly, the end-to-end iteration and the CPU baseline (each still subject to "
+                         "--no-verify / --no-e2e / --no-cpu-baseline).  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: the whole batch's per-block and per-sequence results, the graphs and paths of a fixed seeded sample of blocks)")
     a = ap.parse_args()
 
     import torch
@@ -424,7 +491,11 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(a.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + [x for x in sys.argv[1:] if x != "--launch"]
         sys.stdout.flush()
-        os.execvpe(cmd[0], cmd, env)
+        # a child process, not exec: this process has initialised the GPU (torch.cuda above), and replacing a program that holds
+        # the device open is unsafe
+        import subprocess
+        rc = subprocess.run(cmd, env=env).returncode
+        sys.exit(rc if rc >= 0 else 128 - rc)   # (killed by a signal: the shell's 128 + signal)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -549,8 +620,11 @@ def main():
 
     # The number printed below is worth something only if the batch it timed is right: the blocks of the batch that the
     # committed full-shape fixture holds are downloaded and compared (outside the timed region; no oracle code involved).
-    verified, verified_blocks, verified_note = None, [], "skipped (--no-verify)"
-    if rank == 0 and not a.no_verify:
+    # A plain run leaves that to --full.
+    verified, verified_blocks, verified_note = None, [], "skipped (--no-verify)" if a.full else "not checked (a plain run; --full checks it)"
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng.download_sharded() if (strong and exchange == "cabi") else eng.download())
+    if rank == 0 and a.full and not a.no_verify:
         if strong and exchange == "cabi":
             verified_note = "strong scaling deals the blocks over the ranks: not checked here"
         elif FIXTURE_CASE.get((a.workload, a.mode)) is None:
@@ -569,10 +643,10 @@ def main():
 
     # What rank 0 does with a step's exchange before it can lace: the blobs of all ranks reassembled in batch order
     # (sxg_poa_batch_download_sharded).  Outside the timed region; only while the reassembled batch stays below ~12 GB of host memory.
-    root_ms, root_note = None, "not measured"
-    if multi and exchange == "cabi" and not strong:
+    root_ms, root_note = None, "not measured" if a.full else "not measured (a plain run; --full measures it)"
+    if a.full and multi and exchange == "cabi" and not strong:
         root_note = "weak scaling: every rank brought its own blocks, there is no common batch to put back in order (--scaling strong measures it)"
-    elif multi and exchange == "cabi":
+    elif a.full and multi and exchange == "cabi":
         est_bytes = 5.0 * float(len(bases))
         if est_bytes > 12e9 and not os.environ.get("SXG_BENCH_ROOT_DOWNLOAD"):
             root_note = "skipped: ~%.0f GB of reassembled results on rank 0 (SXG_BENCH_ROOT_DOWNLOAD=1 forces it)" % (est_bytes / 1e9)
@@ -587,7 +661,7 @@ def main():
             except Exception as e:   # (a measurement beside the headline: never fails the line)
                 root_note = "failed: %s" % e
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and a.full:
         try:
             copy_gbps = eng.measure_copy(1 << 30, 5)
         except Exception as e:   # (a figure beside the roofline: never fails the line)
@@ -711,7 +785,7 @@ def main():
             # peak (hbm.algo_frac_of_peak > 1 is NOT an achieved fraction).  frac = architectural issue cycles of the
             # VALU instructions executed per second / SIMD cycles per second (1024 SIMDs x measured clock);
             # hbm.counter_* is what FETCH_SIZE/WRITE_SIZE measured.
-            "roofline": roof,
+            "roofline": roof, "cpu_baseline": None,
             "engine": {"slots": st["n_slots"], "retries": st["retries"], "arena_bytes": st["device_bytes"],
                        "roctx_ranges": bool(eng.roctx_available())},
             "exchange": ({"path": "C ABI: sxg_poa_batch_execute_sharded (RCCL all-gather of sizes + grouped ncclSend/ncclRecv to rank 0)"
@@ -719,7 +793,7 @@ def main():
                           "rank0_reassembly_ms": root_ms, "rank0_reassembly_what": root_note,
                           "launcher": "bench.py started its own ranks" if os.environ.get("SXG_BENCH_LAUNCHED") == "1" else "started by a launcher"} if multi else None),
         }
-        if world == 1 and not a.no_e2e and a.workload in ("ns", "c2", "c2x8", "tiny"):
+        if world == 1 and a.full and not a.no_e2e and a.workload in ("ns", "c2", "c2x8", "tiny"):
             e_s, e_bytes, e_first = end_to_end(eng, bases, seq_off, blk_off, prm, mode, spoa_order)
             out["end_to_end"] = {"what": "sxg_smooth_gfa on the same %d blocks: host collection + upload + POA kernels + "
                                          "download + block graphs + lacing + validation + unchop + GFA text (padding off)" % nb,
@@ -729,7 +803,7 @@ def main():
                                  "blocks_per_sec": nb / e_s, "gfa_bytes": e_bytes,
                                  "kernel_only_blocks_per_sec": nb * a.steps / (kernel_ms / 1e3),
                                  "ratio_to_kernel_only": (nb / e_s) / (nb * a.steps / (kernel_ms / 1e3))}
-        if world == 1 and not a.no_cpu_baseline and a.workload not in ("c4", "c3b", "c3a"):  # (no fixed shape to sample for c4)
+        if world == 1 and a.full and not a.no_cpu_baseline and a.workload not in ("c4", "c3b", "c3a"):  # (no fixed shape to sample for c4)
             cb = cpu_baseline(a.workload, mode, spoa_order)
             cells_per_block = cells / a.steps / nb
             out["cpu_baseline"] = {"value": cb["cells_per_s"] / cells_per_block, "unit": "blocks/s",
