@@ -261,11 +261,12 @@ __host__ __device__ constexpr int dp16_let_words(int W) { return (W + 1) / 2; }
 // (round 3: the packed sweep reads its row descriptors through the scalar cache; what is left of the staging area holds the
 // wave-to-wave mailboxes during a sweep and the traceback window after it: 4 KB for every geometry)
 __host__ __device__ constexpr int dp16_meta_bytes(int) { return LDS_META_BYTES / 2; }
-__host__ __device__ constexpr int dp16_row_bytes(int T, int W) { return T * W * 8 + T * 4; }   // a stored row + its left-neighbour words
+// a stored row + its left-neighbour words: 8-byte row words (CB = 4) or 4-byte row codes (CB = 2: P16RowCode, poa_rowcode.h)
+__host__ __device__ constexpr int dp16_row_bytes(int T, int W, int CB) { return T * W * (CB == 2 ? 4 : 8) + T * 4; }
 // control words | mailboxes / traceback window | lds_rows on-chip copies of stored rows | query letters.  The traceback
 // keeps its precomputed runs (2.3 KB) where the row copies start: never less than that behind the window.
-__host__ __device__ constexpr int dp16_lds_bytes(int T, int W, int lds_rows) {
-    const int body = lds_rows * dp16_row_bytes(T, W) + T * dp16_let_words(W) * 4;
+__host__ __device__ constexpr int dp16_lds_bytes(int T, int W, int lds_rows, int CB) {
+    const int body = lds_rows * dp16_row_bytes(T, W, CB) + T * dp16_let_words(W) * 4;
     return LDS_CTL_BYTES + dp16_meta_bytes(T) + (body > 2560 ? body : 2560);
 }
 __host__ __device__ constexpr int dp_lds_launch_bytes(int Lpad, int word_bytes) {

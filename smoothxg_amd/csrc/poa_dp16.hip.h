@@ -30,8 +30,10 @@
 // 32-bit sweep runs.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include <utility>
 #include "poa_dp.hip.h"
+#include "poa_rowcode.h"
 
 namespace sxg {
 
@@ -91,35 +93,7 @@ __device__ __forceinline__ void p16_unpack_row(u32x2 w, int& h, int& of, int& oo
     oo = BIASED ? (int)((unsigned)h - (unsigned)dq) : pk_sub(h, dq);
 }
 
-// ---- 2-byte plane cells (CB = 2, round 5) --------------------------------------------------------------------------
-// The band stores of the traceback plane were the largest single cost of the packed sweep (cost map of round 4: 24 % of the
-// headline launch; 45 % of the sweep of 8000 blocks of 16 x 1 kbp, where the launch sits at the HBM write roof).  A plane cell
-// held H (16 bits) and the two distances H - oF, H - oO (8 bits each).  H need not be stored in full: along a row it moves in
-// small steps --
-//     g <= H[i][j] - H[i][j-1] <= m - g        (g = the cheapest gap opening, normalised scores; proof in DESIGN.md section 3.1:
-//     the lower bound is the in-row gap E >= H[j-1] + g, the upper one follows by induction over the ranks from
-//     H[i][j-1] >= H[p][j-1] + g for the predecessor p a diagonal step into (i, j) came from)
-// -- and the distances lie in [-e, -g] and [-c, -q].  A cell is therefore the 16-bit code
-//     (H[j] - H[j-1] - g)  |  (H - oF + e) << bH  |  (H - oO + c) << (bH + bF),      bH + bF + bO <= 16,
-// and a strip of a row is W + 1 halfwords: the H of the column LEFT of the strip (the value the sweep hands from lane to
-// lane anyway; strip 0: H of column 0, whose own step is written as 0), then the W codes.  12 bits for the default scores
-// 1,4,6,2,26,1; 16 for pggb's asm10 set; a score set that needs more (asm5: 1,19,39,3,81,1 -- 20 bits) takes the 4-byte
-// cells (CB = 4: the round-4 format, every kernel class exists in both).  The traceback rebuilds H by summing the steps of
-// a strip from its left end -- at most W additions for a cell it visits.
-struct P16Delta {
-    int bH, bF, bO;      // field widths
-    int g, eabs, cabs;   // what the fields are offset by: dH - g, dF - |e|, dO - |c| are >= 0
-};
-__host__ __device__ inline int p16_bits_for(int n_values) { int b = 0; while ((1 << b) < n_values) ++b; return b; }
-__host__ __device__ inline P16Delta p16_delta_of(const Scoring& S) {
-    P16Delta D;
-    D.g = S.g; D.eabs = -S.e; D.cabs = -S.c;
-    D.bH = p16_bits_for(S.m - 2 * S.g + 1);
-    D.bF = p16_bits_for(S.e - S.g + 1);
-    D.bO = S.convex ? p16_bits_for(S.c - S.q + 1) : 0;
-    return D;
-}
-__host__ __device__ inline bool p16_delta_fits(const Scoring& S) { const P16Delta D = p16_delta_of(S); return D.bH + D.bF + D.bO <= 16; }
+// 2-byte plane cells (CB = 2): P16Delta, poa_rowcode.h
 // dwords of one strip of a row: W + 1 halfwords
 __host__ __device__ constexpr int p16_slot_dwords(int W, int CB) { return CB == 2 ? (W + 2) / 2 : W; }
 
@@ -300,12 +274,10 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     const int We = W * e, Wc = W * c;
     const int BS = __builtin_amdgcn_readfirstlane(B.band_strips);
     constexpr int SD = p16_slot_dwords(W, CB);   // dwords of one strip in a plane row
-    // (CB = 2) the multipliers that shift a cell's two distances into their fields of the code
+    // (CB = 2) the field widths of the plane's delta code
     Scoring SD_ = S;
     if (DS) { SD_.m = P16_DEF_M; SD_.n = P16_DEF_N; SD_.g = P16_DEF_G; SD_.e = P16_DEF_E; SD_.q = P16_DEF_Q; SD_.c = P16_DEF_C; SD_.convex = 1; }
     const P16Delta DF = p16_delta_of(SD_);
-    const int KF2 = pk2(1 << __builtin_amdgcn_readfirstlane(DF.bH), 1 << __builtin_amdgcn_readfirstlane(DF.bH));
-    const int KO2 = pk2(1 << __builtin_amdgcn_readfirstlane(DF.bH + DF.bF), 1 << __builtin_amdgcn_readfirstlane(DF.bH + DF.bF));
     // ... and what reading a row back out of the plane needs (full-width planes only, see ring_plane below)
     const int dbH_ = __builtin_amdgcn_readfirstlane(DF.bH), dbF_ = __builtin_amdgcn_readfirstlane(DF.bF);
     const int D_SH1 = pk2(dbH_, dbH_), D_SH2 = pk2(dbH_ + dbF_, dbH_ + dbF_);
@@ -313,6 +285,11 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     const int d_cst_ = g + ((-e) << dbH_) + ((CVX ? -c : 0) << (dbH_ + dbF_));
     const int D_CST = pk2(d_cst_, d_cst_);
     const int D_EA = pk2(-e, -e), D_CA = pk2(-c, -c);
+    // (CB = 2) stored rows: the row code (poa_rowcode.h); the field widths are the plane's
+    P16Delta DFu = DF;
+    DFu.bH = dbH_; DFu.bF = dbF_; DFu.bO = __builtin_amdgcn_readfirstlane(DF.bO);
+    DFu.g = g; DFu.eabs = -e; DFu.cabs = -c;
+    const P16RowCode RC = p16_row_code_of(DFu, CVX);
     // A plane that keeps EVERY strip of every row (sequences up to ~1.4 kbp -- the blocks smoothxg's default -l 700 ... 1100
     // produces --, the every-strip plane of a band-miss re-run) already holds what the row ring would: stored rows are not
     // written a second time, a stored predecessor is read back from its plane row and decoded.  (Cost map of 8000 x 16 x 1 kbp,
@@ -364,7 +341,14 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     // (raw LDS byte offset: the dynamic LDS starts right behind the kernel's static LDS)
     typedef __attribute__((address_space(3))) unsigned lds_u32;
     const int LDS_ROWS = __builtin_amdgcn_readfirstlane(B.lds_rows);
-    const unsigned llet_off = (unsigned)__builtin_amdgcn_groupstaticsize() + (unsigned)(LDS_CTL_BYTES + MB + LDS_ROWS * (TW * 8 + T * 4) + t * NL * 4);
+    // a stored row: W columns of row words [column][lane] (CB = 4: 8-byte words, packed H + two distances; CB = 2: one dword of
+    // row codes, see P16RowCode), then the column LEFT of every lane's strips (4 bytes per lane).
+    // (Pairs of columns per 16-byte access, as in the plane, were measured in round 4: 90 instead of 131 memory instructions in
+    // the row loop, 2 010 against 1 996 ms on the headline, c3 -1 %, c4 +1 %: the ring's cost is its volume, not its instruction
+    // count -- kept at one word per column.)
+    constexpr int RWB = CB == 2 ? 4 : 8;   // bytes of one row word
+    const int RB = dp16_row_bytes(T, W, CB);
+    const unsigned llet_off = (unsigned)__builtin_amdgcn_groupstaticsize() + (unsigned)(LDS_CTL_BYTES + MB + LDS_ROWS * RB + t * NL * 4);
 #pragma unroll
     for (int k2 = 0; k2 < NL; ++k2) ((lds_u32*)(size_t)llet_off)[k2] = let[k2];
 
@@ -406,17 +390,24 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
         }
         Hleft = pk2(h2[0], h2[1]);
     }
-    // a stored row: W columns of 8-byte words [column][lane], then the column LEFT of every lane's strips (4 bytes per lane).
-    // (Pairs of columns per 16-byte access, as in the plane, were measured in round 4: 90 instead of 131 memory instructions in
-    // the row loop, 2 010 against 1 996 ms on the headline, c3 -1 %, c4 +1 %: the ring's cost is its volume, not its instruction
-    // count -- kept at 8 bytes.)
-    const int RB = TW * 8 + T * 4;
     {
         const __amdgpu_buffer_rsrc_t rs0 = p16_rsrc((const void*)g_row0, RB);
+        if constexpr (CB == 2) {
+            // (strip 0 has no left neighbour: its codes start from its own first column, as in the plane)
+            const int lh0 = t == 0 ? (int)(((unsigned)Hleft & 0xffff0000u) | ((unsigned)Hp[0] & 0x0000ffffu)) : Hleft;
+            int prev = lh0;
 #pragma unroll
-        for (int k = 0; k < W; ++k)
-            __builtin_amdgcn_raw_buffer_store_b64(p16_pack_row<CVX, SW>(Hp[k], Fp[k], Op[k]), rs0, ut8, k * T * 8, 0);
-        __builtin_amdgcn_raw_buffer_store_b32((unsigned)Hleft, rs0, (unsigned)t * 4u, TW * 8, 0);
+            for (int k = 0; k < W; ++k) {
+                __builtin_amdgcn_raw_buffer_store_b32((unsigned)p16_row_encode<CVX, SW>(Hp[k], prev, Fp[k], Op[k], DFu, RC), rs0, (unsigned)t * 4u, k * T * 4, 0);
+                prev = Hp[k];
+            }
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)lh0, rs0, (unsigned)t * 4u, TW * 4, 0);
+        } else {
+#pragma unroll
+            for (int k = 0; k < W; ++k)
+                __builtin_amdgcn_raw_buffer_store_b64(p16_pack_row<CVX, SW>(Hp[k], Fp[k], Op[k]), rs0, ut8, k * T * 8, 0);
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)Hleft, rs0, (unsigned)t * 4u, TW * 8, 0);
+        }
     }
     int best_lo = NEGP * 2, best_hi = best_lo, bi_lo = -1, bi_hi = -1, bk_lo = 0, bk_hi = 0;   // (global alignment only)
     const int kL_lo = L - j0, kL_hi = L - j0h;  // strip-local index of the end column L
@@ -455,15 +446,15 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     // on-chip copies of stored rows (finish_rows: a stored row whose last reader comes before LDS_ROWS more rows are stored
     // lives in LDS only and never travels to HBM): behind the control words and the mailbox / traceback-window area
     const unsigned lds_rows0 = lds0 + (unsigned)(LDS_CTL_BYTES + MB);
-// my words of on-chip row copy b_: W 8-byte words [wave][column][lane] (a wave's 64 lanes side by side: every LDS access of
-// the sweep is conflict-free, and column k is the immediate offset k * 512), then the left-neighbour word [lane].  The
+// my words of on-chip row copy b_: W row words [wave][column][lane] (a wave's 64 lanes side by side: every LDS access of
+// the sweep is conflict-free, and column k is the immediate offset k * 64 * RWB), then the left-neighbour word [lane].  The
 // addresses are rebuilt from an opaque copy of the thread index: no loop-invariant address registers.
 #define P16_LDS_ROW(words_, left_, b_)                                                                      \
     int tq_ = t;                                                                                            \
     asm volatile("" : "+v"(tq_));                                                                           \
     const unsigned lb_ = lds_rows0 + (unsigned)(b_) * (unsigned)RB;                                         \
-    lds_u32x2* const words_ = (lds_u32x2*)(size_t)(lb_ + (unsigned)(wv * (512 * W - 512)) + (unsigned)tq_ * 8u); \
-    lds_u32* const left_ = (lds_u32*)(size_t)(lb_ + (unsigned)(TW * 8) + (unsigned)tq_ * 4u)
+    std::conditional_t<CB == 2, lds_u32, lds_u32x2>* const words_ = (std::conditional_t<CB == 2, lds_u32, lds_u32x2>*)(size_t)(lb_ + (unsigned)(wv * (64 * RWB * W - 64 * RWB)) + (unsigned)tq_ * (unsigned)RWB); \
+    lds_u32* const left_ = (lds_u32*)(size_t)(lb_ + (unsigned)(TW * RWB) + (unsigned)tq_ * 4u)
     // (B lives in the kernel's private memory: testing B.prio_board per row was a scratch load plus an
     // in-order vmcnt(0) -- a wait for every store of the previous row -- at the top of EVERY row)
     const bool has_board = __builtin_amdgcn_readfirstlane((int)(B.prio_board != nullptr)) != 0;
@@ -514,6 +505,7 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
         // 1 859 -> 1 786 ms on one box, 1 417 -> 1 025 static VALU instructions and 132 -> 42 v_mov in the loop.)
 // words of the stored row of predecessor p_ (slot sl_) and the column to their left (stored with the row: every word of
 // a stored row was written by the lane that reads it).  sl_ <= -2: the row is one of the LDS_ROWS on-chip copies.
+// (CB = 2: wr_ are the row codes, unsigned [W], and hl_ is the left word as stored -- P16_DECODE turns both into values)
 #define P16_FETCH(p_, sl_, wr_, hl_)                                                                        \
     do {                                                                                                    \
         if ((sl_) <= -2) {                                                                                  \
@@ -522,11 +514,26 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
             hl_ = (int)*lf_;                                                                                \
         } else {                                                                                            \
             const __amdgpu_buffer_rsrc_t rs_ = p16_rsrc(((p_) == 0) ? (const void*)g_row0 : (const void*)((SXG_GLOBAL const char*)g_pool + (size_t)(sl_) * (size_t)RB), RB); \
-            _Pragma("unroll") for (int k = 0; k < W; ++k) wr_[k] = __builtin_amdgcn_raw_buffer_load_b64(rs_, ut8, k * T * 8, 0); \
+            if constexpr (CB == 2) {                                                                        \
+                _Pragma("unroll") for (int k = 0; k < W; ++k) wr_[k] = __builtin_amdgcn_raw_buffer_load_b32(rs_, ut8 >> 1, k * T * 4, 0); \
+            } else {                                                                                        \
+                _Pragma("unroll") for (int k = 0; k < W; ++k) wr_[k] = __builtin_amdgcn_raw_buffer_load_b64(rs_, ut8, k * T * 8, 0); \
+            }                                                                                               \
             P16_PROF_FETCH();                                                                               \
-            hl_ = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_, ut8 >> 1, TW * 8, 0);                       \
+            hl_ = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_, ut8 >> 1, TW * RWB, 0);                     \
             P16_DRAIN();                                                                                    \
         }                                                                                                   \
+    } while (0)
+// (CB = 2) a fetched row's codes -> HS_/FS_/OS_[k], the row's H and outgoing candidates, summing the steps from the left word;
+// then the left word as the sweep keeps it (strip 0: "minus infinity", see the left word of P16RowCode)
+#define P16_DECODE(wr_, hl_, HS_, FS_, OS_)                                                                 \
+    do {                                                                                                    \
+        int run_ = hl_;                                                                                     \
+        _Pragma("unroll") for (int k = 0; k < W; ++k) {                                                     \
+            p16_row_decode<CVX, SW>(wr_[k], run_, FS_[k], OS_[k], RC);                                      \
+            HS_[k] = run_;                                                                                  \
+        }                                                                                                   \
+        if (t == 0) hl_ = (int)(((unsigned)hl_ & 0xffff0000u) | ((unsigned)FLOORV & 0xffffu));               \
     } while (0)
 
 // ... or, with ring_plane, the row's strips out of its plane row: H of the column left of the strips, then per column the
@@ -572,7 +579,13 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
             if (!regbase) {
                 int hl;
                 if (ring_plane && s0 >= 0 && p0 != 0) P16_FETCH_PLANE(p0, true, Hp, Fp, Op, hl);
-                else {
+                else if constexpr (CB == 2) {
+                    unsigned wr[W];
+                    P16_FETCH(p0, s0, wr, hl);
+                    P16_DECODE(wr, hl, Hp, Fp, Op);
+#pragma unroll
+                    for (int k = 0; k < W; ++k) SXG_PIN("+v"(Hp[k]), "+v"(Fp[k]), "+v"(Op[k]));
+                } else {
                     u32x2 wr[W];
                     P16_FETCH(p0, s0, wr, hl);
 #pragma unroll
@@ -587,9 +600,10 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
 #define P16_FOLD(p_, sl_)                                                                                   \
     do {                                                                                                    \
         int hl;                                                                                             \
-        if (ring_plane && (sl_) >= 0 && (p_) != 0) {                                                        \
+        if constexpr (CB == 2) {                                                                            \
             int hs_[W], fs_[W], os_[W];                                                                     \
-            P16_FETCH_PLANE(p_, true, hs_, fs_, os_, hl);                                                   \
+            if (ring_plane && (sl_) >= 0 && (p_) != 0) P16_FETCH_PLANE(p_, true, hs_, fs_, os_, hl);        \
+            else { unsigned wr_[W]; P16_FETCH(p_, sl_, wr_, hl); P16_DECODE(wr_, hl, hs_, fs_, os_); }      \
             _Pragma("unroll") for (int k = 0; k < W; ++k) {                                                 \
                 Fp[k] = pk_max(Fp[k], fs_[k]);                                                              \
                 if (CVX) Op[k] = pk_max(Op[k], os_[k]);                                                     \
@@ -597,16 +611,16 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
                 SXG_PIN("+v"(Hp[k]), "+v"(Fp[k]), "+v"(Op[k]));                                             \
             }                                                                                               \
         } else {                                                                                            \
-        u32x2 wr[W];                                                                                        \
-        P16_FETCH(p_, sl_, wr, hl);                                                                         \
-        _Pragma("unroll") for (int k = 0; k < W; ++k) {                                                     \
-            int hs, fs, os;                                                                                 \
-            p16_unpack_row<SW>(wr[k], hs, fs, os);                                                          \
-            Fp[k] = pk_max(Fp[k], fs);                                                                      \
-            if (CVX) Op[k] = pk_max(Op[k], os);                                                             \
-            Hp[k] = pk_max(Hp[k], hs);                                                                      \
-            SXG_PIN("+v"(Hp[k]), "+v"(Fp[k]), "+v"(Op[k]));                                                 \
-        }                                                                                                   \
+            u32x2 wr[W];                                                                                    \
+            P16_FETCH(p_, sl_, wr, hl);                                                                     \
+            _Pragma("unroll") for (int k = 0; k < W; ++k) {                                                 \
+                int hs, fs, os;                                                                             \
+                p16_unpack_row<SW>(wr[k], hs, fs, os);                                                      \
+                Fp[k] = pk_max(Fp[k], fs);                                                                  \
+                if (CVX) Op[k] = pk_max(Op[k], os);                                                         \
+                Hp[k] = pk_max(Hp[k], hs);                                                                  \
+                SXG_PIN("+v"(Hp[k]), "+v"(Fp[k]), "+v"(Op[k]));                                             \
+            }                                                                                               \
         }                                                                                                   \
         Hleft = pk_max(Hleft, hl);                                                                          \
     } while (0)
@@ -624,6 +638,7 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
         }
 #undef P16_DRAIN
 #undef P16_FETCH
+#undef P16_DECODE
         if (!CVX) {
 #pragma unroll
             for (int k = 0; k < W; ++k) Op[k] = NEG2;
@@ -790,7 +805,7 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
 // ring row + band cells of this row; CF(k) / CO(k) = the row's outgoing candidates of column k
 #define P16_STORES(CF, CO)                                                                                  \
     do {                                                                                                    \
-        if (ring) {                                                                                         \
+        if constexpr (CB == 4) if (ring) {                                                                  \
             if (myslot <= -2) {                                                                             \
                 P16_LDS_ROW(la_, lf_, -2 - myslot);                                                         \
                 _Pragma("unroll") for (int k = 0; k < W; ++k) la_[k * 64] = p16_pack_row<CVX, SW>(Hc[k], CF, CO); \
@@ -801,17 +816,25 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
                 __builtin_amdgcn_raw_buffer_store_b32((unsigned)lh, rs_ring, ut8 >> 1, TW * 8, 0);          \
             }                                                                                               \
         }                                                                                                   \
-        if (CB == 2) {                                                                                      \
+        if constexpr (CB == 2) {                                                                            \
+            const bool copy_lds = ring && myslot <= -2, copy_hbm = ring && myslot > -2 && !ring_plane;      \
+            /* a stored row: the row codes (P16RowCode) of my two strips, and the left word */              \
+            if (copy_lds) {                                                                                 \
+                P16_LDS_ROW(la_, lf_, -2 - myslot);                                                         \
+                _Pragma("unroll") for (int k = 0; k < W; ++k)                                               \
+                    la_[k * 64] = (unsigned)p16_row_encode<CVX, SW>(Hc[k], k ? Hc[k ? k - 1 : 0] : lhs, (CF), (CO), DFu, RC); \
+                *lf_ = (unsigned)lhs;                                                                       \
+            } else if (copy_hbm) {                                                                          \
+                _Pragma("unroll") for (int k = 0; k < W; ++k)                                               \
+                    __builtin_amdgcn_raw_buffer_store_b32((unsigned)p16_row_encode<CVX, SW>(Hc[k], k ? Hc[k ? k - 1 : 0] : lhs, (CF), (CO), DFu, RC), rs_ring, ut8 >> 1, k * T * 4, 0); \
+                __builtin_amdgcn_raw_buffer_store_b32((unsigned)lhs, rs_ring, ut8 >> 1, TW * 4, 0);         \
+            }                                                                                               \
             if (band_lo || band_hi) {                                                                       \
                 /* delta codes of my two strips (see P16Delta): both halves of a register at once */       \
                 int code_[W], prev_ = lhs;                                                                  \
                 _Pragma("unroll") for (int k = 0; k < W; ++k) {                                             \
-                    const int h_ = Hc[k], of_ = (CF), oo_ = (CO);                                           \
-                    const int d2_ = SW ? (int)((unsigned)h_ - (unsigned)of_) : pk_sub(h_, of_);             \
-                    int cd_ = pk_mad(d2_, KF2, pk_sub(h_, prev_));                                          \
-                    if (CVX) cd_ = pk_mad(SW ? (int)((unsigned)h_ - (unsigned)oo_) : pk_sub(h_, oo_), KO2, cd_); \
-                    code_[k] = cd_;                                                                         \
-                    prev_ = h_;                                                                             \
+                    code_[k] = p16_plane_code<CVX, SW>(Hc[k], prev_, (CF), (CO), DFu);                      \
+                    prev_ = Hc[k];                                                                          \
                 }                                                                                           \
                 /* dword x of a strip: halfwords 2x, 2x + 1 of (left H, code 0, ..., code W-1) */            \
                 if (band_lo)                                                                                \

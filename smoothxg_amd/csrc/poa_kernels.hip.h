@@ -72,9 +72,11 @@ inline SlotLayout make_layout(int nodes_cap, int rows_cap, int pool_slots, int s
     // traceback plane: one byte per cell, or (packed sweep) one dword per cell of the row's band of strips
     L.tb = lay(cur, ((size_t)rows_cap + 1) * (packed ? (size_t)band_strips * (size_t)p16_slot_dwords(Lpad / (2 * threads), cell_bytes) * 4 : (size_t)Lpad));
     L.steps = lay(cur, packed ? 256 : (size_t)std::max(step_cap, 1) * 3 * threads * 4);
-    // (a stored row of the packed sweep ends with one more word per lane: the column left of the lane's strips)
-    L.pool = lay(cur, (size_t)pool_slots * ((size_t)Lpad * word_bytes + (size_t)threads * 4));
-    L.row0 = lay(cur, (size_t)Lpad * word_bytes + (size_t)threads * 4);
+    // (a stored row of the packed sweep ends with one more word per lane: the column left of the lane's strips; its 2-byte
+    //  classes store 2 bytes per column, dp16_row_bytes)
+    const size_t row_bytes = (size_t)Lpad * (packed && cell_bytes == 2 ? 2 : word_bytes) + (size_t)threads * 4;
+    L.pool = lay(cur, (size_t)pool_slots * row_bytes);
+    L.row0 = lay(cur, row_bytes);
     L.park = lay(cur, (size_t)Lpad * word_bytes);
     L.cons_sc = lay(cur, 8 * C); L.cons_pr = lay(cur, 4 * C);
     if (pairs) { L.pair_row = lay(cur, 4 * (Rr + Lpad)); L.pair_pos = lay(cur, 4 * (Rr + Lpad)); }

@@ -192,11 +192,11 @@ static bool variant_for_len(int maxlen, int rm, Variant* v, bool sw = false) {
 // 160 KB of LDS when as many workgroups share the CU as its registers allow (128 VGPRs: 16 waves per CU).
 // (Round 4: giving the workgroups of a launch that does not fill the chip -- 1000 two-wave blocks: four per CU where eight
 //  fit -- the LDS the absent ones leave, i.e. 8 on-chip rows instead of 2-3, was measured on c2: 59.6 ms against 57.4 ms.  Dropped.)
-static int p16_lds_rows(const int T, const int W) {
+static int p16_lds_rows(const int T, const int W, const int CB) {
     if (const char* e = getenv("SXG_POA_LDS_ROWS")) return std::max(0, std::min(8, atoi(e)));
     const int wg_per_cu = std::max(1, 16 / std::max(T / 64, 1));
     const int share = (160 * 1024) / wg_per_cu - 512;   // (allocation granularity)
-    const int rows = (share - dp16_lds_bytes(T, W, 0)) / dp16_row_bytes(T, W);
+    const int rows = (share - dp16_lds_bytes(T, W, 0, CB)) / dp16_row_bytes(T, W, CB);
     return std::max(0, std::min(8, rows));
 }
 
@@ -719,7 +719,7 @@ static void prepare_plan(sxg_poa_handle* h, LaunchPlan& P, int attempt) {
     P.kern = block_kernel(P.variant, P.cvx, P.sw);
     P.smem = dp_lds_launch_bytes(Lpad, wb);
     P.park_lds = dp_park_in_lds(Lpad, wb);
-    if (V.RM == 2) { P.lay.lds_rows = p16_lds_rows(V.T(), V.W); P.smem = dp16_lds_bytes(V.T(), V.W, P.lay.lds_rows); P.park_lds = true; }
+    if (V.RM == 2) { P.lay.lds_rows = p16_lds_rows(V.T(), V.W, V.CB); P.smem = dp16_lds_bytes(V.T(), V.W, P.lay.lds_rows, V.CB); P.park_lds = true; }
     if (V.RM == 3) { P.smem = band_lds_bytes(V.W); P.park_lds = true; }
     P.pf_off = (V.RM < 2 && getenv("SXG_POA_PREFETCH")) ? dp_pf_offset(Lpad, wb, V.T()) : -1;
     if (P.pf_off >= 0) P.smem += dp_pf_bytes(Lpad, wb, V.T());
@@ -2273,10 +2273,10 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         const int wb = V.RM == 1 ? 8 : 4;
         SlotLayout lay2 = make_layout((int)std::max<int64_t>(maxe + 8, rows_cap + 8), rows_cap, rows_cap + 1,
                                       (int)maxe + 8, V.T(), V.Lpad(), wb, true, V.RM == 2 ? 2 * V.T() : 0);  // every strip kept
-        if (V.RM == 2) lay2.lds_rows = p16_lds_rows(V.T(), V.W);
+        if (V.RM == 2) lay2.lds_rows = p16_lds_rows(V.T(), V.W, 4);   // (the align-only kernel runs the 4-byte cells)
         auto kern = align_kernel(pl.variant, pl.cvx, pl.sw);
         int per_cu = 1;
-        int smem = V.RM == 2 ? dp16_lds_bytes(V.T(), V.W, lay2.lds_rows) : dp_lds_launch_bytes(V.Lpad(), wb);
+        int smem = V.RM == 2 ? dp16_lds_bytes(V.T(), V.W, lay2.lds_rows, 4) : dp_lds_launch_bytes(V.Lpad(), wb);
         const int pf_off = (V.RM != 2 && getenv("SXG_POA_PREFETCH")) ? dp_pf_offset(V.Lpad(), wb, V.T()) : -1;
         if (pf_off >= 0) smem += dp_pf_bytes(V.Lpad(), wb, V.T());
         if (smem > 48 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
