@@ -120,6 +120,20 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t p16_rsrc(const void* base, con
 __host__ __device__ constexpr int p16_band_strips(int T, int W) {
     return 2 * T * W <= 1408 ? 2 * T : (plane_round4((1100 + W - 1) / W) < 2 * T ? plane_round4((1100 + W - 1) / W) : 2 * T);
 }
+// Adaptive band (round 8): the strips one alignment keeps, from the largest |path column - hint| the block's earlier walks
+// saw (`drift`) plus `margin` columns.  band_first_strip centres the band on the hint's strip, so every column within
+// (BS / 2 - 1) * W of the hint is kept: BS = 2 (ceil((drift + margin) / W) + 1), rounded up to 4, at least lo, and never
+// more than cap (the plane's arena is sized for cap strips per row; a cap narrowed below lo by SXG_POA_BAND_COLS wins).
+// (defaults of BlockArgs::band_floor, band_margin, band_full -- see sxg_poa.hip::band_adapt_args.  Measured on the headline,
+//  1000 x 64 x 5 kbp: floor 48 strips, margin 96 columns keep 54-64 strips per row on average, with 0.4 % of the sweeps
+//  repeated; floor 32, margin 64 keep 41-55 strips but repeat twice as many sweeps, and the launch was no faster)
+constexpr int P16_BAND_FLOOR = 48, P16_BAND_MARGIN = 96, P16_BAND_FULL = 2;
+__host__ __device__ constexpr int p16_drift_strips(int drift, int margin, int W, int lo, int cap) {
+    const int bs = plane_round4(2 * ((drift + margin + W - 1) / W + 1));
+    return (bs < lo ? lo : bs) < cap ? (bs < lo ? lo : bs) : cap;
+}
+static_assert(p16_drift_strips(0, 96, 8, 48, 12) == 12 && p16_drift_strips(300, 96, 11, 48, 100) == 76 &&
+              p16_drift_strips(0, 96, 11, 48, 100) == 48, "adaptive band: floor, then the arena's cap");
 template <int W>
 __device__ __forceinline__ size_t plane_cell(const size_t row, const int BS, const int slot, const int k) {
     return row * (size_t)(W * BS) + (size_t)plane_cell_in_row(W, BS, slot, k);   // (poa_types.h)

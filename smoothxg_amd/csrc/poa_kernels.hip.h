@@ -153,6 +153,10 @@ struct BlockArgs {
     const unsigned long long* est;     // [n_work] estimated cells of work item wi (host cost model)
     int lds_bytes;                     // dynamic LDS of the launch (S7': the re-sort keeps its per-node states behind the control words)
     unsigned long long* blk_cycles;    // [n_blocks] shader-clock cycles the slot spent on block b (sxg_poa_batch_out::block_cycles)
+    // packed sweep, adaptive band: the first `band_full` alignments of a block keep lay.band_strips strips per plane row, the
+    // later ones p16_drift_strips(drift seen so far, band_margin, W, band_floor, lay.band_strips); band_floor = 0: every
+    // alignment keeps lay.band_strips (the fixed band)
+    int band_floor, band_margin, band_full;
 };
 
 // Kernel classes <TMAX, W>: TMAX bounds blockDim.x (the actual T = 64 * strips is a run-time
@@ -218,6 +222,7 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
         }
         unsigned long long tc0 = clock64(), tc1;
         const unsigned long long tblk0 = tc0;
+        int band_drift = 0, band_min = 0;   // packed sweep, adaptive band: largest drift of the block's walks, least width after a repeat
 #define PROF(k) do { if (t == 0) { tc1 = clock64(); prof[k] += tc1 - tc0; tc0 = tc1; } } while (0)
         for (int s = s0; s < s1 && status == ST_OK; ++s) {
             const int64_t so = A.seq_off[s];
@@ -270,7 +275,17 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                     // row's hint.  If the walk needs a cell outside (a structural variant moved the alignment
                     // more than half a band away from the backbone coordinates), the hints of the rows not yet
                     // walked are shifted onto the walk and this sequence's sweep is repeated.
+                    // The band's width follows the block (round 8): the block's first alignments keep the layout's
+                    // strips, the later ones as many as the largest drift of the block's earlier walks asks for, and
+                    // after a repeat at least twice the width that missed.  A plane that keeps every strip is not
+                    // narrowed (ring_plane classes read stored rows back from it).
+                    const int bs_cap = A.lay.band_strips;
+                    int bs = bs_cap;
+                    if (A.band_floor > 0 && bs_cap < 2 * T && s - s0 > A.band_full)
+                        bs = max(p16_drift_strips(band_drift, A.band_margin, W, A.band_floor, bs_cap), band_min);
                     for (int att = 0;; ++att) {
+                        V.B.band_strips = bs;
+                        if (t == 0) { prof[47] += (unsigned long long)bs; prof[48] += 1; }
 #ifdef SXG_EXP
                         // (development: a sweep with parts switched off in front of the real one -- see dp_fill_p16's EXP)
                         if (att == 0) { res = dp_fill_p16<W, CVX, SW, CB, (RM == 2 && CB == 2 && TMAX <= 128) ? ((TMAX == 64 && W <= 11) ? 2 : 1) : 0, (RM == 2 && CB == 2 && TMAX <= 512 && SXG_TFIX_OK(TMAX)) ? TMAX : 0, DS, SXG_EXP>(S, V.R, N, seq, len, V.B, smem); __syncthreads(); if (res.best == 0x7fffffff) break; }
@@ -293,9 +308,20 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                         for (int r2 = t; r2 < mrow; r2 += T) V.R.meta[8 * (size_t)r2 + 7] += mdelta;
                         for (int i2 = t; i2 < len; i2 += T) V.G.posnode[i2] = -1;
                         if (t == 0) prof[27] += 1;
+                        band_min = bs = min(plane_round4(2 * bs), bs_cap);
                         __syncthreads();
                     }
                     if (status != ST_OK) break;
+                    // drift of this walk: |DP column - backbone hint| of every aligned letter (column j + 1 aligns to
+                    // node posnode[j], whose row's hint is its xpos)
+                    if (A.band_floor > 0 && bs_cap < 2 * T) {
+                        int d = 0;
+                        for (int j2 = t; j2 < len; j2 += T) {
+                            const int v = V.G.posnode[j2];
+                            if (v >= 0) d = max(d, abs(j2 + 1 - V.G.xpos[v]));
+                        }
+                        band_drift = max(band_drift, ctx.reduce_max(d));
+                    }
                 } else {
                     dp_fill<W, CVX, H16, SW>(S, V.R, N, seq, len, V.B, smem, A.park_in_lds != 0, A.pf_off, res);
                     __syncthreads();

@@ -669,6 +669,21 @@ static int plane_strips_p16(int T, int W) {
     return p16_band_strips(T, W);
 }
 
+// Adaptive band of the packed sweep (BlockArgs::band_floor): the later alignments of a block keep
+// 2 (ceil((drift + margin) / W) + 1) strips per plane row, at least `floor`, at most the layout's.  SXG_POA_BAND_ADAPT =
+// "floor,margin,full" sets the three (full: alignments of a block that keep the layout's width); "0" keeps the layout's width
+// for every alignment -- the fixed band, a test knob: the adaptive band changes speed, never results.
+static void band_adapt_args(BlockArgs& A) {
+    A.band_floor = P16_BAND_FLOOR; A.band_margin = P16_BAND_MARGIN; A.band_full = P16_BAND_FULL;
+    if (const char* e = getenv("SXG_POA_BAND_ADAPT")) {
+        int f = 0, m = A.band_margin, n = A.band_full;
+        const int k = sscanf(e, "%d,%d,%d", &f, &m, &n);
+        A.band_floor = k >= 1 && f > 0 ? plane_round4(f) : 0;
+        if (k >= 2) A.band_margin = std::max(m, 0);
+        if (k >= 3) A.band_full = std::max(n, 0);
+    }
+}
+
 static void prepare_plan(sxg_poa_handle* h, LaunchPlan& P, int attempt) {
     const Variant V = P.variant;
     const int Lpad = V.Lpad();
@@ -803,6 +818,7 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     A.est = R.est.as<unsigned long long>();
     A.blk_cycles = h->d_blk_cycles.as<unsigned long long>();
     A.lds_bytes = getenv("SXG_POA_RESORT_NO_LDS") ? 0 : P.smem;   // (test knob: the S7' re-sort keeps its states in the slot's scratch, as it does for graphs beyond its LDS)
+    band_adapt_args(A);
     // every slot's header (counters, phase times, clock readings) starts a launch at zero: one strided memset
     HIPCHK(hipMemset2DAsync(R.arena.as<uint8_t>() + P.lay.hdr, P.lay.total, 0, 512, (size_t)P.n_slots, R.stream));
     HIPCHK(hipStreamWaitEvent(R.stream, h->ev0, 0));
@@ -824,6 +840,16 @@ static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt)
         unsigned long long st = 0;
         for (int k = 0; k < 6; ++k) st += one[k];
         smin = std::min(smin, st); smax = std::max(smax, st);
+    }
+    if (V.RM == 2) {   // packed sweep: the width of the plane rows the sweeps kept (adaptive band) and the hint-shift repeats
+        unsigned long long rep = 0, wsum = 0, nsw = 0;
+        for (int64_t sl = 0; sl < P.n_slots; ++sl) {
+            unsigned long long v[49];
+            HIPCHK(hipMemcpy(v, R.arena.as<uint8_t>() + (size_t)sl * P.lay.total + P.lay.hdr + 64, sizeof(v), hipMemcpyDeviceToHost));
+            rep += v[27]; wsum += v[47]; nsw += v[48];
+        }
+        fprintf(stderr, "[sxg]   band: %llu sweeps, mean width %.1f strips of %d (%.0f columns), %llu hint-shift repeats\n", nsw,
+                (double)wsum / (double)std::max(nsw, 1ull), P.lay.band_strips, (double)wsum / (double)std::max(nsw, 1ull) * V.W, rep);
     }
     if (const char* path = getenv("SXG_POA_SLOT_CSV")) {  // per-slot placement and wall-clock span
         if (FILE* f = fopen(path, "a")) {
