@@ -5,10 +5,11 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(CSRC, "libsxgpoa.so")
-# sxg_poa.hip: host side of the C ABI; kern_part*.hip: the kernel classes in parts (poa_kern_tables.hip.h), one translation
-# unit each so that they compile side by side
-SOURCES = ["sxg_poa.hip"] + ["kern_part%d.hip" % k for k in range(1, 10)]
-DEPS = SOURCES + ["poa_kernels.hip.h", "poa_kern_tables.hip.h", "poa_dp.hip.h", "poa_dp16.hip.h", "poa_rowcode.h", "poa_band16.hip.h", "poa_graph_dev.h",
+# sxg_poa.hip: host side of the C ABI; kern_part.hip: the kernel classes, compiled once per part of the class list
+# (poa_classes.h, -DSXG_KERN_PART=k -> build/kern_partK.o) so that the parts compile side by side
+KERN_PARTS = range(1, 10)
+SOURCES = [("sxg_poa.hip", "sxg_poa.o", [])] + [("kern_part.hip", "kern_part%d.o" % k, ["-DSXG_KERN_PART=%d" % k]) for k in KERN_PARTS]
+DEPS = ["sxg_poa.hip", "kern_part.hip", "poa_classes.h", "poa_kernels.hip.h", "poa_kern_tables.hip.h", "poa_dp.hip.h", "poa_dp16.hip.h", "poa_rowcode.h", "poa_band16.hip.h", "poa_graph_dev.h",
                   "poa_bgraph_dev.h", "poa_types.h", os.path.join("..", "..", "include", "sxg_poa.h")]
 OBJ_DIR = os.path.join(CSRC, "build")
 
@@ -32,9 +33,9 @@ def build(force=False, verbose=False):
     failed = None
     while pending or running:
         while pending and len(running) < jobs and failed is None:
-            src = pending.pop(0)
-            obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
-            cmd = [hipcc] + flags + ["-c", "-o", obj, os.path.join(CSRC, src)]
+            src, obj, defs = pending.pop(0)
+            obj = os.path.join(OBJ_DIR, obj)
+            cmd = [hipcc] + flags + defs + ["-c", "-o", obj, os.path.join(CSRC, src)]
             if verbose:
                 print(" ".join(cmd), flush=True)
             running.append((subprocess.Popen(cmd), cmd))

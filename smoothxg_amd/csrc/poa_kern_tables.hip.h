@@ -1,198 +1,100 @@
-// poa_kern_tables.hip.h -- kernel classes by launch geometry.
+// poa_kern_tables.hip.h -- from a launch geometry to its kernel.
 //
-// The engine has ~300 kernel instantiations (strip width x workgroup size x gap model x alignment mode x plane cell
-// format, block and align-only kernels): compiled in ONE translation unit they cost three minutes of hipcc.  The classes
-// are therefore instantiated in PARTS, each in a translation unit of its own (kern_*.hip: `#define SXG_KERN_PART n` and
-// this header) that smoothxg_amd/build.py compiles in parallel; sxg_poa.hip only sees the declarations.  Development
-// builds of a single packed class (-DSXG_DEV_ONLY_W=<w> -DSXG_DEV_ONLY_TMAX=<t>: seconds) compile sxg_poa.hip alone.
-//
-//   part 1   32-bit sweeps (row modes 0, 1), block and align-only kernels; the banded one-wave sweep (row mode 3)
-//   part 2   packed sweep (row mode 2), block kernels, 2-byte delta plane cells, workgroups of up to 4 waves
-//   part 3   ... 8 and 16 waves
-//   part 4   packed sweep, block kernels, 4-byte plane cells (score sets whose deltas do not fit 16 bits), up to 4 waves
-//   part 5   ... 8 and 16 waves
-//   part 6   packed sweep, align-only kernels (4-byte cells)
-//   part 7   packed sweep, block kernels, 2-byte cells, two-wave workgroups (TMAX = 128: with part 8 the classes that may read
-//            stored rows back from a full-width plane and batch their graph phases 8 / 16 elements per thread)
-//   part 8   ... one-wave workgroups (TMAX = 64: no wave-to-wave hand-over compiled in)
-//   part 9   packed sweep, block kernels, 2-byte cells, three-wave workgroups (TMAX = 192)
-// The 2-byte classes of up to eight waves run at EXACTLY TMAX threads, and the sweep is compiled for that thread count (1.6 % on the
-// headline; the two-wave class measured 1 % slower that way and keeps reading it at run time); the 4-byte classes and the 16-wave
-// ones take their thread count at run time.
+// The engine has ~560 kernel instantiations (strip width x workgroup size x gap model x alignment mode x plane cell
+// format, block and align-only kernels): compiled in ONE translation unit they cost minutes of hipcc.  The list of classes,
+// kClasses in poa_classes.h, therefore assigns every class to a PART; kern_part.hip, compiled once per part with
+// -DSXG_KERN_PART=<k> by smoothxg_amd/build.py (in parallel), instantiates the rows of its part and defines that part's
+// entry points, sxg_part_kernel<BlockArgs / AlignArgs, k>; sxg_poa.hip only sees their declaration.  What a class is compiled
+// for (thread count, plane read-back, launch bounds) is class_traits in poa_classes.h.
+// Development builds of a single packed class (-DSXG_DEV_ONLY_W=<w> -DSXG_DEV_ONLY_TMAX=<t>, -DSXG_DEV_CB4: its 4-byte cells
+// too; seconds) compile sxg_poa.hip alone: the same list, filtered, with every part in that one translation unit.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "poa_kernels.hip.h"
 
-// A launch geometry: W columns per strip, NW waves (T = 64*NW), kernel class TMAX, row mode RM
-// (2 = packed sweep: two strips per lane), CB = bytes per plane cell of the packed sweep (poa_dp16.hip.h).
-struct Variant {
-    int W, NW, TMAX, RM;
-    int CB = 4;
-    bool DS = false;   // the class compiled for smoothxg's default scores (packed sweep, 2-byte cells, convex)
-    int T() const { return 64 * NW; }
-    int Lpad() const { return 64 * NW * W * (RM >= 2 ? 2 : 1); }
-};
-
 template <class Args> using KernelFn = void (*)(const Args);
+template <class Args> constexpr ClassKind kind_of = std::is_same_v<Args, AlignArgs> ? CLASS_ALIGN : CLASS_BLOCK;
 
-KernelFn<BlockArgs> sxg_block_kernel_part1(const Variant& v, bool cvx, bool sw);
-KernelFn<AlignArgs> sxg_align_kernel_part1(const Variant& v, bool cvx, bool sw);
-KernelFn<BlockArgs> sxg_block_kernel_part2(const Variant& v, bool cvx, bool sw);
-KernelFn<BlockArgs> sxg_block_kernel_part3(const Variant& v, bool cvx, bool sw);
-KernelFn<BlockArgs> sxg_block_kernel_part4(const Variant& v, bool cvx, bool sw);
-KernelFn<BlockArgs> sxg_block_kernel_part5(const Variant& v, bool cvx, bool sw);
-KernelFn<AlignArgs> sxg_align_kernel_part6(const Variant& v, bool cvx, bool sw);
-KernelFn<BlockArgs> sxg_block_kernel_part7(const Variant& v, bool cvx, bool sw);
-KernelFn<BlockArgs> sxg_block_kernel_part8(const Variant& v, bool cvx, bool sw);
-KernelFn<BlockArgs> sxg_block_kernel_part9(const Variant& v, bool cvx, bool sw);
+// the kernel of part PART for geometry v (nullptr: not a class of this part)
+template <class Args, int PART> KernelFn<Args> sxg_part_kernel(const Variant& v, bool cvx, bool sw);
 
 #if defined(SXG_KERN_PART) || defined(SXG_DEV_ONLY_W)
-template <int TMAX, int W, int RM, int CB = 4> static KernelFn<BlockArgs> pick_block(bool cvx, bool sw, bool ds = false) {
-    if constexpr (RM == 2 && CB == 2) {
-        if (cvx && ds) return sw ? poa_block_kernel<TMAX, W, true, RM, true, CB, true> : poa_block_kernel<TMAX, W, true, RM, false, CB, true>;
-    }
-    if (cvx) return sw ? poa_block_kernel<TMAX, W, true, RM, true, CB> : poa_block_kernel<TMAX, W, true, RM, false, CB>;
-    return sw ? poa_block_kernel<TMAX, W, false, RM, true, CB> : poa_block_kernel<TMAX, W, false, RM, false, CB>;
-}
-template <int TMAX, int W, int CB> static KernelFn<BlockArgs> pick_block_sw(bool cvx, bool ds) {   // (packed, local alignment only)
-    if constexpr (CB == 2) {
-        if (cvx && ds) return poa_block_kernel<TMAX, W, true, 2, true, CB, true>;
-    }
-    return cvx ? poa_block_kernel<TMAX, W, true, 2, true, CB> : poa_block_kernel<TMAX, W, false, 2, true, CB>;
-}
-template <int TMAX, int W, int RM> static KernelFn<AlignArgs> pick_align(bool cvx, bool sw) {
-    if (cvx) return sw ? poa_align_kernel<TMAX, W, true, RM, true> : poa_align_kernel<TMAX, W, true, RM, false>;
-    return sw ? poa_align_kernel<TMAX, W, false, RM, true> : poa_align_kernel<TMAX, W, false, RM, false>;
-}
-#define SXG_PICK(FN, TM, Wd)                                             \
-    do {                                                                 \
-        if (v.TMAX == TM && v.W == Wd) {                                 \
-            if (v.RM == 0) return FN<TM, Wd, 0>(cvx, sw);                \
-            if (v.RM == 1) return FN<TM, Wd, 1>(cvx, sw);                \
-        }                                                                \
-    } while (0)
-#define SXG_PICK16B(TM, Wd, CBv) \
-    do { if (v.TMAX == TM && v.W == Wd && v.RM == 2 && v.CB == CBv) return pick_block<TM, Wd, 2, CBv>(cvx, sw, v.DS); } while (0)
-// (the long classes exist for local alignment only: a global score of such lengths does not fit int16)
-#define SXG_PICK16B_SW(TM, Wd, CBv) \
-    do { if (v.TMAX == TM && v.W == Wd && v.RM == 2 && v.CB == CBv && sw) return pick_block_sw<TM, Wd, CBv>(cvx, v.DS); } while (0)
-#define SXG_PICK16A(TM, Wd) \
-    do { if (v.TMAX == TM && v.W == Wd && v.RM == 2) return pick_align<TM, Wd, 2>(cvx, sw); } while (0)
-#define SXG_PICK16A_SW(TM, Wd) \
-    do { if (v.TMAX == TM && v.W == Wd && v.RM == 2 && sw) return cvx ? poa_align_kernel<TM, Wd, true, 2, true> : poa_align_kernel<TM, Wd, false, 2, true>; } while (0)
-#endif
-
-#if defined(SXG_DEV_ONLY_W)
-// development: ONE packed class, both cell formats, everything in the including translation unit
-KernelFn<BlockArgs> sxg_block_kernel_part1(const Variant&, bool, bool) { return nullptr; }
-KernelFn<AlignArgs> sxg_align_kernel_part1(const Variant&, bool, bool) { return nullptr; }
-KernelFn<BlockArgs> sxg_block_kernel_part2(const Variant& v, bool cvx, bool sw) { SXG_PICK16B(SXG_DEV_ONLY_TMAX, SXG_DEV_ONLY_W, 2); return nullptr; }
-KernelFn<BlockArgs> sxg_block_kernel_part3(const Variant&, bool, bool) { return nullptr; }
+// is the class <row R, width W, row mode RM> instantiated in this translation unit's part PART?
+template <class Args, int PART, int R, int W, int RM> constexpr bool class_here() {
+    constexpr ClassRow c = kClasses[R];
+#ifdef SXG_DEV_ONLY_W
 #ifdef SXG_DEV_CB4
-KernelFn<BlockArgs> sxg_block_kernel_part4(const Variant& v, bool cvx, bool sw) { SXG_PICK16B(SXG_DEV_ONLY_TMAX, SXG_DEV_ONLY_W, 4); return nullptr; }
+    constexpr bool dev = c.kind == CLASS_BLOCK && RM == 2 && c.tmax == SXG_DEV_ONLY_TMAX && W == SXG_DEV_ONLY_W;
 #else
-KernelFn<BlockArgs> sxg_block_kernel_part4(const Variant&, bool, bool) { return nullptr; }
+    constexpr bool dev = c.kind == CLASS_BLOCK && RM == 2 && c.cb == 2 && c.tmax == SXG_DEV_ONLY_TMAX && W == SXG_DEV_ONLY_W;
 #endif
-KernelFn<BlockArgs> sxg_block_kernel_part5(const Variant&, bool, bool) { return nullptr; }
-KernelFn<AlignArgs> sxg_align_kernel_part6(const Variant&, bool, bool) { return nullptr; }
-KernelFn<BlockArgs> sxg_block_kernel_part7(const Variant& v, bool cvx, bool sw) { return sxg_block_kernel_part2(v, cvx, sw); }
-KernelFn<BlockArgs> sxg_block_kernel_part8(const Variant& v, bool cvx, bool sw) { return sxg_block_kernel_part2(v, cvx, sw); }
-KernelFn<BlockArgs> sxg_block_kernel_part9(const Variant& v, bool cvx, bool sw) { return sxg_block_kernel_part2(v, cvx, sw); }
-#elif defined(SXG_KERN_PART)
-#if SXG_KERN_PART == 1
-KernelFn<BlockArgs> sxg_block_kernel_part1(const Variant& v, bool cvx, bool sw) {
-    if (v.RM == 3) {   // banded: the strip width is part of the semantics (decree B2), never merged or widened
-        if (v.CB == 2 && sw) {   // (round 6) 2-byte band cells: local alignment, score sets whose delta code fits 16 bits
-            if (v.W == 6) return cvx ? poa_block_kernel<64, 6, true, 3, true, 2> : poa_block_kernel<64, 6, false, 3, true, 2>;
-            if (v.W == 8) return cvx ? poa_block_kernel<64, 8, true, 3, true, 2> : poa_block_kernel<64, 8, false, 3, true, 2>;
-            return cvx ? poa_block_kernel<64, 11, true, 3, true, 2> : poa_block_kernel<64, 11, false, 3, true, 2>;
+#else
+    constexpr bool dev = true;
+#endif
+    return dev && c.part == PART && c.kind == kind_of<Args> && (c.widths & cw(W)) != 0 && (c.rms & cw(RM)) != 0;
+}
+template <class Args, int R, int W, int RM, bool CVX, bool SW, bool DS> static KernelFn<Args> class_kernel() {
+    constexpr ClassRow c = kClasses[R];
+    if constexpr (std::is_same_v<Args, AlignArgs>) return poa_align_kernel<c.tmax, W, CVX, RM, SW>;
+    else return poa_block_kernel<c.tmax, W, CVX, RM, SW, c.cb, DS>;
+}
+// the kernel of a class for (cvx, sw, ds): only the modes its row lists are instantiated
+template <class Args, int R, int W, int RM> static KernelFn<Args> pick_mode(bool cvx, bool sw, bool ds) {
+    constexpr unsigned m = kClasses[R].modes;
+    if constexpr ((m & CLS_DS) != 0) {
+        if (cvx && ds) {
+            if constexpr ((m & CLS_LOCAL) != 0) if (sw) return class_kernel<Args, R, W, RM, true, true, true>();
+            if constexpr ((m & CLS_GLOBAL) != 0) if (!sw) return class_kernel<Args, R, W, RM, true, false, true>();
         }
-        if (v.W == 6) return pick_block<64, 6, 3>(cvx, sw);
-        if (v.W == 8) return pick_block<64, 8, 3>(cvx, sw);
-        return pick_block<64, 11, 3>(cvx, sw);
     }
-    SXG_PICK(pick_block, 256, 8); SXG_PICK(pick_block, 256, 12); SXG_PICK(pick_block, 256, 16);
-    SXG_PICK(pick_block, 512, 8); SXG_PICK(pick_block, 512, 12); SXG_PICK(pick_block, 512, 16);
-    SXG_PICK(pick_block, 1024, 8); SXG_PICK(pick_block, 1024, 12);
+    if (cvx) {
+        if constexpr ((m & CLS_LOCAL) != 0) if (sw) return class_kernel<Args, R, W, RM, true, true, false>();
+        if constexpr ((m & CLS_GLOBAL) != 0) if (!sw) return class_kernel<Args, R, W, RM, true, false, false>();
+    } else {
+        if constexpr ((m & CLS_LOCAL) != 0) if (sw) return class_kernel<Args, R, W, RM, false, true, false>();
+        if constexpr ((m & CLS_GLOBAL) != 0) if (!sw) return class_kernel<Args, R, W, RM, false, false, false>();
+    }
     return nullptr;
 }
-KernelFn<AlignArgs> sxg_align_kernel_part1(const Variant& v, bool cvx, bool sw) {
-    SXG_PICK(pick_align, 256, 8); SXG_PICK(pick_align, 256, 12); SXG_PICK(pick_align, 256, 16);
-    SXG_PICK(pick_align, 512, 8); SXG_PICK(pick_align, 512, 12); SXG_PICK(pick_align, 512, 16);
-    SXG_PICK(pick_align, 1024, 8); SXG_PICK(pick_align, 1024, 12);
-    return nullptr;
+// One selector: rows x widths x row modes, folded at compile time.  (Each level is folded from its LAST element to its first: the
+// compiler emits the kernels of a translation unit in the reverse order of these references, and the order of kernels inside a code
+// object is kept as it was when the classes were spelled out one by one -- inlining and register allocation of the shared
+// out-of-line functions depend on it.)
+template <int N, int... I> using rev_seq = std::integer_sequence<int, (N - 1 - I)...>;
+template <int N, int... I> constexpr rev_seq<N, I...> rev_of(std::integer_sequence<int, I...>) { return {}; }
+template <int N> constexpr auto rev_range() { return rev_of<N>(std::make_integer_sequence<int, N>()); }
+template <class Args, int PART, int R, int W, int... RM> static void pick_rm(KernelFn<Args>& k, int row, const Variant& v, bool cvx, bool sw, std::integer_sequence<int, RM...>) {
+    ((void)([&] { if constexpr (class_here<Args, PART, R, W, RM>()) if (row == R && v.W == W && v.RM == RM) k = pick_mode<Args, R, W, RM>(cvx, sw, v.DS); }()), ...);
 }
-#elif SXG_KERN_PART == 2 || SXG_KERN_PART == 4
-#if SXG_KERN_PART == 2
-#define SXG_PART_CB 2
-KernelFn<BlockArgs> sxg_block_kernel_part2(const Variant& v, bool cvx, bool sw) {
-#else
-#define SXG_PART_CB 4
-KernelFn<BlockArgs> sxg_block_kernel_part4(const Variant& v, bool cvx, bool sw) {
-#endif
-    SXG_PICK16B(256, 4, SXG_PART_CB); SXG_PICK16B(256, 5, SXG_PART_CB); SXG_PICK16B(256, 6, SXG_PART_CB); SXG_PICK16B(256, 7, SXG_PART_CB);
-    SXG_PICK16B(256, 8, SXG_PART_CB); SXG_PICK16B(256, 9, SXG_PART_CB); SXG_PICK16B(256, 10, SXG_PART_CB);
-    SXG_PICK16B(256, 11, SXG_PART_CB); SXG_PICK16B(256, 12, SXG_PART_CB);
-    return nullptr;
+template <class Args, int PART, int R, int... Wo> static void pick_width(KernelFn<Args>& k, int row, const Variant& v, bool cvx, bool sw, std::integer_sequence<int, Wo...>) {
+    (pick_rm<Args, PART, R, CLASS_W_MIN + Wo>(k, row, v, cvx, sw, rev_range<CLASS_RM_MAX + 1>()), ...);
 }
-#elif SXG_KERN_PART == 3 || SXG_KERN_PART == 5
-#if SXG_KERN_PART == 3
-#define SXG_PART_CB 2
-KernelFn<BlockArgs> sxg_block_kernel_part3(const Variant& v, bool cvx, bool sw) {
-#else
-#define SXG_PART_CB 4
-KernelFn<BlockArgs> sxg_block_kernel_part5(const Variant& v, bool cvx, bool sw) {
-#endif
-    SXG_PICK16B(512, 8, SXG_PART_CB); SXG_PICK16B(512, 9, SXG_PART_CB); SXG_PICK16B(512, 10, SXG_PART_CB);
-    SXG_PICK16B(512, 11, SXG_PART_CB); SXG_PICK16B(512, 12, SXG_PART_CB);
-    SXG_PICK16B(1024, 8, SXG_PART_CB);
-    SXG_PICK16B_SW(1024, 10, SXG_PART_CB); SXG_PICK16B_SW(1024, 12, SXG_PART_CB); SXG_PICK16B_SW(1024, 13, SXG_PART_CB);
-    return nullptr;
+template <class Args, int PART, int... R> static KernelFn<Args> pick_class(const Variant& v, bool cvx, bool sw, std::integer_sequence<int, R...>) {
+    KernelFn<Args> k = nullptr;
+    const int row = class_row(kind_of<Args>, v, sw);
+    (pick_width<Args, PART, R>(k, row, v, cvx, sw, rev_range<CLASS_W_MAX - CLASS_W_MIN + 1>()), ...);
+    return k;
 }
-#elif SXG_KERN_PART == 7
-KernelFn<BlockArgs> sxg_block_kernel_part7(const Variant& v, bool cvx, bool sw) {
-    SXG_PICK16B(128, 4, 2); SXG_PICK16B(128, 5, 2); SXG_PICK16B(128, 6, 2); SXG_PICK16B(128, 7, 2);
-    SXG_PICK16B(128, 8, 2); SXG_PICK16B(128, 9, 2); SXG_PICK16B(128, 10, 2);
-    SXG_PICK16B(128, 11, 2); SXG_PICK16B(128, 12, 2);
-    return nullptr;
-}
-#elif SXG_KERN_PART == 8
-KernelFn<BlockArgs> sxg_block_kernel_part8(const Variant& v, bool cvx, bool sw) {
-    SXG_PICK16B(64, 4, 2); SXG_PICK16B(64, 5, 2); SXG_PICK16B(64, 6, 2); SXG_PICK16B(64, 7, 2);
-    SXG_PICK16B(64, 8, 2); SXG_PICK16B(64, 9, 2); SXG_PICK16B(64, 10, 2);
-    SXG_PICK16B(64, 11, 2); SXG_PICK16B(64, 12, 2);
-    return nullptr;
-}
-#elif SXG_KERN_PART == 9
-KernelFn<BlockArgs> sxg_block_kernel_part9(const Variant& v, bool cvx, bool sw) {
-    SXG_PICK16B(192, 4, 2); SXG_PICK16B(192, 5, 2); SXG_PICK16B(192, 6, 2); SXG_PICK16B(192, 7, 2);
-    SXG_PICK16B(192, 8, 2); SXG_PICK16B(192, 9, 2); SXG_PICK16B(192, 10, 2);
-    SXG_PICK16B(192, 11, 2); SXG_PICK16B(192, 12, 2);
-    return nullptr;
-}
-#elif SXG_KERN_PART == 6
-KernelFn<AlignArgs> sxg_align_kernel_part6(const Variant& v, bool cvx, bool sw) {
-    SXG_PICK16A(256, 4); SXG_PICK16A(256, 5); SXG_PICK16A(256, 6); SXG_PICK16A(256, 7);
-    SXG_PICK16A(256, 8); SXG_PICK16A(256, 9); SXG_PICK16A(256, 10);
-    SXG_PICK16A(256, 11); SXG_PICK16A(256, 12);
-    SXG_PICK16A(512, 8); SXG_PICK16A(512, 9); SXG_PICK16A(512, 10);
-    SXG_PICK16A(512, 11); SXG_PICK16A(512, 12);
-    SXG_PICK16A(1024, 8);
-    SXG_PICK16A_SW(1024, 10); SXG_PICK16A_SW(1024, 12); SXG_PICK16A_SW(1024, 13);
-    return nullptr;
+template <class Args, int PART> KernelFn<Args> sxg_part_kernel(const Variant& v, bool cvx, bool sw) {
+    return pick_class<Args, PART>(v, cvx, sw, rev_range<kNumClasses>());
 }
 #endif
+#ifdef SXG_KERN_PART
+template KernelFn<BlockArgs> sxg_part_kernel<BlockArgs, SXG_KERN_PART>(const Variant&, bool, bool);
+template KernelFn<AlignArgs> sxg_part_kernel<AlignArgs, SXG_KERN_PART>(const Variant&, bool, bool);
 #endif
 
-// the kernel class of a geometry (nullptr: none built)
-static inline KernelFn<BlockArgs> block_kernel(const Variant& v, bool cvx, bool sw) {
-    if (v.RM != 2) return sxg_block_kernel_part1(v, cvx, sw);
-    if (v.CB == 2) return v.TMAX <= 64 ? sxg_block_kernel_part8(v, cvx, sw) : v.TMAX <= 128 ? sxg_block_kernel_part7(v, cvx, sw) : v.TMAX <= 192 ? sxg_block_kernel_part9(v, cvx, sw) : (v.TMAX <= 256 ? sxg_block_kernel_part2(v, cvx, sw) : sxg_block_kernel_part3(v, cvx, sw));
-    Variant u = v;
-    if (u.TMAX < 256) u.TMAX = 256;   // (4-byte cells: no class of its own for one and two waves)
-    return u.TMAX <= 256 ? sxg_block_kernel_part4(u, cvx, sw) : sxg_block_kernel_part5(u, cvx, sw);
+#ifndef SXG_KERN_PART
+// host side: the kernel class of a geometry, exactly the class v names (nullptr: none built)
+// (kept out of the parts' translation units: there it would instantiate every part's entry point, and with it every class)
+template <class Args, int... P> static KernelFn<Args> kernel_of(const Variant& v, bool cvx, bool sw, std::integer_sequence<int, P...>) {
+    const int row = class_row(kind_of<Args>, v, sw);
+    KernelFn<Args> k = nullptr;
+    if (row >= 0) ((void)(kClasses[row].part == P + 1 ? (k = sxg_part_kernel<Args, P + 1>(v, cvx, sw), 0) : 0), ...);
+    return k;
 }
-static inline KernelFn<AlignArgs> align_kernel(const Variant& v, bool cvx, bool sw) {
-    Variant u = v;
-    if (u.RM == 2 && u.TMAX < 256) u.TMAX = 256;
-    return u.RM != 2 ? sxg_align_kernel_part1(u, cvx, sw) : sxg_align_kernel_part6(u, cvx, sw);
-}
+static inline KernelFn<BlockArgs> block_kernel(const Variant& v, bool cvx, bool sw) { return kernel_of<BlockArgs>(v, cvx, sw, std::make_integer_sequence<int, CLASS_PARTS>()); }
+static inline KernelFn<AlignArgs> align_kernel(const Variant& v, bool cvx, bool sw) { return kernel_of<AlignArgs>(v, cvx, sw, std::make_integer_sequence<int, CLASS_PARTS>()); }
+#endif

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/sxg_poa.h"
+#include "poa_classes.h"
 #include "poa_dp.hip.h"
 #include "poa_dp16.hip.h"
 #include "poa_band16.hip.h"
@@ -166,25 +167,16 @@ struct BlockArgs {
 // RM = row mode: 0 = 32-bit sweep with int16 row words, 1 = 32-bit sweep with int32 row words,
 // 2 = packed-int16 sweep (poa_dp16.hip.h; two strips per lane, W <= 12),
 // 3 = banded packed sweep (poa_band16.hip.h; one wave, a sliding window of 128 strips of W = 6, 8 or 11 columns).
-__host__ __device__ constexpr int sxg_min_waves(int TMAX, int W, int RM) {
-#ifdef SXG_DEV_WAVES
-    return SXG_DEV_WAVES;
-#endif
-    // (packed sweep: 128 VGPRs hold up to 13 columns per strip since round 2 -- two 8-wave workgroups share a CU)
-    return TMAX > 512 ? 4 : (RM == 2 ? 4 : (W <= 12 ? 4 : 3));
-}
+// What a class is compiled for beyond its parameters is class_traits (poa_classes.h).
+__host__ __device__ constexpr int sxg_min_waves(int TMAX, int W, int RM) { return class_traits(TMAX, W, RM, 4).min_waves; }
 
 // CB: bytes per cell of the packed sweep's traceback plane (poa_dp16.hip.h: 2 = delta codes, 4 = H and the two distances)
-#ifdef SXG_DEV_TFIX128
-#define SXG_TFIX_OK(tm) true
-#else
-#define SXG_TFIX_OK(tm) ((tm) != 128)   /* (the two-wave class measured 1 % slower with a compile-time thread count) */
-#endif
 // DS: packed sweep compiled for smoothxg's default scores (see dp_fill_p16); the host launches it only for blocks that have them
 template <int TMAX, int W, bool CVX, int RM, bool SW, int CB = 4, bool DS = false>
 __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_kernel(const BlockArgs A) {
     constexpr bool H16 = RM != 1;
     constexpr int CPL = RM >= 2 ? 2 * W : W;  // columns per lane
+    constexpr ClassTraits CT = class_traits(TMAX, W, RM, CB);
     const int T = (int)blockDim.x;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int* lds = (int*)smem;
@@ -245,8 +237,8 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                 const int band_mode = RM == 3 ? (int)A.params[A.per_block_params ? b : 0].banded : 0;   // 1 = B2, 2 = adaptive (B4)
                 // (workgroups of one and two waves take more elements per thread and step: see WgCtxT)
                 const int hinted_ = RM == 3 ? (band_mode == 2 ? 3 : 2) : (RM == 2 ? 1 : 0);
-                if (TMAX == 64 || (TMAX <= 128 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; status = prep_rows(c16, V.G, V.R, caps, hinted_); }
-                else if (TMAX == 128) { WgCtxT<8> c8{ctx.lds}; status = prep_rows(c8, V.G, V.R, caps, hinted_); }
+                if (CT.graph_batch == 16 || (CT.graph_batch == 8 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; status = prep_rows(c16, V.G, V.R, caps, hinted_); }
+                else if (CT.graph_batch == 8) { WgCtxT<8> c8{ctx.lds}; status = prep_rows(c8, V.G, V.R, caps, hinted_); }
                 else status = prep_rows(ctx, V.G, V.R, caps, hinted_);
                 if (status != ST_OK) break;
                 PROF(1);
@@ -288,9 +280,9 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                         if (t == 0) { prof[47] += (unsigned long long)bs; prof[48] += 1; }
 #ifdef SXG_EXP
                         // (development: a sweep with parts switched off in front of the real one -- see dp_fill_p16's EXP)
-                        if (att == 0) { res = dp_fill_p16<W, CVX, SW, CB, (RM == 2 && CB == 2 && TMAX <= 128) ? ((TMAX == 64 && W <= 11) ? 2 : 1) : 0, (RM == 2 && CB == 2 && TMAX <= 512 && SXG_TFIX_OK(TMAX)) ? TMAX : 0, DS, SXG_EXP>(S, V.R, N, seq, len, V.B, smem); __syncthreads(); if (res.best == 0x7fffffff) break; }
+                        if (att == 0) { res = dp_fill_p16<W, CVX, SW, CB, CT.rp, CT.tfix, DS, SXG_EXP>(S, V.R, N, seq, len, V.B, smem); __syncthreads(); if (res.best == 0x7fffffff) break; }
 #endif
-                        res = dp_fill_p16<W, CVX, SW, CB, (RM == 2 && CB == 2 && TMAX <= 128) ? ((TMAX == 64 && W <= 11) ? 2 : 1) : 0, (RM == 2 && CB == 2 && TMAX <= 512 && SXG_TFIX_OK(TMAX)) ? TMAX : 0, DS>(S, V.R, N, seq, len, V.B, smem);
+                        res = dp_fill_p16<W, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
                         __syncthreads();
                         PROF(2);
                         if (t == 0) { lds[TBM_FLAG] = 0; lds[TBM_RANGE] = 0; }
@@ -336,8 +328,8 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
             done_cells += (unsigned long long)N * (unsigned long long)len;
             // (spoa's order: the re-sort below rebuilds order and ranks; AddAlignment leaves its own bookkeeping of them out)
             const bool spoa_order = (A.params[A.per_block_params ? b : 0].mode & SXG_ORDER_SPOA) != 0;
-            if (TMAX == 64 || (TMAX <= 128 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; add_alignment(c16, V.G, seq, len, A.weights ? A.weights[s] : 1u, A.paths + so, !spoa_order); }
-            else if (TMAX == 128) { WgCtxT<8> c8{ctx.lds}; add_alignment(c8, V.G, seq, len, A.weights ? A.weights[s] : 1u, A.paths + so, !spoa_order); }
+            if (CT.graph_batch == 16 || (CT.graph_batch == 8 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; add_alignment(c16, V.G, seq, len, A.weights ? A.weights[s] : 1u, A.paths + so, !spoa_order); }
+            else if (CT.graph_batch == 8) { WgCtxT<8> c8{ctx.lds}; add_alignment(c8, V.G, seq, len, A.weights ? A.weights[s] : 1u, A.paths + so, !spoa_order); }
             else add_alignment(ctx, V.G, seq, len, A.weights ? A.weights[s] : 1u, A.paths + so, !spoa_order);
             if (spoa_order) {   // S7': spoa's depth-first re-sort (every thread walks its roots: poa_graph_dev.h)
                 typedef __attribute__((address_space(3))) uint8_t lds_u8;

@@ -145,49 +145,6 @@ static int fail(int code, const std::string& msg) {
                         std::string(#x) + ": " + hipGetErrorString(_e));                       \
     } while (0)
 
-// Geometry choice.  Inside a workgroup all waves meet at two barriers per row, so the wave
-// count should load the four SIMDs of a CU evenly: 1, 2, 3, 4, 8, 12 or 16 waves.  Among the
-// (W, NW) pairs that cover the sequence pick the one with the fewest padded columns, then the
-// wider strip (less per-row overhead).  Strip widths are bounded by VGPRs: 32-bit sweep 16
-// columns (~165 VGPRs, <= 512 threads) / 12 (128 VGPRs); packed sweep 12 (~152) / 8 (124).
-// Long local alignments (sequences of 12-26 kbp: smoothxg runs with -l 13k cut at 2 * 13k) get 16-wave workgroups of the
-// packed sweep with 10, 12 or 13 columns per strip (128 VGPRs, a handful of spill slots): 20 480 / 24 576 / 26 624 columns.
-static bool variant_for_len(int maxlen, int rm, Variant* v, bool sw = false) {
-    static const int kNW[] = {1, 2, 3, 4, 8, 12, 16};
-    if (rm == 2) {   // development knob: SXG_POA_FORCE_P16="W,NW" forces one packed geometry (A/B runs of a single-class build)
-        if (const char* e = getenv("SXG_POA_FORCE_P16")) {
-            int fw = 0, fnw = 0;
-            if (sscanf(e, "%d,%d", &fw, &fnw) == 2 && 128L * fnw * fw >= maxlen + 1 && (fnw <= 4 || fnw == 8 || fnw == 12 || fnw == 16)) {
-                *v = Variant{fw, fnw, fnw <= 4 ? 64 * fnw : (fnw <= 8 ? 512 : 1024), rm};
-                return true;
-            }
-        }
-    }
-    // (narrow strips, 4-7 columns, for sequences below 1 kbp -- pggb's -l 700 ... 1100 -- in workgroups of up to 4 waves)
-    static const int kW32[] = {16, 12, 8}, kW16[] = {13, 12, 11, 10, 9, 8, 7, 6, 5, 4};
-    const int* ws = rm == 2 ? kW16 : kW32;
-    const int nws = rm == 2 ? 10 : 3;
-    const int need = maxlen + 1;
-    long best_cols = -1;
-    for (int wi = 0; wi < nws; ++wi)
-        for (int NW : kNW) {
-            const int W = ws[wi];
-            const long cols = 64L * NW * W * (rm == 2 ? 2 : 1);
-            if (cols < need) continue;
-            const bool wide = rm == 2 ? W > 8 : W > 12;   // needs > 128 VGPRs unless squeezed
-            const bool long_class = rm == 2 && sw && NW == 16 && (W == 10 || W == 12 || W == 13);
-            if (W == 13 && !long_class) continue;
-            if (rm == 2 && W < 8 && NW > 4) continue;
-            if (wide && NW > 8 && !long_class) continue;
-            if (best_cols < 0 || cols < best_cols) {
-                best_cols = cols;
-                *v = Variant{W, NW, (rm == 2 && NW <= 4) ? 64 * NW : (NW <= 4 ? 256 : (NW <= 8 ? 512 : 1024)), rm};   // (packed: one and two waves have classes of their own)
-            }
-            break;  // larger NW for this W only adds padding
-        }
-    return best_cols >= 0;
-}
-
 // On-chip copies of stored rows a packed-sweep workgroup gets (SlotLayout::lds_rows): what is left of its share of the CU's
 // 160 KB of LDS when as many workgroups share the CU as its registers allow (128 VGPRs: 16 waves per CU).
 // (Round 4: giving the workgroups of a launch that does not fill the chip -- 1000 two-wave blocks: four per CU where eight
@@ -251,6 +208,13 @@ static int row_mode(const Scoring& S, int maxlen, int rows, int at_least = 2, bo
     return 1;
 }
 
+// development knob: SXG_POA_FORCE_P16="W,NW" forces one packed geometry (A/B runs of a single-class build)
+static void forced_p16(int* w, int* nw) {
+    *w = *nw = 0;
+    if (const char* e = getenv("SXG_POA_FORCE_P16"))
+        if (sscanf(e, "%d,%d", w, nw) != 2) *w = *nw = 0;
+}
+
 // SXG_POA_DEBUG: wall-clock laps of the host side (stderr)
 struct HostLaps {
     bool on = getenv("SXG_POA_DEBUG") != nullptr;
@@ -293,6 +257,18 @@ struct BlockMeta {
     bool cvx = false, sw = true;
     Scoring S;
 };
+
+// Row mode (the narrowest >= at_least that holds the block's scores), plane cell format and launch geometry of a block
+// (optimistic: the kernel re-checks -- see score_floor -- and a packed global sweep checks the cells its traceback visits)
+static void classify_block(BlockMeta& m, int at_least, bool clamp_ok) {
+    m.rm = row_mode(m.S, m.maxlen, m.maxlen, at_least, clamp_ok);
+    const int cb = m.rm == 2 ? plane_cell_bytes(m.S) : 4;
+    int fw, fnw;
+    forced_p16(&fw, &fnw);
+    m.fits = variant_for_len(m.maxlen, m.rm, &m.variant, m.S.sw, cb, fw, fnw);
+    m.variant.CB = cb;   // (also of a block that does not fit)
+    m.variant.DS = m.rm == 2 && cb == 2 && p16_default_scores(m.S) && !getenv("SXG_POA_NO_DEFAULT_CLASS");
+}
 
 struct PlanRes {
     DevBuf arena, work, queue, est;
@@ -584,11 +560,7 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
             if (s > in->blk_off[b]) m.cost += (double)len * (l1 + 0.05 * prev);
             prev += (double)len;
         }
-        // (optimistic; the kernel re-checks -- see score_floor -- and a packed global sweep checks the cells its traceback visits)
-        m.rm = row_mode(m.S, m.maxlen, m.maxlen, 2, h->h_params[in->per_block_params ? b : 0].banded == 0);
-        m.fits = variant_for_len(m.maxlen, m.rm, &m.variant, m.S.sw);
-        m.variant.CB = m.rm == 2 ? plane_cell_bytes(m.S) : 4;
-        m.variant.DS = m.rm == 2 && m.variant.CB == 2 && p16_default_scores(m.S) && !getenv("SXG_POA_NO_DEFAULT_CLASS");
+        classify_block(m, 2, h->h_params[in->per_block_params ? b : 0].banded == 0);
         // A11: the reference's abPOA path is banded (wb=311, wf=0.03); local alignments whose scores fit the packed
         // sweep run the one-wave banded kernel, everything else asked to be banded runs the full matrix
         // (global alignment: the adaptive band only -- the band of a row without successors holds the end column by
@@ -596,8 +568,9 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
         const int bnd = h->h_params[in->per_block_params ? b : 0].banded;
         if (bnd && (m.S.sw || bnd == 2) && m.rm == 2 && m.maxlen <= SXG_POA_MAX_SEQ_LEN) {
             m.rm = 3;
-            m.variant = Variant{band_strip_width(m.maxlen), 1, 64, 3};   // decree B2: strip width from the block's longest sequence
-            m.variant.CB = band_cell_bytes(m.S);
+            // decree B2: strip width from the block's longest sequence
+            const int bw = band_strip_width(m.maxlen), bcb = band_cell_bytes(m.S);
+            m.variant = Variant{bw, 1, class_tmax(bw, 1, 3, bcb, true), 3, bcb};
             m.fits = true;
         }
     }
@@ -654,7 +627,7 @@ struct LaunchPlan {
     std::vector<int32_t> work;  // block ids, largest cost first
     std::vector<unsigned long long> est;  // cost-model cells per work item (priority balancing)
     // filled by prepare_plan
-    SlotLayout lay; KernelFn<BlockArgs> kern = nullptr; int per_cu = 1; int64_t want_slots = 0, n_slots = 0;
+    SlotLayout lay; KernelFn<BlockArgs> kern = nullptr; std::string why; int per_cu = 1; int64_t want_slots = 0, n_slots = 0;
     int clock_mhz = 0;   // shader clock this launch ran at, sampled from its slots (see sample_clock)
     int smem = 0, pf_off = -1; bool park_lds = true; uint64_t cells = 0, bytes = 0; float ms = 0;
 };
@@ -728,10 +701,13 @@ static void prepare_plan(sxg_poa_handle* h, LaunchPlan& P, int attempt) {
     P.lay = make_layout(nodes_cap, rows_cap, pool_slots, step_cap, V.T(), Lpad, wb, false,
                         V.RM == 3 ? (any_adaptive ? BAND_WIN : band_plane_strips(maxlen, V.W)) : (V.RM == 2 ? (P.wide_band ? 2 * V.T() : plane_strips_p16(V.T(), V.W)) : 0),
                         V.RM >= 2 ? V.CB : 4, any_spoa);
-    // (the one-wave 2-byte classes up to W = 11 are compiled for a plane that keeps every strip -- dp_fill_p16's RP = 2; a launch whose
-    //  plane was narrowed, SXG_POA_BAND_COLS, runs the two-wave class at 64 threads instead)
-    if (V.RM == 2 && V.CB == 2 && V.TMAX == 64 && V.W <= 11 && P.lay.band_strips != 2 * V.T()) P.variant.TMAX = 128;
+    // (a class compiled for a plane that keeps every strip -- class_traits' rp == 2 -- gives way when the launch's plane was narrowed,
+    //  SXG_POA_BAND_COLS: class_tmax)
+    P.variant.TMAX = class_tmax(V.W, V.NW, V.RM, V.CB, P.lay.band_strips == 2 * V.T());
     P.kern = block_kernel(P.variant, P.cvx, P.sw);
+    const int tfix = class_traits(P.variant.TMAX, V.W, V.RM, V.CB).tfix;
+    if (tfix && tfix != V.T()) { P.kern = nullptr; P.why = "kernel class compiled for " + std::to_string(tfix) + " threads asked to run at " + std::to_string(V.T()); }
+    if (!P.kern && P.why.empty()) P.why = "no kernel class built for this geometry";   // (launch_plan fails this launch)
     P.smem = dp_lds_launch_bytes(Lpad, wb);
     P.park_lds = dp_park_in_lds(Lpad, wb);
     if (V.RM == 2) { P.lay.lds_rows = p16_lds_rows(V.T(), V.W, V.CB); P.smem = dp16_lds_bytes(V.T(), V.W, P.lay.lds_rows, V.CB); P.park_lds = true; }
@@ -765,7 +741,7 @@ static int sample_clock(const LaunchPlan& P, const PlanRes& R) {
 static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int prio_base) {
     const Variant V = P.variant;
     int rc;
-    if (!P.kern) return fail(SXG_E_INVALID, "no kernel class built for this geometry");
+    if (!P.kern) return fail(SXG_E_INVALID, P.why);
     if ((rc = R.arena.ensure((size_t)P.n_slots * P.lay.total))) return rc;
     // Workgroup k runs on CU k mod #CU (measured, profiles/tools/slot_report.py): when the slots do not
     // divide evenly, the CUs with one workgroup less run theirs faster -- they get the costliest blocks, so
@@ -1032,7 +1008,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
             const BlockMeta& m = h->meta[b];
             LaunchPlan* pl = nullptr;
             for (auto& q : plans)
-                if (q.variant.W == m.variant.W && q.variant.NW == m.variant.NW && q.variant.RM == m.variant.RM && q.variant.CB == m.variant.CB && q.variant.DS == m.variant.DS && q.cvx == m.cvx && q.sw == m.sw && q.tier == m.tier && q.wide_band == m.wide_band) { pl = &q; break; }
+                if (q.variant == m.variant && q.cvx == m.cvx && q.sw == m.sw && q.tier == m.tier && q.wide_band == m.wide_band) { pl = &q; break; }
             if (!pl) { plans.emplace_back(); pl = &plans.back(); pl->variant = m.variant; pl->cvx = m.cvx; pl->sw = m.sw; pl->tier = m.tier; pl->wide_band = m.wide_band; }
             pl->work.push_back(b);
         }
@@ -1048,7 +1024,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         for (size_t i = 0; i < plans.size(); ++i)
             for (size_t j = i + 1; j < plans.size();) {
                 const LaunchPlan &a = plans[i], &b = plans[j];
-                if (a.variant.RM == b.variant.RM && a.variant.CB == b.variant.CB && a.variant.DS == b.variant.DS && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
+                if (same_kind(a.variant, b.variant) && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
                     (double)b.variant.Lpad() >= (merge_env > 0 ? merge_env : (a.variant.Lpad() >= 4096 ? 0.92 : 0.75)) * (double)a.variant.Lpad()) {
                     plans[i].work.insert(plans[i].work.end(), b.work.begin(), b.work.end());
                     plans.erase(plans.begin() + (long)j);
@@ -1063,7 +1039,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
                 Variant& v = pl.variant;
                 while (v.RM == 2 && v.NW <= 2 && v.W % 2 == 0 && v.W / 2 >= 4 && 2 * waves <= (uint64_t)h->num_cu * 16u) {
                     waves += (uint64_t)pl.work.size() * (uint64_t)v.NW;
-                    v = Variant{v.W / 2, 2 * v.NW, 64 * 2 * v.NW, 2, v.CB, v.DS};   // (NW 1 -> 2: the two-wave class; 2 -> 4: the four-wave class)
+                    v = Variant{v.W / 2, 2 * v.NW, class_tmax(v.W / 2, 2 * v.NW, 2, v.CB, true), 2, v.CB, v.DS};   // (NW 1 -> 2: the two-wave class; 2 -> 4: the four-wave class)
                 }
             }
         }
@@ -1204,10 +1180,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
             } else if (status[b] == ST_RANGE_OVERFLOW || status[b] == ST_BAND_MISS) {
                 // one step wider at the same capacity tier: packed -> int16 row words -> int32 row words
                 if (m.rm != 1) {
-                    m.rm = row_mode(m.S, m.maxlen, m.maxlen, m.rm >= 2 ? 0 : 1);
-                    m.fits = variant_for_len(m.maxlen, m.rm, &m.variant, m.S.sw);
-                    m.variant.CB = m.rm == 2 ? plane_cell_bytes(m.S) : 4;
-        m.variant.DS = m.rm == 2 && m.variant.CB == 2 && p16_default_scores(m.S) && !getenv("SXG_POA_NO_DEFAULT_CLASS");
+                    classify_block(m, m.rm >= 2 ? 0 : 1, false);
                     if (m.fits) again.push_back(b);
                     else status[b] = ST_TOO_LONG;    // (a score range beyond int16 on a sequence beyond SXG_POA_MAX_SEQ_LEN_WIDE)
                 } else status[b] = ST_TOO_LONG;      // (unreachable: the int32 sweep reports neither)
@@ -2280,11 +2253,13 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
     for (int p = 0; p < n; ++p) {
         const Scoring S = normalise(in->params[in->per_problem_params ? p : 0]);
         const int len = (int)(in->seq_off[p + 1] - in->seq_off[p]), N = (int)(in->row_off[p + 1] - in->row_off[p]);
-        Variant v;
-        if (!variant_for_len(len, row_mode(S, len, N), &v, S.sw)) { o->status[p] = ST_TOO_LONG; continue; }
+        Variant v;   // (the align-only kernels run the 4-byte cells, no default-score class)
+        int fw, fnw;
+        forced_p16(&fw, &fnw);
+        if (!variant_for_len(len, row_mode(S, len, N), &v, S.sw, 4, fw, fnw)) { o->status[p] = ST_TOO_LONG; continue; }
         APlan* pl = nullptr;
         for (auto& q : plans)
-            if (q.variant.W == v.W && q.variant.NW == v.NW && q.variant.RM == v.RM && q.cvx == (bool)S.convex && q.sw == (bool)S.sw) { pl = &q; break; }
+            if (q.variant == v && q.cvx == (bool)S.convex && q.sw == (bool)S.sw) { pl = &q; break; }
         if (!pl) { plans.push_back(APlan{v, (bool)S.convex, (bool)S.sw, {}, 0}); pl = &plans.back(); }
         pl->work.push_back(p);
         pl->rows_cap = std::max(pl->rows_cap, N);
@@ -2301,6 +2276,8 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
                                       (int)maxe + 8, V.T(), V.Lpad(), wb, true, V.RM == 2 ? 2 * V.T() : 0);  // every strip kept
         if (V.RM == 2) lay2.lds_rows = p16_lds_rows(V.T(), V.W, 4);   // (the align-only kernel runs the 4-byte cells)
         auto kern = align_kernel(pl.variant, pl.cvx, pl.sw);
+        const int tfix = class_traits(V.TMAX, V.W, V.RM, V.CB).tfix;
+        if (!kern || (tfix && tfix != V.T())) { cleanup(); sxg_poa_align_free(out); return fail(SXG_E_INVALID, kern ? "kernel class compiled for another thread count" : "no kernel class built for this geometry"); }
         int per_cu = 1;
         int smem = V.RM == 2 ? dp16_lds_bytes(V.T(), V.W, lay2.lds_rows, 4) : dp_lds_launch_bytes(V.Lpad(), wb);
         const int pf_off = (V.RM != 2 && getenv("SXG_POA_PREFETCH")) ? dp_pf_offset(V.Lpad(), wb, V.T()) : -1;
