@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-/* 5: sxg_poa_batch_out gained block_cycles (before _owner): per-block time on the device, the reference's POA_DEBUG column
+/* 5 (addition, no number change: no struct or existing entry point changed): sxg_poa_pair_identity_batch, sxg_poa_split_batch,
+ *    sxg_poa_split_free and their two structs -- the identity split of break_blocks (src/breaks.cpp:335-586) on the device.
+ * 5: sxg_poa_batch_out gained block_cycles (before _owner): per-block time on the device, the reference's POA_DEBUG column
  *    poa.time.ms (src/smooth.cpp:2121-2265); sxg_poa_sharded_timing.
  * 4: block graphs on the device: sxg_poa_batch_in gained want_block_graph / bg_consensus_visited_only / bg_trim at its END
  *    (callers must zero-initialise the struct, as before), sxg_poa_batch_out the bg_* arrays before _owner; stats.bg_ms.
@@ -321,6 +323,56 @@ int sxg_poa_batch_run_sharded_local(sxg_poa_handle *h, const sxg_poa_batch_in *i
 
 int sxg_poa_align_batch(sxg_poa_handle *h, const sxg_poa_align_in *in, sxg_poa_align_out *out);
 void sxg_poa_align_free(sxg_poa_align_out *out);
+
+/* The identity split of break_blocks (src/breaks.cpp:335-586; -I / --block-id-min, -R / --block-ratio-min), decrees P1-P4
+ * of DESIGN.md section 9.  WFA, the aligner the reference calls there, is absent from the snapshot (deps/WFA is empty), so the
+ * pair identity is restated as an OPTIMUM, with no tie-break to pin:
+ *   P1  a global alignment of a and b is a string of columns: diagonal (match / mismatch), I (consumes a), D (consumes b).  Its
+ *       cost is the triple (penalty, cols, nonmatch): penalty = 7 per mismatch + (11 + k) per gap of k bases, a switch between I
+ *       and D opening a new gap (the reference's penalties 0/7/11/1); cols = matches + mismatches + maximal runs of consecutive
+ *       gap columns, I and D mixed counting as ONE run (wfa_gap_compressed_identity, src/breaks.cpp:72-102); nonmatch =
+ *       mismatches + those runs.  The pair's result is the lexicographically smallest triple over all alignments;
+ *       matches = cols - nonmatch, identity = (double)matches / (double)cols.  N is a letter like any other.
+ *   P2  with cap given per pair (the reference: max_score = curr_len, :491-500): an optimal penalty >= cap means "no identity",
+ *       reported as cols = matches = 0 (penalty is still the optimum).  The reference's REDUCED wavefront (a heuristic that may
+ *       miss the optimum) is not restated: the optimum here is exact.
+ *   P3  sxg_poa_split_batch runs the greedy of :414-528 for every block, statement by statement: block b holds its dedup'd
+ *       sequences sorted by (length, letters); sequence 0 seeds group 0; every later sequence i is tried forward then reverse-
+ *       complemented, against the groups last to first, against each group's members last to first, and joins the group of the
+ *       first member with (double)matches / (double)cols >= identity[b] (IEEE double, cap = the length of i); a group's member
+ *       loop is left at the first member with (double)other_len / (double)curr_len < length_ratio_min[b] or with
+ *       other_len < curr_len && other_len < (uint64)(identity / (1 - identity)) ("always" at identity 1); a sequence that
+ *       joins nobody opens a new group.
+ *   P4  the mash-based branch (:388-471, enabled by the CLI at a dedup depth >= 12000 only) is NOT built: no mash parameters here.
+ * One wavefront per pair / one persistent wavefront per block; the scratch comes out of the handle's memory budget; both calls run
+ * inside ROCTx ranges and fill kernel_ms / cells / n_slots / dp_launches of sxg_poa_stats. */
+#define SXG_POA_SPLIT_PANEL 512 /* columns a wavefront sweeps at once; longer second sequences run panel after panel */
+/* n_pairs pairs over one flat sequence set: pair k aligns sequence pair_a[k] with sequence pair_b[k], the latter reverse-
+ * complemented where b_rev[k] (NULL = none), with bound cap[k].  Results go to the caller's arrays [n_pairs].  A zero-length
+ * sequence or one longer than SXG_POA_MAX_SEQ_LEN in a pair is SXG_E_INVALID. */
+int sxg_poa_pair_identity_batch(sxg_poa_handle *h, int64_t n_seqs, const int64_t *seq_off, const uint8_t *bases, int64_t n_pairs,
+                                const int32_t *pair_a, const int32_t *pair_b, const uint8_t *b_rev, const int32_t *cap,
+                                int32_t *penalty, int32_t *cols, int32_t *matches);
+typedef struct sxg_poa_split_in {
+    int32_t n_blocks;
+    const int32_t *blk_off;          /* [n_blocks+1] */
+    const int64_t *seq_off;          /* [n_seqs+1] */
+    const uint8_t *bases;            /* dedup'd sequences of every block, sorted by (length, letters) */
+    const double *identity;          /* [n_blocks] block_group_identity, 0 < t <= 1 */
+    const double *length_ratio_min;  /* [n_blocks] */
+} sxg_poa_split_in;
+typedef struct sxg_poa_split_out {
+    int32_t n_blocks;
+    int64_t n_seqs;
+    int32_t *group;    /* [n_seqs] group of every sequence, 0-based in order of creation (0 for a failed block) */
+    int32_t *n_groups; /* [n_blocks] (0 for a failed or empty block) */
+    int64_t *n_pairs;  /* [n_blocks] pair alignments the block's greedy ran */
+    int32_t *status;   /* [n_blocks] SXG_ST_OK, or SXG_ST_TOO_LONG: a sequence exceeds SXG_POA_MAX_SEQ_LEN */
+    void *_owner;
+} sxg_poa_split_out;
+/* Returns SXG_E_BLOCK when some block failed (the others are valid), SXG_E_INVALID for a zero-length sequence. */
+int sxg_poa_split_batch(sxg_poa_handle *h, const sxg_poa_split_in *in, sxg_poa_split_out *out);
+void sxg_poa_split_free(sxg_poa_split_out *out);
 
 int sxg_poa_get_stats(sxg_poa_handle *h, sxg_poa_stats *out);
 /* Cap on device memory the handle may use for scratch arenas (bytes; 0 = default 3/4 of free). */

@@ -126,12 +126,32 @@ int sxg_blockset_smoothable(const sxg_graph *g, uint64_t max_block_weight, uint6
  * blind cuts only).  The repeat detector stands in for sautocorr::repeat, an un-vendored dependency absent from the
  * snapshot, BY DECREE: match-fraction autocorrelation at every lag in [min_copy_length,
  * max_copy_length] over positions sampled every autocorr_stride bases, z-score across the lags, first lag of greatest z
- * if that z reaches min_autocorr_z.  Identity splitting (src/breaks.cpp:335+; off by default) is not applied. */
+ * if that z reaches min_autocorr_z.  Identity splitting (src/breaks.cpp:335+; off by default) is not applied by these two:
+ * it is the call below, sxg_blockset_split, run on their result. */
 int sxg_blockset_break(const sxg_graph *g, const sxg_blockset *in, uint64_t max_poa_length, int order_paths_from_longest,
                        sxg_blockset **out);
 int sxg_blockset_break_ex(const sxg_graph *g, const sxg_blockset *in, uint64_t max_poa_length, int break_repeats,
                           uint64_t min_copy_length, uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride,
                           int order_paths_from_longest, sxg_blockset **out);
+/* The splitting half of break_blocks, src/breaks.cpp:335-586 (-I / --block-id-min, -R / --block-ratio-min and the dedup
+ * depth; an addition to ABI 2, no struct changed): a block whose sequences fall into more than one identity group becomes one
+ * block per group.  Decree P3 of DESIGN.md section 9, statement by statement as the reference: nothing happens to a block
+ * unless block_group_identity > 0 and it has more than one range; its range sequences are dedup'd ("equal to a kept sequence
+ * or to its reverse complement": the first occurrence is kept, in its orientation, with the list of original ranks); nothing
+ * happens unless min_dedup_depth != 0 && dedup'd sequences >= min_dedup_depth -- the quirk is kept: the CLI default 0 means
+ * "never split" --; the kept sequences are sorted by (length, letters) and handed, all candidate blocks in ONE call, to the
+ * split provider, which runs the greedy clustering (sxg_poa_split_batch: the pair alignments are the hot part and run on the
+ * GPU; this library holds no alignment code).  One group: the block is unchanged.  More: one new block per group in group
+ * order, a group's members in the order they joined, each member contributing its original ranges in their original order.
+ * New blocks are numbered consecutively in old-block order.  A block the provider reports with a status other than
+ * SXG_ST_OK stays whole and is counted in *n_too_long; *n_split counts the blocks that were split.  The mash-based branch
+ * (:388-471, dedup depth >= 12000 on the CLI) is not built (decree P4): there are no mash parameters.
+ * Split provider: exactly sxg_poa_split_batch's contract, ctx is its handle; called at most once, on the calling thread. */
+typedef int (*sxg_split_fn)(void *ctx, const sxg_poa_split_in *in, sxg_poa_split_out *out);
+typedef void (*sxg_split_free_fn)(sxg_poa_split_out *out);
+int sxg_blockset_split(const sxg_graph *g, const sxg_blockset *in, double block_group_identity, double length_ratio_min,
+                       uint64_t min_dedup_depth, sxg_split_fn split, sxg_split_free_fn split_free, void *ctx, sxg_blockset **out,
+                       int64_t *n_split, int64_t *n_too_long);
 int64_t sxg_blockset_block_size(const sxg_blockset *b, int64_t block_id);              /* ranges of a block, -1 on error */
 int sxg_blockset_block_ranges(const sxg_blockset *b, int64_t block_id, sxg_path_range *out); /* out[block size] */
 void sxg_blockset_free(sxg_blockset *b);

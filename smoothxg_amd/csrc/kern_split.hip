@@ -1,0 +1,4 @@
+// kern_split.hip -- the kernels of the identity split (pair_identity_kernel, split_kernel: poa_split.hip.h) and their
+// launchers, a translation unit of its own beside the kernel classes of kern_part.hip.
+#define SXG_SPLIT_IMPL
+#include "poa_split.hip.h"

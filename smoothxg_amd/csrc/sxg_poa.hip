@@ -23,6 +23,7 @@
 #include <dlfcn.h>
 #include "poa_kernels.hip.h"       // slot layout, launch arguments, the persistent kernels (device side)
 #include "poa_kern_tables.hip.h"   // kernel classes by geometry; instantiated in the kern_*.hip translation units
+#include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
 
 
 // ---------------------------------------------------------------------------------------
@@ -2328,6 +2329,223 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
     out->pair_row = o->pair_row.data(); out->pair_pos = o->pair_pos.data();
     for (int p = 0; p < n; ++p)
         if (o->status[p] != ST_OK) return fail(SXG_E_BLOCK, "problem " + std::to_string(p) + " failed with status " + std::to_string(o->status[p]));
+    return SXG_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The identity split of break_blocks (src/breaks.cpp:335-586): decrees P1-P4 (include/sxg_poa.h).  Kernels in
+// poa_split.hip.h / kern_split.hip; here the validation, the cost-sorted queues, the scratch (out of the memory budget) and the timing.
+static_assert(SXG_POA_SPLIT_PANEL == SXG_SPLIT_PANEL, "panel width of the header");
+namespace {
+struct SplitBufs {
+    DevBuf seq_off, bases, a, b, c, d, e, f, g, hh, work, queue, bound, lists;
+    ~SplitBufs() {
+        DevBuf* bs[] = {&seq_off, &bases, &a, &b, &c, &d, &e, &f, &g, &hh, &work, &queue, &bound, &lists};
+        for (DevBuf* x : bs) x->release();
+    }
+};
+// slots of a split launch: what fits the chip, the work and the budget (one slot = one wavefront with its boundary column)
+int split_slots(sxg_poa_handle* h, int which, int64_t n_work, size_t slot_bytes, int64_t* n_slots) {
+    int per_cu = 1;
+    sxg_split_occupancy(which, &per_cu);
+    int64_t n = std::min<int64_t>(n_work, (int64_t)std::max(h->num_cu, 1) * per_cu);
+    n = std::min<int64_t>(n, (int64_t)(arena_budget(h) / std::max<size_t>(slot_bytes, 1)));
+    if (n < 1) return fail(SXG_E_NOMEM, "memory budget too small for one split slot");
+    *n_slots = n;
+    return SXG_OK;
+}
+int split_upload_seqs(sxg_poa_handle* h, SplitBufs& B, int64_t n_seqs, const int64_t* seq_off, const uint8_t* bases) {
+    const int64_t nbases = seq_off[n_seqs];
+    std::vector<uint8_t> stage((size_t)std::max<int64_t>(nbases, 1));
+    for (int64_t i = 0; i < nbases; ++i) stage[(size_t)i] = bases[i] > 4 ? 4 : bases[i];
+    if (int rc = B.seq_off.ensure(8 * (size_t)(n_seqs + 1))) return rc;
+    if (int rc = B.bases.ensure((size_t)nbases + 16)) return rc;
+    HIPCHK(hipMemcpyAsync(B.seq_off.p, seq_off, 8 * (size_t)(n_seqs + 1), hipMemcpyHostToDevice, h->stream));
+    if (nbases) HIPCHK(hipMemcpyAsync(B.bases.p, stage.data(), (size_t)nbases, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));   // (stage leaves scope)
+    return SXG_OK;
+}
+template <class Tp> int split_up(sxg_poa_handle* h, DevBuf& d, const Tp* src, size_t n) {
+    if (int rc = d.ensure(sizeof(Tp) * std::max<size_t>(n, 1))) return rc;
+    if (n) HIPCHK(hipMemcpy(d.p, src, sizeof(Tp) * n, hipMemcpyHostToDevice));
+    return SXG_OK;
+}
+void split_stats(sxg_poa_handle* h, float ms, uint64_t cells, int64_t n_slots, size_t dev_bytes) {
+    h->stats = sxg_poa_stats{};
+    h->stats.kernel_ms = ms; h->stats.cells = cells; h->stats.dp_launches = 1; h->stats.n_slots = (int32_t)n_slots;
+    h->stats.device_bytes = dev_bytes;
+    h->stats.dom_kernel_ms = ms; h->stats.dom_cells = cells; h->stats.dom_threads = 64; h->stats.dom_cols_per_lane = SXG_SPLIT_W;
+}
+}  // namespace
+
+extern "C" int sxg_poa_pair_identity_batch(sxg_poa_handle* h, int64_t n_seqs, const int64_t* seq_off, const uint8_t* bases, int64_t n_pairs,
+                                           const int32_t* pair_a, const int32_t* pair_b, const uint8_t* b_rev, const int32_t* cap,
+                                           int32_t* penalty, int32_t* cols, int32_t* matches) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    if (n_seqs < 0 || n_pairs < 0 || n_pairs > 0x7fffffff || !seq_off || (n_pairs > 0 && (!pair_a || !pair_b || !cap || !penalty || !cols || !matches)))
+        return fail(SXG_E_INVALID, "pair_identity: bad argument");
+    if (seq_off[0] != 0) return fail(SXG_E_INVALID, "seq_off[0] must be 0");
+    for (int64_t s = 0; s < n_seqs; ++s)
+        if (seq_off[s + 1] < seq_off[s]) return fail(SXG_E_INVALID, "seq_off not monotone");
+    if (seq_off[n_seqs] > 0 && !bases) return fail(SXG_E_INVALID, "bases is NULL");
+    RoctxRange range("sxg_poa_pair_identity_batch");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    if (n_pairs == 0) return SXG_OK;
+    uint64_t cells = 0;
+    int64_t max_la = 0;
+    std::vector<std::pair<int64_t, int32_t>> cost((size_t)n_pairs);
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        if (pair_a[k] < 0 || pair_a[k] >= n_seqs || pair_b[k] < 0 || pair_b[k] >= n_seqs) return fail(SXG_E_INVALID, "pair " + std::to_string(k) + ": no such sequence");
+        const int64_t la = seq_off[pair_a[k] + 1] - seq_off[pair_a[k]], lb = seq_off[pair_b[k] + 1] - seq_off[pair_b[k]];
+        if (la < 1 || lb < 1) return fail(SXG_E_INVALID, "pair " + std::to_string(k) + ": zero-length sequence");
+        if (la > SXG_POA_MAX_SEQ_LEN || lb > SXG_POA_MAX_SEQ_LEN) return fail(SXG_E_INVALID, "pair " + std::to_string(k) + ": sequence longer than SXG_POA_MAX_SEQ_LEN");
+        cost[(size_t)k] = {la * lb, (int32_t)k};
+        cells += (uint64_t)(la * lb);
+        max_la = std::max(max_la, la);
+    }
+    std::stable_sort(cost.begin(), cost.end(), [](const std::pair<int64_t, int32_t>& x, const std::pair<int64_t, int32_t>& y) { return x.first > y.first; });
+    std::vector<int32_t> work((size_t)n_pairs);
+    for (int64_t k = 0; k < n_pairs; ++k) work[(size_t)k] = cost[(size_t)k].second;
+    std::vector<uint8_t> rev((size_t)n_pairs, 0);
+    if (b_rev) for (int64_t k = 0; k < n_pairs; ++k) rev[(size_t)k] = b_rev[k] ? 1 : 0;
+    SplitBufs B;
+    if (int rc = split_upload_seqs(h, B, n_seqs, seq_off, bases)) return rc;
+    if (int rc = split_up(h, B.a, pair_a, (size_t)n_pairs)) return rc;
+    if (int rc = split_up(h, B.b, pair_b, (size_t)n_pairs)) return rc;
+    if (int rc = split_up(h, B.c, rev.data(), (size_t)n_pairs)) return rc;
+    if (int rc = split_up(h, B.d, cap, (size_t)n_pairs)) return rc;
+    if (int rc = split_up(h, B.work, work.data(), (size_t)n_pairs)) return rc;
+    if (int rc = B.e.ensure(4 * (size_t)n_pairs)) return rc;
+    if (int rc = B.f.ensure(4 * (size_t)n_pairs)) return rc;
+    if (int rc = B.g.ensure(4 * (size_t)n_pairs)) return rc;
+    if (int rc = B.queue.ensure(256)) return rc;
+    const int64_t bound_rows = max_la + 1;
+    const size_t slot_bytes = 3 * sizeof(sxg_key_t) * (size_t)bound_rows;
+    int64_t n_slots = 0;
+    if (int rc = split_slots(h, 0, n_pairs, slot_bytes, &n_slots)) return rc;
+    if (int rc = B.bound.ensure(slot_bytes * (size_t)n_slots)) return rc;
+    HIPCHK(hipMemsetAsync(B.queue.p, 0, 4, h->stream));
+    SplitPairArgs A;
+    A.seq_off = B.seq_off.as<int64_t>(); A.bases = B.bases.as<uint8_t>(); A.pair_a = B.a.as<int32_t>(); A.pair_b = B.b.as<int32_t>();
+    A.b_rev = B.c.as<uint8_t>(); A.cap = B.d.as<int32_t>(); A.work = B.work.as<int32_t>(); A.n_work = (int32_t)n_pairs;
+    A.queue = B.queue.as<int32_t>(); A.bound = B.bound.as<sxg_key_t>(); A.bound_rows = bound_rows;
+    A.penalty = B.e.as<int32_t>(); A.cols = B.f.as<int32_t>(); A.matches = B.g.as<int32_t>();
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    sxg_split_launch_pairs(A, (int)n_slots, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    HIPCHK(hipMemcpy(penalty, B.e.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cols, B.f.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(matches, B.g.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    split_stats(h, ms, cells, n_slots, B.bound.cap);
+    return SXG_OK;
+}
+
+struct SplitOwner {
+    std::vector<int32_t> group, n_groups, status;
+    std::vector<int64_t> n_pairs;
+};
+extern "C" void sxg_poa_split_free(sxg_poa_split_out* out) {
+    if (!out) return;
+    delete (SplitOwner*)out->_owner;
+    memset(out, 0, sizeof(*out));
+}
+extern "C" int sxg_poa_split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, sxg_poa_split_out* out) {
+    if (!h || !in || !out) return fail(SXG_E_INVALID, "NULL argument");
+    memset(out, 0, sizeof(*out));
+    const int nb = in->n_blocks;
+    if (nb < 0 || (nb > 0 && (!in->blk_off || !in->seq_off || !in->identity || !in->length_ratio_min))) return fail(SXG_E_INVALID, "split_in has NULL arrays");
+    if (nb > 0 && (in->blk_off[0] != 0 || in->seq_off[0] != 0)) return fail(SXG_E_INVALID, "blk_off[0] and seq_off[0] must be 0");
+    for (int b = 0; b < nb; ++b) {
+        if (in->blk_off[b + 1] < in->blk_off[b]) return fail(SXG_E_INVALID, "blk_off not monotone");
+        if (!(in->identity[b] > 0.0 && in->identity[b] <= 1.0)) return fail(SXG_E_INVALID, "block " + std::to_string(b) + ": identity must be in (0, 1]");
+        if (!(in->length_ratio_min[b] == in->length_ratio_min[b])) return fail(SXG_E_INVALID, "block " + std::to_string(b) + ": length_ratio_min is NaN");
+    }
+    const int64_t ns = nb ? in->blk_off[nb] : 0;
+    for (int64_t s = 0; s < ns; ++s)
+        if (in->seq_off[s + 1] <= in->seq_off[s]) return fail(SXG_E_INVALID, "sequence " + std::to_string(s) + " has no bases (or seq_off is not monotone)");
+    if (ns > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
+    RoctxRange range("sxg_poa_split_batch");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    SplitOwner* o = new SplitOwner();
+    out->_owner = o; out->n_blocks = nb; out->n_seqs = ns;
+    o->group.assign((size_t)std::max<int64_t>(ns, 1), 0); o->n_groups.assign((size_t)std::max(nb, 1), 0);
+    o->status.assign((size_t)std::max(nb, 1), 0); o->n_pairs.assign((size_t)std::max(nb, 1), 0);
+    out->group = o->group.data(); out->n_groups = o->n_groups.data(); out->status = o->status.data(); out->n_pairs = o->n_pairs.data();
+    // the queue: blocks by cost (sum of len_i * len_(i-1)), most expensive first; a block with a sequence too long stays out
+    std::vector<std::pair<uint64_t, int32_t>> cost;
+    int64_t max_len = 0, max_depth = 0;
+    bool any_failed = false;
+    for (int b = 0; b < nb; ++b) {
+        const int64_t s0 = in->blk_off[b], s1 = in->blk_off[b + 1];
+        uint64_t c = 0;
+        int64_t longest = 0;
+        for (int64_t s = s0; s < s1; ++s) {
+            const int64_t len = in->seq_off[s + 1] - in->seq_off[s];
+            longest = std::max(longest, len);
+            if (s > s0) c += (uint64_t)len * (uint64_t)(in->seq_off[s] - in->seq_off[s - 1]);
+        }
+        if (longest > SXG_POA_MAX_SEQ_LEN) { o->status[(size_t)b] = SXG_ST_TOO_LONG; any_failed = true; continue; }
+        if (s1 == s0) continue;
+        cost.push_back({c, b});
+        max_len = std::max(max_len, longest);
+        max_depth = std::max(max_depth, s1 - s0);
+    }
+#define SPLIT_CK(x) do { int _rc = (x); if (_rc) { sxg_poa_split_free(out); return _rc; } } while (0)
+#define SPLIT_HCK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { sxg_poa_split_free(out); return fail(SXG_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); } } while (0)
+    if (!cost.empty()) {
+        std::stable_sort(cost.begin(), cost.end(), [](const std::pair<uint64_t, int32_t>& x, const std::pair<uint64_t, int32_t>& y) { return x.first > y.first; });
+        std::vector<int32_t> work(cost.size());
+        for (size_t k = 0; k < cost.size(); ++k) work[k] = cost[k].second;
+        SplitBufs B;
+        SPLIT_CK(split_upload_seqs(h, B, ns, in->seq_off, in->bases));
+        SPLIT_CK(split_up(h, B.a, in->blk_off, (size_t)nb + 1));
+        SPLIT_CK(split_up(h, B.b, in->identity, (size_t)nb));
+        SPLIT_CK(split_up(h, B.c, in->length_ratio_min, (size_t)nb));
+        SPLIT_CK(split_up(h, B.work, work.data(), work.size()));
+        SPLIT_CK(B.d.ensure(4 * (size_t)ns)); SPLIT_CK(B.e.ensure(4 * (size_t)nb)); SPLIT_CK(B.f.ensure(8 * (size_t)nb)); SPLIT_CK(B.g.ensure(8 * (size_t)nb));
+        SPLIT_CK(B.queue.ensure(256));
+        const int64_t bound_rows = max_len + 1;
+        const size_t slot_bytes = 3 * sizeof(sxg_key_t) * (size_t)bound_rows + 2 * sizeof(int32_t) * (size_t)max_depth;
+        int64_t n_slots = 0;
+        SPLIT_CK(split_slots(h, 1, (int64_t)work.size(), slot_bytes, &n_slots));
+        SPLIT_CK(B.bound.ensure(3 * sizeof(sxg_key_t) * (size_t)bound_rows * (size_t)n_slots));
+        SPLIT_CK(B.lists.ensure(2 * sizeof(int32_t) * (size_t)max_depth * (size_t)n_slots));
+        SPLIT_HCK(hipMemsetAsync(B.queue.p, 0, 4, h->stream));
+        SPLIT_HCK(hipMemsetAsync(B.d.p, 0, 4 * (size_t)ns, h->stream));
+        SPLIT_HCK(hipMemsetAsync(B.e.p, 0, 4 * (size_t)nb, h->stream));
+        SPLIT_HCK(hipMemsetAsync(B.f.p, 0, 8 * (size_t)nb, h->stream));
+        SPLIT_HCK(hipMemsetAsync(B.g.p, 0, 8 * (size_t)nb, h->stream));
+        SplitBlockArgs A;
+        A.blk_off = B.a.as<int32_t>(); A.seq_off = B.seq_off.as<int64_t>(); A.bases = B.bases.as<uint8_t>();
+        A.identity = B.b.as<double>(); A.ratio_min = B.c.as<double>(); A.work = B.work.as<int32_t>(); A.n_work = (int32_t)work.size();
+        A.queue = B.queue.as<int32_t>(); A.bound = B.bound.as<sxg_key_t>(); A.bound_rows = bound_rows;
+        A.lists = B.lists.as<int32_t>(); A.list_cap = max_depth;
+        A.group = B.d.as<int32_t>(); A.n_groups = B.e.as<int32_t>(); A.n_pairs = B.f.as<int64_t>(); A.cells = B.g.as<uint64_t>();
+        SPLIT_HCK(hipEventRecord(h->ev0, h->stream));
+        sxg_split_launch_blocks(A, (int)n_slots, h->stream);
+        SPLIT_HCK(hipGetLastError());
+        SPLIT_HCK(hipEventRecord(h->ev1, h->stream));
+        SPLIT_HCK(hipEventSynchronize(h->ev1));
+        float ms = 0;
+        SPLIT_HCK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        std::vector<uint64_t> cells((size_t)nb);
+        SPLIT_HCK(hipMemcpy(o->group.data(), B.d.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
+        SPLIT_HCK(hipMemcpy(o->n_groups.data(), B.e.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        SPLIT_HCK(hipMemcpy(o->n_pairs.data(), B.f.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
+        SPLIT_HCK(hipMemcpy(cells.data(), B.g.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
+        uint64_t total = 0;
+        for (uint64_t c : cells) total += c;
+        split_stats(h, ms, total, n_slots, B.bound.cap + B.lists.cap);
+    }
+#undef SPLIT_CK
+#undef SPLIT_HCK
+    if (any_failed) return fail(SXG_E_BLOCK, "a block holds a sequence longer than SXG_POA_MAX_SEQ_LEN");
     return SXG_OK;
 }
 

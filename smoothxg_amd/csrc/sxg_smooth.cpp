@@ -2799,6 +2799,108 @@ int sxg_blockset_break_ex(const sxg_graph* g, const sxg_blockset* in, uint64_t m
 }
 
 }  // extern "C"
+// The splitting half of break_blocks (src/breaks.cpp:335-586), decree P3: dedup, guards and sort here, the greedy clustering
+// with its pair alignments behind the split provider (ONE call for all candidate blocks), the reassembly here.
+static int blockset_split(const sxg_graph* g, const sxg_blockset* in, double t, double ratio_min, uint64_t min_dedup_depth, sxg_split_fn split,
+                          sxg_split_free_fn split_free, void* ctx, sxg_blockset** out, int64_t* n_split, int64_t* n_too_long) {
+    if (!g || !in || !out || !split || !split_free) return fail(SXG_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (n_split) *n_split = 0;
+    if (n_too_long) *n_too_long = 0;
+    if (!(t <= 1.0)) return fail(SXG_E_INVALID, "block_group_identity must not exceed 1");
+    if (ratio_min != ratio_min) return fail(SXG_E_INVALID, "length_ratio_min is NaN");
+    const int64_t nb = (int64_t)in->blocks.size();
+    struct cand_t { int64_t block; std::vector<std::string> seqs; std::vector<std::vector<uint64_t>> ranks; };   // dedup'd, sorted
+    std::vector<cand_t> cands((size_t)nb);
+    std::vector<char> is_cand((size_t)nb, 0);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t k = 0; k < nb; ++k) {
+        const auto& blk = in->blocks[(size_t)k];
+        if (!(t > 0 && blk.size() > 1)) continue;                                       // :335
+        std::vector<std::string> kept;
+        std::vector<std::vector<uint64_t>> ranks;
+        for (uint64_t rank = 0; rank < blk.size(); ++rank) {                            // :340-371
+            const auto& r = blk[rank];
+            std::string seq;
+            for (uint64_t st = r.begin; st != r.end; ++st) seq += g->sequence(g->steps[r.path][st]);
+            const std::string seq_rev = revcomp(seq);
+            bool new_seq = true;
+            for (size_t j = 0; j < kept.size(); ++j)
+                if (seq == kept[j] || seq_rev == kept[j]) { ranks[j].push_back(rank); new_seq = false; break; }
+            if (new_seq) { kept.push_back(seq); ranks.push_back({rank}); }
+        }
+        if (!(min_dedup_depth != 0 && kept.size() >= min_dedup_depth)) continue;        // :373
+        std::vector<size_t> order(kept.size());
+        for (size_t j = 0; j < order.size(); ++j) order[j] = j;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {                 // :375-381 (kept sequences are distinct)
+            if (kept[a].size() != kept[b].size()) return kept[a].size() < kept[b].size();
+            return kept[a] < kept[b];
+        });
+        cand_t& c = cands[(size_t)k];
+        c.block = k;
+        for (size_t j : order) { c.seqs.push_back(std::move(kept[j])); c.ranks.push_back(std::move(ranks[j])); }
+        is_cand[(size_t)k] = 1;
+    }
+    // the batch: every candidate block's sequences as codes
+    std::vector<int64_t> which;
+    std::vector<int32_t> blk_off{0};
+    std::vector<int64_t> seq_off{0};
+    std::vector<uint8_t> bases;
+    for (int64_t k = 0; k < nb; ++k) {
+        if (!is_cand[(size_t)k]) continue;
+        which.push_back(k);
+        for (auto& sq : cands[(size_t)k].seqs) {
+            if (sq.empty()) return fail(SXG_E_INVALID, "block " + std::to_string(k) + " holds an empty range");
+            for (char ch : sq) bases.push_back(ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4);
+            seq_off.push_back((int64_t)bases.size());
+        }
+        if (seq_off.size() - 1 > 0x7fffffffu) return fail(SXG_E_INVALID, "too many sequences for one split batch");
+        blk_off.push_back((int32_t)(seq_off.size() - 1));
+    }
+    sxg_blockset* bs = new sxg_blockset();
+    if (which.empty()) { bs->blocks = in->blocks; *out = bs; return SXG_OK; }
+    const int32_t nc = (int32_t)which.size();
+    std::vector<double> ident((size_t)nc, t), ratio((size_t)nc, ratio_min);
+    if (bases.empty()) bases.push_back(0);
+    sxg_poa_split_in si;
+    memset(&si, 0, sizeof(si));
+    si.n_blocks = nc; si.blk_off = blk_off.data(); si.seq_off = seq_off.data(); si.bases = bases.data();
+    si.identity = ident.data(); si.length_ratio_min = ratio.data();
+    sxg_poa_split_out so;
+    memset(&so, 0, sizeof(so));
+    const int rc = split(ctx, &si, &so);
+    if (rc != SXG_OK && rc != SXG_E_BLOCK) { delete bs; return fail(rc < 0 ? rc : SXG_E_INVALID, "the split provider failed with code " + std::to_string(rc)); }
+    auto refuse = [&](const std::string& why) { split_free(&so); delete bs; return fail(SXG_E_INVALID, "split provider: " + why); };
+    if (so.n_blocks != nc || so.n_seqs != (int64_t)blk_off.back() || !so.group || !so.n_groups || !so.status) return refuse("result does not match the batch");
+    int64_t splits = 0, failed = 0;
+    size_t c = 0;
+    for (int64_t k = 0; k < nb; ++k) {
+        const auto& blk = in->blocks[(size_t)k];
+        if (!is_cand[(size_t)k]) { bs->blocks.push_back(blk); continue; }
+        const cand_t& cd = cands[(size_t)k];
+        const size_t ci = c++;
+        if (so.status[ci] != SXG_ST_OK) { ++failed; bs->blocks.push_back(blk); continue; }
+        const int32_t ng = so.n_groups[ci];
+        const int64_t s0 = blk_off[ci], n = blk_off[ci + 1] - s0;
+        if (ng < 1 || ng > n) return refuse("block " + std::to_string(k) + ": " + std::to_string(ng) + " groups for " + std::to_string(n) + " sequences");
+        for (int64_t q = 0; q < n; ++q)
+            if (so.group[s0 + q] < 0 || so.group[s0 + q] >= ng) return refuse("block " + std::to_string(k) + ": group id out of range");
+        if (ng == 1) { bs->blocks.push_back(blk); continue; }                           // :530-532
+        ++splits;
+        std::vector<std::vector<path_range_t>> nw((size_t)ng);
+        for (int64_t q = 0; q < n; ++q)                                                 // :537-552 (members joined in ascending q)
+            for (uint64_t rank : cd.ranks[(size_t)q]) nw[(size_t)so.group[s0 + q]].push_back(blk[(size_t)rank]);
+        for (auto& v : nw) {
+            if (v.empty()) return refuse("block " + std::to_string(k) + ": an empty group");
+            bs->blocks.push_back(std::move(v));
+        }
+    }
+    split_free(&so);
+    if (n_split) *n_split = splits;
+    if (n_too_long) *n_too_long = failed;
+    *out = bs;
+    return SXG_OK;
+}
 // no exception crosses the C ABI: an allocation that fails anywhere in the iteration becomes SXG_E_NOMEM (the pipeline's
 // worker thread is joined while the stack unwinds)
 template <class F> static int guarded(F f) {
@@ -2823,6 +2925,11 @@ int sxg_smooth_maf_gfa(const sxg_graph* g, const sxg_blockset* b, const sxg_smoo
                        sxg_poa_free_fn fre, void* ctx, char** out_gfa, char** out_maf, int64_t* n_flipped) {
     if (!mp || !out_maf) return fail(SXG_E_INVALID, "NULL argument");
     return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, out_gfa, out_maf, n_flipped); });
+}
+
+int sxg_blockset_split(const sxg_graph* g, const sxg_blockset* in, double block_group_identity, double length_ratio_min, uint64_t min_dedup_depth,
+                       sxg_split_fn split, sxg_split_free_fn split_free, void* ctx, sxg_blockset** out, int64_t* n_split, int64_t* n_too_long) {
+    return guarded([&] { return blockset_split(g, in, block_group_identity, length_ratio_min, min_dedup_depth, split, split_free, ctx, out, n_split, n_too_long); });
 }
 
 // blockset_t from the caller's own blocks (src/blocks.hpp:29-43,70-120): block k owns ranges

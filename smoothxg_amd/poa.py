@@ -77,7 +77,22 @@ class DeviceView(C.Structure):
                 ("seq_path_nodes", C.c_void_p), ("score", C.c_void_p)]
 
 
-EXPORTS = ["sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
+class SplitIn(C.Structure):
+    """sxg_poa_split_in: blocks of dedup'd, sorted sequences with their identity threshold and length ratio."""
+    _fields_ = [("n_blocks", C.c_int32), ("blk_off", _i32p), ("seq_off", _i64p), ("bases", _u8p),
+                ("identity", C.POINTER(C.c_double)), ("length_ratio_min", C.POINTER(C.c_double))]
+
+
+class SplitOut(C.Structure):
+    _fields_ = [("n_blocks", C.c_int32), ("n_seqs", C.c_int64), ("group", _i32p), ("n_groups", _i32p),
+                ("n_pairs", _i64p), ("status", _i32p), ("_owner", C.c_void_p)]
+
+
+SPLIT_PANEL = 512   # SXG_POA_SPLIT_PANEL: columns of the second sequence a wavefront sweeps at once
+MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
+ST_TOO_LONG = 5
+
+EXPORTS = ["sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
            "sxg_poa_get_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
@@ -128,6 +143,10 @@ def load_library(build_if_missing=True):
     L.sxg_poa_batch_download_sharded.argtypes = [vp, C.POINTER(BatchIn), C.POINTER(BatchOut)]
     L.sxg_poa_sharded_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
     L.sxg_poa_sharded_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sxg_poa_pair_identity_batch.argtypes = [vp, C.c_int64, _i64p, _u8p, C.c_int64, _i32p, _i32p, _u8p, _i32p, _i32p, _i32p, _i32p]
+    L.sxg_poa_split_batch.argtypes = [vp, C.POINTER(SplitIn), C.POINTER(SplitOut)]
+    L.sxg_poa_split_free.argtypes = [C.POINTER(SplitOut)]
+    L.sxg_poa_split_free.restype = None
     L.sxg_xxh64.restype = C.c_uint64
     L.sxg_xxh64.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64]
     _lib = L
@@ -435,6 +454,57 @@ class PoaEngine:
             blk_off[1:] = np.cumsum([len(b) for b in blocks])
         w = None if weights is None else np.concatenate([np.asarray(x, np.uint32) for x in weights])
         return self.run_flat(bases, seq_off, blk_off, w, params, want_consensus, want_msa, check)
+
+    # -- the identity split of break_blocks (src/breaks.cpp:335-586) -------------------------
+    @staticmethod
+    def _flat(seqs):
+        seqs = [np.ascontiguousarray(x, np.uint8) for x in seqs]
+        seq_off = np.zeros(len(seqs) + 1, np.int64)
+        if seqs:
+            seq_off[1:] = np.cumsum([len(x) for x in seqs])
+        bases = np.concatenate(seqs) if seqs else np.zeros(0, np.uint8)
+        return (bases if len(bases) else np.zeros(1, np.uint8)), seq_off
+
+    def pair_identity(self, seqs, pairs, caps, rev=None):
+        """sxg_poa_pair_identity_batch.  seqs: code arrays; pairs: (a, b) indices into seqs; caps: one bound per pair;
+        rev: per pair, b is read reverse-complemented.  Returns int32 arrays (penalty, cols, matches); cols == 0 means
+        the optimal penalty is not below the cap."""
+        bases, seq_off = self._flat(seqs)
+        n = len(pairs)
+        pa = np.ascontiguousarray([p[0] for p in pairs], np.int32) if n else np.zeros(1, np.int32)
+        pb = np.ascontiguousarray([p[1] for p in pairs], np.int32) if n else np.zeros(1, np.int32)
+        cap = np.ascontiguousarray(caps, np.int32) if n else np.zeros(1, np.int32)
+        rv = None if rev is None else (np.ascontiguousarray(rev, np.uint8) if n else np.zeros(1, np.uint8))
+        pen, cols, mat = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+        rc = self.lib.sxg_poa_pair_identity_batch(self.h, len(seqs), _p(seq_off, C.c_int64), _p(bases, C.c_uint8), n, _p(pa, C.c_int32),
+                                                  _p(pb, C.c_int32), _p(rv, C.c_uint8) if rv is not None else None, _p(cap, C.c_int32),
+                                                  _p(pen, C.c_int32), _p(cols, C.c_int32), _p(mat, C.c_int32))
+        if rc:
+            raise self._err("sxg_poa_pair_identity_batch")
+        return pen[:n], cols[:n], mat[:n]
+
+    def split(self, blocks, identity, length_ratio_min=0.0, check=True):
+        """sxg_poa_split_batch.  blocks: list of lists of code arrays, each block dedup'd and sorted by (length, letters);
+        identity / length_ratio_min: one value or one per block.  Returns one (groups, n_groups, n_pairs, status) per
+        block, groups being the int32 group id of every sequence."""
+        nb = len(blocks)
+        bases, seq_off = self._flat([x for blk in blocks for x in blk])
+        blk_off = np.zeros(nb + 1, np.int32)
+        if nb:
+            blk_off[1:] = np.cumsum([len(b) for b in blocks])
+        ident = np.ascontiguousarray(np.broadcast_to(np.asarray(identity, np.float64), (nb,)) if nb else np.zeros(1), np.float64)
+        ratio = np.ascontiguousarray(np.broadcast_to(np.asarray(length_ratio_min, np.float64), (nb,)) if nb else np.zeros(1), np.float64)
+        si = SplitIn(nb, _p(blk_off, C.c_int32), _p(seq_off, C.c_int64), _p(bases, C.c_uint8), _p(ident, C.c_double), _p(ratio, C.c_double))
+        out = SplitOut()
+        rc = self.lib.sxg_poa_split_batch(self.h, C.byref(si), C.byref(out))
+        try:
+            if rc and (check or rc != -4):
+                raise self._err("sxg_poa_split_batch")
+            grp = _arr(out.group, int(blk_off[-1]), np.int32)
+            ng, npairs, st = _arr(out.n_groups, nb, np.int32), _arr(out.n_pairs, nb, np.int64), _arr(out.status, nb, np.int32)
+            return [(grp[blk_off[b]:blk_off[b + 1]], int(ng[b]), int(npairs[b]), int(st[b])) for b in range(nb)]
+        finally:
+            self.lib.sxg_poa_split_free(C.byref(out))
 
     # -- stand-alone Align(sequence, graph) --------------------------------------------
     def align(self, problems, params, check=True):

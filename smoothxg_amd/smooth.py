@@ -13,6 +13,8 @@ _lib = None
 
 RUN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.BatchIn), C.POINTER(_poa.BatchOut))
 FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.BatchOut))
+SPLIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitOut))
+SPLIT_FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.SplitOut))
 
 
 class SmoothParams(C.Structure):
@@ -29,7 +31,7 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_blockset_free", "sxg_blockset_size", "sxg_block_collect_text", "sxg_block_graph_gfa",
            "sxg_smooth_gfa", "sxg_adaptive_poa_scores", "sxg_block_identity_threshold",
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
-           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_merge_default_params", "sxg_smooth_maf_gfa"]
+           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_merge_default_params", "sxg_smooth_maf_gfa"]
 
 
 class MergeParams(C.Structure):
@@ -69,6 +71,7 @@ def load_library():
     L.sxg_blockset_smoothable.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp)]
     L.sxg_blockset_break.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
     L.sxg_blockset_break_ex.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_double, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.sxg_blockset_split.argtypes = [vp, vp, C.c_double, C.c_double, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.sxg_blockset_free.argtypes = [vp]
     L.sxg_blockset_size.restype = C.c_int64
     L.sxg_blockset_size.argtypes = [vp]
@@ -113,6 +116,13 @@ def gpu_provider(engine, sharded=False):
     run = C.cast(L.sxg_poa_batch_run_sharded if sharded else L.sxg_poa_batch_run, C.c_void_p)
     fre = C.cast(L.sxg_poa_batch_free, C.c_void_p)
     return run, fre, engine.h
+
+
+def gpu_splitter(engine):
+    """(split, free, ctx) backed by the GPU engine: sxg_poa_split_batch / sxg_poa_split_free of libsxgpoa.so and the
+    engine handle -- the split provider of Smoother.split_blocks."""
+    L = engine.lib
+    return C.cast(L.sxg_poa_split_batch, C.c_void_p), C.cast(L.sxg_poa_split_free, C.c_void_p), engine.h
 
 
 class Smoother:
@@ -171,6 +181,19 @@ class Smoother:
         if self.L.sxg_blockset_block_ranges(self.b, block_id, arr):
             raise SmoothError(self.L.sxg_smooth_last_error().decode())
         return [(arr[k].path, arr[k].step_begin, arr[k].step_end, arr[k].length) for k in range(n)]
+
+    def split_blocks(self, splitter, block_id_min, ratio_min=0.0, min_dedup_depth=0):
+        """The splitting half of break_blocks (sxg_blockset_split; -I, -R and the dedup depth of the reference, whose
+        default depth 0 means "never split"): REPLACES the blockset.  Returns (blocks split, blocks left whole because
+        the provider could not take them)."""
+        split, fre, ctx = splitter
+        nb, ns, nl = C.c_void_p(), C.c_int64(), C.c_int64()
+        if self.L.sxg_blockset_split(self.g, self.b, float(block_id_min), float(ratio_min), int(min_dedup_depth), split, fre, ctx,
+                                     C.byref(nb), C.byref(ns), C.byref(nl)):
+            raise SmoothError(self.L.sxg_smooth_last_error().decode())
+        self.L.sxg_blockset_free(self.b)
+        self.b = nb
+        return ns.value, nl.value
 
     def close(self):
         if getattr(self, "b", None):
