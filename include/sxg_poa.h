@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-/* 5 (addition, no number change: no struct or existing entry point changed): sxg_poa_pair_identity_batch, sxg_poa_split_batch,
+/* 5 (addition, no number change): sxg_poa_kmer_jaccard_batch, sxg_poa_split_mash_batch and struct sxg_poa_split_mash -- the
+ *    mash-based branch of the identity split (src/breaks.cpp:388-471) on the device, decrees M1-M5.
+ * 5 (addition, no number change: no struct or existing entry point changed): sxg_poa_pair_identity_batch, sxg_poa_split_batch,
  *    sxg_poa_split_free and their two structs -- the identity split of break_blocks (src/breaks.cpp:335-586) on the device.
  * 5: sxg_poa_batch_out gained block_cycles (before _owner): per-block time on the device, the reference's POA_DEBUG column
  *    poa.time.ms (src/smooth.cpp:2121-2265); sxg_poa_sharded_timing.
@@ -343,7 +345,8 @@ void sxg_poa_align_free(sxg_poa_align_out *out);
  *       loop is left at the first member with (double)other_len / (double)curr_len < length_ratio_min[b] or with
  *       other_len < curr_len && other_len < (uint64)(identity / (1 - identity)) ("always" at identity 1); a sequence that
  *       joins nobody opens a new group.
- *   P4  the mash-based branch (:388-471, enabled by the CLI at a dedup depth >= 12000 only) is NOT built: no mash parameters here.
+ *   P4  the mash-based branch (:388-471, the CLI's default at a dedup depth >= 12000) is sxg_poa_split_mash_batch below, decrees
+ *       M1-M5; sxg_poa_split_batch is the walk without it.
  * One wavefront per pair / one persistent wavefront per block; the scratch comes out of the handle's memory budget; both calls run
  * inside ROCTx ranges and fill kernel_ms / cells / n_slots / dp_launches of sxg_poa_stats. */
 #define SXG_POA_SPLIT_PANEL 512 /* columns a wavefront sweeps at once; longer second sequences run panel after panel */
@@ -373,6 +376,41 @@ typedef struct sxg_poa_split_out {
 /* Returns SXG_E_BLOCK when some block failed (the others are valid), SXG_E_INVALID for a zero-length sequence. */
 int sxg_poa_split_batch(sxg_poa_handle *h, const sxg_poa_split_in *in, sxg_poa_split_out *out);
 void sxg_poa_split_free(sxg_poa_split_out *out);
+
+/* The mash-based branch of that split (src/breaks.cpp:388-471; -D / -L / -e / -k of src/main.cpp:102-112,302-320), decrees M1-M5
+ * of DESIGN.md section 9.  mkmh / rkmh are absent from the snapshot, so the sketch is fixed by decree:
+ *   M1  K(s, k) is the set of distinct canonical k-mers of s: 2 bits per letter, 1 <= k <= 32, the smaller of the forward value
+ *       and the value of the reverse complement; a window with an N (code 4) contributes nothing.  A sequence shorter than
+ *       min_len has the empty set.  |K| stands for seq_hashes[i].size().
+ *   M2  block b runs the mash rules iff min_len[b] > 0 (the caller applies the depth test of :388-390); min_len[b] >= k.
+ *   M3  two thresholds, computed on the host in double: f = v / (2 - v), v = exp(-(1 - t) k) with t = identity[b], and
+ *       jmin = w / (2 - w), w = exp(-(1 - e) k) with e = est_identity[b]; "1 - dist >= e" with dist = -ln(2J / (1 + J)) / k is
+ *       J >= jmin.
+ *   M4  P3's loops.  For sequence i, size_thr = (uint64)((double)|K_i| * f).  After the length-ratio break a pair with
+ *       curr_len >= min_len and other_len >= min_len is ELIGIBLE: in the forward pass, |K_other| < size_thr leaves the member
+ *       loop; otherwise one comparison is counted in n_mash, inter = |K_i n K_other|, uni = |K_i| + |K_other| - inter, and i
+ *       joins iff uni > 0 && (double)inter / (double)uni >= jmin; in the reverse-complement pass an eligible pair does nothing
+ *       and the walk goes on.  Any other pair takes P3's path unchanged (early exit, alignment, n_pairs).
+ *   M5  identity in (0, 1] as for sxg_poa_split_batch, est_identity in (0, 1], min_len 0 or >= k: anything else is SXG_E_INVALID.
+ * One workgroup per sequence builds, sorts (tiles of SXG_POA_MASH_SORT_TILE keys in LDS, merged in HBM) and de-duplicates the
+ * sets; one wavefront intersects two of them by a merge-path partition; one persistent wavefront per block walks M4.
+ * sxg_poa_stats after these calls: kernel_ms is the sum of the kernels, cells the cells of the alignments run, device_bytes the
+ * scratch including the sets. */
+#define SXG_POA_MASH_SORT_TILE 1024 /* keys sorted on chip at once; longer sequences merge tiles in device memory */
+/* Sets and intersections, for callers and tests: set_size[n_seqs] = |K(s, k)| of every sequence (no min_len here; a sequence
+ * longer than SXG_POA_MAX_SEQ_LEN is SXG_E_INVALID), inter[n_pairs] = |K(a) n K(b)|; kmers: NULL, or [seq_off[n_seqs]] -- the
+ * sorted set of sequence s at kmers + seq_off[s], the rest of its stretch zero. */
+int sxg_poa_kmer_jaccard_batch(sxg_poa_handle *h, int64_t n_seqs, const int64_t *seq_off, const uint8_t *bases, int32_t kmer_size,
+                               int64_t n_pairs, const int32_t *pair_a, const int32_t *pair_b,
+                               int32_t *set_size, int32_t *inter, uint64_t *kmers);
+typedef struct sxg_poa_split_mash {
+    int32_t kmer_size;
+    const int32_t *min_len;       /* [n_blocks] 0 = this block runs P3 only */
+    const double *est_identity;   /* [n_blocks] in (0, 1] */
+} sxg_poa_split_mash;
+/* sxg_poa_split_batch's contract plus M1-M5; n_mash: [n_blocks] set comparisons run, or NULL; out is freed by sxg_poa_split_free */
+int sxg_poa_split_mash_batch(sxg_poa_handle *h, const sxg_poa_split_in *in, const sxg_poa_split_mash *mash,
+                             sxg_poa_split_out *out, int64_t *n_mash);
 
 int sxg_poa_get_stats(sxg_poa_handle *h, sxg_poa_stats *out);
 /* Cap on device memory the handle may use for scratch arenas (bytes; 0 = default 3/4 of free). */

@@ -145,13 +145,25 @@ int sxg_blockset_break_ex(const sxg_graph *g, const sxg_blockset *in, uint64_t m
  * order, a group's members in the order they joined, each member contributing its original ranges in their original order.
  * New blocks are numbered consecutively in old-block order.  A block the provider reports with a status other than
  * SXG_ST_OK stays whole and is counted in *n_too_long; *n_split counts the blocks that were split.  The mash-based branch
- * (:388-471, dedup depth >= 12000 on the CLI) is not built (decree P4): there are no mash parameters.
+ * (:388-471, dedup depth >= 12000 on the CLI) is sxg_blockset_split_mash below; this call is the walk without it.
  * Split provider: exactly sxg_poa_split_batch's contract, ctx is its handle; called at most once, on the calling thread. */
 typedef int (*sxg_split_fn)(void *ctx, const sxg_poa_split_in *in, sxg_poa_split_out *out);
 typedef void (*sxg_split_free_fn)(sxg_poa_split_out *out);
 int sxg_blockset_split(const sxg_graph *g, const sxg_blockset *in, double block_group_identity, double length_ratio_min,
                        uint64_t min_dedup_depth, sxg_split_fn split, sxg_split_free_fn split_free, void *ctx, sxg_blockset **out,
                        int64_t *n_split, int64_t *n_too_long);
+/* The same with the mash-based branch of :388-471 (decrees M1-M5 of DESIGN.md section 9; -L / -D / -e / -k of src/main.cpp:
+ * 102-112,302-320): a candidate block whose dedup depth reaches min_depth_mash (0 = every candidate) compares its sequences of
+ * at least min_len_mash bases by the Jaccard index of their canonical k-mer sets against block_group_est_identity (<= 0: equal
+ * to block_group_identity); min_len_mash = 0 turns the branch off and the result is sxg_blockset_split's.  min_len_mash below
+ * kmer_size (when not 0), kmer_size outside 1..32 and an est identity above 1 are SXG_E_INVALID.
+ * Mash split provider: exactly sxg_poa_split_mash_batch's contract (n_mash is passed as NULL), ctx is its handle. */
+typedef int (*sxg_split_mash_fn)(void *ctx, const sxg_poa_split_in *in, const sxg_poa_split_mash *mash, sxg_poa_split_out *out,
+                                 int64_t *n_mash);
+int sxg_blockset_split_mash(const sxg_graph *g, const sxg_blockset *in, double block_group_identity, double length_ratio_min,
+                            uint64_t min_dedup_depth, uint64_t min_len_mash, uint64_t min_depth_mash, double block_group_est_identity,
+                            int32_t kmer_size, sxg_split_mash_fn split, sxg_split_free_fn split_free, void *ctx, sxg_blockset **out,
+                            int64_t *n_split, int64_t *n_too_long);
 int64_t sxg_blockset_block_size(const sxg_blockset *b, int64_t block_id);              /* ranges of a block, -1 on error */
 int sxg_blockset_block_ranges(const sxg_blockset *b, int64_t block_id, sxg_path_range *out); /* out[block size] */
 void sxg_blockset_free(sxg_blockset *b);

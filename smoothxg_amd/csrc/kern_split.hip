@@ -1,4 +1,6 @@
-// kern_split.hip -- the kernels of the identity split (pair_identity_kernel, split_kernel: poa_split.hip.h) and their
-// launchers, a translation unit of its own beside the kernel classes of kern_part.hip.
+// kern_split.hip -- the kernels of the identity split (pair_identity_kernel, split_kernel: poa_split.hip.h; mash_sketch_kernel,
+// mash_pair_kernel, split_mash_kernel: poa_mash.hip.h) and their launchers, a translation unit of its own beside the kernel
+// classes of kern_part.hip.
 #define SXG_SPLIT_IMPL
 #include "poa_split.hip.h"
+#include "poa_mash.hip.h"

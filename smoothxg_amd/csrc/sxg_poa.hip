@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +25,7 @@
 #include "poa_kernels.hip.h"       // slot layout, launch arguments, the persistent kernels (device side)
 #include "poa_kern_tables.hip.h"   // kernel classes by geometry; instantiated in the kern_*.hip translation units
 #include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
+#include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
 
 
 // ---------------------------------------------------------------------------------------
@@ -2336,11 +2338,14 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
 // The identity split of break_blocks (src/breaks.cpp:335-586): decrees P1-P4 (include/sxg_poa.h).  Kernels in
 // poa_split.hip.h / kern_split.hip; here the validation, the cost-sorted queues, the scratch (out of the memory budget) and the timing.
 static_assert(SXG_POA_SPLIT_PANEL == SXG_SPLIT_PANEL, "panel width of the header");
+static_assert(SXG_POA_MASH_SORT_TILE == SXG_MASH_SORT_TILE, "sort tile of the header");
 namespace {
 struct SplitBufs {
     DevBuf seq_off, bases, a, b, c, d, e, f, g, hh, work, queue, bound, lists;
+    DevBuf sets, set_size, sort_scratch, sketch_work, sketch_queue, min_len, mash_f, mash_jmin, n_mash;   // the mash-based branch
     ~SplitBufs() {
-        DevBuf* bs[] = {&seq_off, &bases, &a, &b, &c, &d, &e, &f, &g, &hh, &work, &queue, &bound, &lists};
+        DevBuf* bs[] = {&seq_off, &bases, &a, &b, &c, &d, &e, &f, &g, &hh, &work, &queue, &bound, &lists,
+                        &sets, &set_size, &sort_scratch, &sketch_work, &sketch_queue, &min_len, &mash_f, &mash_jmin, &n_mash};
         for (DevBuf* x : bs) x->release();
     }
 };
@@ -2368,6 +2373,39 @@ int split_upload_seqs(sxg_poa_handle* h, SplitBufs& B, int64_t n_seqs, const int
 template <class Tp> int split_up(sxg_poa_handle* h, DevBuf& d, const Tp* src, size_t n) {
     if (int rc = d.ensure(sizeof(Tp) * std::max<size_t>(n, 1))) return rc;
     if (n) HIPCHK(hipMemcpy(d.p, src, sizeof(Tp) * n, hipMemcpyHostToDevice));
+    return SXG_OK;
+}
+// M1 on the device: the sets of the sequences in `work` (made longest first here) into B.sets / B.set_size, every other sequence
+// with size 0.  B.seq_off / B.bases are uploaded; the launch goes on the handle's stream; *dev_bytes: sets and sort scratch.
+int mash_sketch(sxg_poa_handle* h, SplitBufs& B, int64_t ns, const int64_t* seq_off, std::vector<int32_t>& work, int k, bool clear_sets, size_t* dev_bytes) {
+    const int64_t nbases = seq_off[ns];
+    if (int rc = B.sets.ensure(8 * (size_t)std::max<int64_t>(nbases, 1))) return rc;
+    if (int rc = B.set_size.ensure(4 * (size_t)std::max<int64_t>(ns, 1))) return rc;
+    HIPCHK(hipMemsetAsync(B.set_size.p, 0, 4 * (size_t)std::max<int64_t>(ns, 1), h->stream));
+    if (clear_sets) HIPCHK(hipMemsetAsync(B.sets.p, 0, 8 * (size_t)std::max<int64_t>(nbases, 1), h->stream));
+    *dev_bytes = B.sets.cap + B.set_size.cap;
+    if (work.empty()) return SXG_OK;
+    auto len_of = [&](int32_t s) { return seq_off[s + 1] - seq_off[s]; };
+    std::stable_sort(work.begin(), work.end(), [&](int32_t x, int32_t y) { return len_of(x) > len_of(y); });
+    const int64_t max_nk = len_of(work[0]) - k + 1;
+    const int64_t scratch_keys = max_nk > SXG_MASH_SORT_TILE ? (max_nk + SXG_MASH_SORT_TILE - 1) / SXG_MASH_SORT_TILE * SXG_MASH_SORT_TILE : 0;
+    const size_t slot_bytes = 2 * sizeof(unsigned long long) * (size_t)scratch_keys;
+    int per_cu = 1;
+    sxg_mash_occupancy(0, &per_cu);
+    int64_t n_slots = std::min<int64_t>((int64_t)work.size(), (int64_t)std::max(h->num_cu, 1) * per_cu);
+    if (slot_bytes) n_slots = std::min<int64_t>(n_slots, (int64_t)(arena_budget(h) / slot_bytes));
+    if (n_slots < 1) return fail(SXG_E_NOMEM, "memory budget too small for one sort slot of the k-mer sets");
+    if (int rc = B.sort_scratch.ensure(std::max<size_t>(slot_bytes * (size_t)n_slots, 16))) return rc;
+    if (int rc = split_up(h, B.sketch_work, work.data(), work.size())) return rc;
+    if (int rc = B.sketch_queue.ensure(256)) return rc;
+    HIPCHK(hipMemsetAsync(B.sketch_queue.p, 0, 4, h->stream));
+    MashSketchArgs A;
+    A.seq_off = B.seq_off.as<int64_t>(); A.bases = B.bases.as<uint8_t>(); A.work = B.sketch_work.as<int32_t>(); A.n_work = (int32_t)work.size();
+    A.queue = B.sketch_queue.as<int32_t>(); A.k = k; A.scratch = B.sort_scratch.as<unsigned long long>(); A.scratch_keys = scratch_keys;
+    A.sets = B.sets.as<unsigned long long>(); A.set_size = B.set_size.as<int32_t>();
+    sxg_mash_launch_sketch(A, (int)n_slots, h->stream);
+    HIPCHK(hipGetLastError());
+    *dev_bytes += B.sort_scratch.cap;
     return SXG_OK;
 }
 void split_stats(sxg_poa_handle* h, float ms, uint64_t cells, int64_t n_slots, size_t dev_bytes) {
@@ -2454,7 +2492,9 @@ extern "C" void sxg_poa_split_free(sxg_poa_split_out* out) {
     delete (SplitOwner*)out->_owner;
     memset(out, 0, sizeof(*out));
 }
-extern "C" int sxg_poa_split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, sxg_poa_split_out* out) {
+// P3 for every block; with `mash`, M1-M5 on top of it (the blocks with min_len > 0 get their sets first)
+static int split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, const sxg_poa_split_mash* mash, sxg_poa_split_out* out, int64_t* n_mash,
+                       const char* range_name) {
     if (!h || !in || !out) return fail(SXG_E_INVALID, "NULL argument");
     memset(out, 0, sizeof(*out));
     const int nb = in->n_blocks;
@@ -2469,7 +2509,24 @@ extern "C" int sxg_poa_split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in
     for (int64_t s = 0; s < ns; ++s)
         if (in->seq_off[s + 1] <= in->seq_off[s]) return fail(SXG_E_INVALID, "sequence " + std::to_string(s) + " has no bases (or seq_off is not monotone)");
     if (ns > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
-    RoctxRange range("sxg_poa_split_batch");
+    std::vector<double> mash_f, mash_jmin;
+    if (mash) {                                                                     // M2, M3, M5
+        const int k = mash->kmer_size;
+        if (k < 1 || k > 32) return fail(SXG_E_INVALID, "kmer_size must be in 1..32");
+        if (nb > 0 && (!mash->min_len || !mash->est_identity)) return fail(SXG_E_INVALID, "split_mash has NULL arrays");
+        mash_f.assign((size_t)std::max(nb, 1), 0.0); mash_jmin.assign((size_t)std::max(nb, 1), 0.0);
+        for (int b = 0; b < nb; ++b) {
+            const double e = mash->est_identity[b];
+            if (mash->min_len[b] < 0 || (mash->min_len[b] > 0 && mash->min_len[b] < k))
+                return fail(SXG_E_INVALID, "block " + std::to_string(b) + ": min_len must be 0 or at least kmer_size");
+            if (!(e > 0.0 && e <= 1.0)) return fail(SXG_E_INVALID, "block " + std::to_string(b) + ": est_identity must be in (0, 1]");
+            const double v = exp(-(1.0 - in->identity[b]) * (double)k), w = exp(-(1.0 - e) * (double)k);
+            mash_f[(size_t)b] = v / (2.0 - v);
+            mash_jmin[(size_t)b] = w / (2.0 - w);
+        }
+        if (n_mash) for (int b = 0; b < nb; ++b) n_mash[b] = 0;
+    }
+    RoctxRange range(range_name);
     HIPCHK(hipSetDevice(h->device));
     h->stats = sxg_poa_stats{};
     SplitOwner* o = new SplitOwner();
@@ -2513,7 +2570,14 @@ extern "C" int sxg_poa_split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in
         const int64_t bound_rows = max_len + 1;
         const size_t slot_bytes = 3 * sizeof(sxg_key_t) * (size_t)bound_rows + 2 * sizeof(int32_t) * (size_t)max_depth;
         int64_t n_slots = 0;
-        SPLIT_CK(split_slots(h, 1, (int64_t)work.size(), slot_bytes, &n_slots));
+        if (!mash) SPLIT_CK(split_slots(h, 1, (int64_t)work.size(), slot_bytes, &n_slots));
+        else {
+            int per_cu = 1;
+            sxg_mash_occupancy(2, &per_cu);
+            n_slots = std::min<int64_t>((int64_t)work.size(), (int64_t)std::max(h->num_cu, 1) * per_cu);
+            n_slots = std::min<int64_t>(n_slots, (int64_t)(arena_budget(h) / std::max<size_t>(slot_bytes, 1)));
+            if (n_slots < 1) { sxg_poa_split_free(out); return fail(SXG_E_NOMEM, "memory budget too small for one split slot"); }
+        }
         SPLIT_CK(B.bound.ensure(3 * sizeof(sxg_key_t) * (size_t)bound_rows * (size_t)n_slots));
         SPLIT_CK(B.lists.ensure(2 * sizeof(int32_t) * (size_t)max_depth * (size_t)n_slots));
         SPLIT_HCK(hipMemsetAsync(B.queue.p, 0, 4, h->stream));
@@ -2527,8 +2591,29 @@ extern "C" int sxg_poa_split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in
         A.queue = B.queue.as<int32_t>(); A.bound = B.bound.as<sxg_key_t>(); A.bound_rows = bound_rows;
         A.lists = B.lists.as<int32_t>(); A.list_cap = max_depth;
         A.group = B.d.as<int32_t>(); A.n_groups = B.e.as<int32_t>(); A.n_pairs = B.f.as<int64_t>(); A.cells = B.g.as<uint64_t>();
+        size_t mash_bytes = 0;
+        MashBlockArgs M;
+        std::vector<int32_t> sketch_work;
+        if (mash) {
+            for (const auto& cb : cost) {                                          // M1: the eligible sequences of the blocks that run
+                const int b = cb.second;
+                if (mash->min_len[b] <= 0) continue;
+                for (int64_t s = in->blk_off[b]; s < in->blk_off[b + 1]; ++s)
+                    if (in->seq_off[s + 1] - in->seq_off[s] >= mash->min_len[b]) sketch_work.push_back((int32_t)s);
+            }
+            SPLIT_CK(split_up(h, B.min_len, mash->min_len, (size_t)nb));
+            SPLIT_CK(split_up(h, B.mash_f, mash_f.data(), (size_t)nb));
+            SPLIT_CK(split_up(h, B.mash_jmin, mash_jmin.data(), (size_t)nb));
+            SPLIT_CK(B.n_mash.ensure(8 * (size_t)nb));
+            SPLIT_HCK(hipMemsetAsync(B.n_mash.p, 0, 8 * (size_t)nb, h->stream));
+        }
         SPLIT_HCK(hipEventRecord(h->ev0, h->stream));
-        sxg_split_launch_blocks(A, (int)n_slots, h->stream);
+        if (mash) {
+            SPLIT_CK(mash_sketch(h, B, ns, in->seq_off, sketch_work, mash->kmer_size, false, &mash_bytes));
+            M.S = A; M.min_len = B.min_len.as<int32_t>(); M.f = B.mash_f.as<double>(); M.jmin = B.mash_jmin.as<double>();
+            M.sets = B.sets.as<unsigned long long>(); M.set_size = B.set_size.as<int32_t>(); M.n_mash = B.n_mash.as<int64_t>();
+            sxg_mash_launch_blocks(M, (int)n_slots, h->stream);
+        } else sxg_split_launch_blocks(A, (int)n_slots, h->stream);
         SPLIT_HCK(hipGetLastError());
         SPLIT_HCK(hipEventRecord(h->ev1, h->stream));
         SPLIT_HCK(hipEventSynchronize(h->ev1));
@@ -2539,13 +2624,83 @@ extern "C" int sxg_poa_split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in
         SPLIT_HCK(hipMemcpy(o->n_groups.data(), B.e.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
         SPLIT_HCK(hipMemcpy(o->n_pairs.data(), B.f.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
         SPLIT_HCK(hipMemcpy(cells.data(), B.g.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
+        if (mash && n_mash) SPLIT_HCK(hipMemcpy(n_mash, B.n_mash.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
         uint64_t total = 0;
         for (uint64_t c : cells) total += c;
-        split_stats(h, ms, total, n_slots, B.bound.cap + B.lists.cap);
+        split_stats(h, ms, total, n_slots, B.bound.cap + B.lists.cap + mash_bytes);
+        if (mash && !sketch_work.empty()) h->stats.dp_launches = 2;
     }
 #undef SPLIT_CK
 #undef SPLIT_HCK
     if (any_failed) return fail(SXG_E_BLOCK, "a block holds a sequence longer than SXG_POA_MAX_SEQ_LEN");
+    return SXG_OK;
+}
+extern "C" int sxg_poa_split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, sxg_poa_split_out* out) {
+    return split_batch(h, in, nullptr, out, nullptr, "sxg_poa_split_batch");
+}
+extern "C" int sxg_poa_split_mash_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, const sxg_poa_split_mash* mash, sxg_poa_split_out* out,
+                                        int64_t* n_mash) {
+    if (!mash) return fail(SXG_E_INVALID, "NULL argument");
+    return split_batch(h, in, mash, out, n_mash, "sxg_poa_split_mash_batch");
+}
+
+// M1 for callers and tests: the set of every sequence (no min_len), and the exact intersection of pairs of them.
+extern "C" int sxg_poa_kmer_jaccard_batch(sxg_poa_handle* h, int64_t n_seqs, const int64_t* seq_off, const uint8_t* bases, int32_t kmer_size,
+                                          int64_t n_pairs, const int32_t* pair_a, const int32_t* pair_b, int32_t* set_size, int32_t* inter,
+                                          uint64_t* kmers) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    if (n_seqs < 0 || n_seqs > 0x7fffffff || n_pairs < 0 || n_pairs > 0x7fffffff || !seq_off || (n_seqs > 0 && !set_size) ||
+        (n_pairs > 0 && (!pair_a || !pair_b || !inter)))
+        return fail(SXG_E_INVALID, "kmer_jaccard: bad argument");
+    if (kmer_size < 1 || kmer_size > 32) return fail(SXG_E_INVALID, "kmer_size must be in 1..32");
+    if (seq_off[0] != 0) return fail(SXG_E_INVALID, "seq_off[0] must be 0");
+    std::vector<int32_t> work;
+    for (int64_t s = 0; s < n_seqs; ++s) {
+        const int64_t len = seq_off[s + 1] - seq_off[s];
+        if (len < 0) return fail(SXG_E_INVALID, "seq_off not monotone");
+        if (len > SXG_POA_MAX_SEQ_LEN) return fail(SXG_E_INVALID, "sequence " + std::to_string(s) + " is longer than SXG_POA_MAX_SEQ_LEN");
+        if (len >= kmer_size) work.push_back((int32_t)s);
+    }
+    if (seq_off[n_seqs] > 0 && !bases) return fail(SXG_E_INVALID, "bases is NULL");
+    for (int64_t p = 0; p < n_pairs; ++p)
+        if (pair_a[p] < 0 || pair_a[p] >= n_seqs || pair_b[p] < 0 || pair_b[p] >= n_seqs) return fail(SXG_E_INVALID, "pair " + std::to_string(p) + ": no such sequence");
+    RoctxRange range("sxg_poa_kmer_jaccard_batch");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    if (n_seqs == 0) return SXG_OK;
+    SplitBufs B;
+    if (int rc = split_upload_seqs(h, B, n_seqs, seq_off, bases)) return rc;
+    size_t dev_bytes = 0;
+    int64_t n_slots = 0;
+    if (n_pairs) {
+        if (int rc = split_up(h, B.a, pair_a, (size_t)n_pairs)) return rc;
+        if (int rc = split_up(h, B.b, pair_b, (size_t)n_pairs)) return rc;
+        if (int rc = B.c.ensure(4 * (size_t)n_pairs)) return rc;
+        if (int rc = B.queue.ensure(256)) return rc;
+        HIPCHK(hipMemsetAsync(B.queue.p, 0, 4, h->stream));
+    }
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    if (int rc = mash_sketch(h, B, n_seqs, seq_off, work, kmer_size, kmers != nullptr, &dev_bytes)) return rc;
+    if (n_pairs) {
+        int per_cu = 1;
+        sxg_mash_occupancy(1, &per_cu);
+        n_slots = std::min<int64_t>(n_pairs, (int64_t)std::max(h->num_cu, 1) * per_cu);
+        MashPairArgs A;
+        A.seq_off = B.seq_off.as<int64_t>(); A.sets = B.sets.as<unsigned long long>(); A.set_size = B.set_size.as<int32_t>();
+        A.pair_a = B.a.as<int32_t>(); A.pair_b = B.b.as<int32_t>(); A.n_pairs = (int32_t)n_pairs; A.queue = B.queue.as<int32_t>();
+        A.inter = B.c.as<int32_t>();
+        sxg_mash_launch_pairs(A, (int)n_slots, h->stream);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    HIPCHK(hipMemcpy(set_size, B.set_size.p, 4 * (size_t)n_seqs, hipMemcpyDeviceToHost));
+    if (n_pairs) HIPCHK(hipMemcpy(inter, B.c.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    if (kmers && seq_off[n_seqs] > 0) HIPCHK(hipMemcpy(kmers, B.sets.p, 8 * (size_t)seq_off[n_seqs], hipMemcpyDeviceToHost));
+    split_stats(h, ms, 0, n_slots, dev_bytes);
+    h->stats.dp_launches = n_pairs ? 2 : 1;
     return SXG_OK;
 }
 

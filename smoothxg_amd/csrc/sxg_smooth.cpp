@@ -2801,14 +2801,25 @@ int sxg_blockset_break_ex(const sxg_graph* g, const sxg_blockset* in, uint64_t m
 }  // extern "C"
 // The splitting half of break_blocks (src/breaks.cpp:335-586), decree P3: dedup, guards and sort here, the greedy clustering
 // with its pair alignments behind the split provider (ONE call for all candidate blocks), the reassembly here.
+// With `mash` (the mash-based branch, :388-471, decrees M1-M5): M2's per-block decision here, the sets and the walk of M4 behind
+// the mash split provider.
+struct mash_opts_t { uint64_t min_len, min_depth; double est_identity; int32_t kmer_size; sxg_split_mash_fn split; };
 static int blockset_split(const sxg_graph* g, const sxg_blockset* in, double t, double ratio_min, uint64_t min_dedup_depth, sxg_split_fn split,
-                          sxg_split_free_fn split_free, void* ctx, sxg_blockset** out, int64_t* n_split, int64_t* n_too_long) {
-    if (!g || !in || !out || !split || !split_free) return fail(SXG_E_INVALID, "NULL argument");
+                          const mash_opts_t* mash, sxg_split_free_fn split_free, void* ctx, sxg_blockset** out, int64_t* n_split,
+                          int64_t* n_too_long) {
+    if (!g || !in || !out || !(mash ? (bool)mash->split : (bool)split) || !split_free) return fail(SXG_E_INVALID, "NULL argument");
     *out = nullptr;
     if (n_split) *n_split = 0;
     if (n_too_long) *n_too_long = 0;
     if (!(t <= 1.0)) return fail(SXG_E_INVALID, "block_group_identity must not exceed 1");
     if (ratio_min != ratio_min) return fail(SXG_E_INVALID, "length_ratio_min is NaN");
+    double est = t;
+    if (mash) {                                                                         // src/main.cpp:305,317
+        if (mash->kmer_size < 1 || mash->kmer_size > 32) return fail(SXG_E_INVALID, "kmer_size must be in 1..32");
+        if (mash->min_len > 0 && mash->min_len < (uint64_t)mash->kmer_size) return fail(SXG_E_INVALID, "min_len_mash must be 0 or at least kmer_size");
+        if (mash->est_identity > 0) est = mash->est_identity;
+        if (!(est <= 1.0)) return fail(SXG_E_INVALID, "block_group_est_identity must not exceed 1");
+    }
     const int64_t nb = (int64_t)in->blocks.size();
     struct cand_t { int64_t block; std::vector<std::string> seqs; std::vector<std::vector<uint64_t>> ranks; };   // dedup'd, sorted
     std::vector<cand_t> cands((size_t)nb);
@@ -2868,7 +2879,19 @@ static int blockset_split(const sxg_graph* g, const sxg_blockset* in, double t, 
     si.identity = ident.data(); si.length_ratio_min = ratio.data();
     sxg_poa_split_out so;
     memset(&so, 0, sizeof(so));
-    const int rc = split(ctx, &si, &so);
+    int rc;
+    if (mash) {
+        std::vector<int32_t> min_len((size_t)nc, 0);
+        std::vector<double> est_id((size_t)nc, est);
+        for (int32_t c = 0; c < nc; ++c) {                                              // M2 (:388-390)
+            const uint64_t n_dedup = (uint64_t)(blk_off[(size_t)c + 1] - blk_off[(size_t)c]);
+            if (mash->min_len > 0 && (mash->min_depth == 0 || n_dedup >= mash->min_depth))
+                min_len[(size_t)c] = (int32_t)std::min<uint64_t>(mash->min_len, 0x7fffffffu);
+        }
+        sxg_poa_split_mash sm;
+        sm.kmer_size = mash->kmer_size; sm.min_len = min_len.data(); sm.est_identity = est_id.data();
+        rc = mash->split(ctx, &si, &sm, &so, nullptr);
+    } else rc = split(ctx, &si, &so);
     if (rc != SXG_OK && rc != SXG_E_BLOCK) { delete bs; return fail(rc < 0 ? rc : SXG_E_INVALID, "the split provider failed with code " + std::to_string(rc)); }
     auto refuse = [&](const std::string& why) { split_free(&so); delete bs; return fail(SXG_E_INVALID, "split provider: " + why); };
     if (so.n_blocks != nc || so.n_seqs != (int64_t)blk_off.back() || !so.group || !so.n_groups || !so.status) return refuse("result does not match the batch");
@@ -2929,7 +2952,15 @@ int sxg_smooth_maf_gfa(const sxg_graph* g, const sxg_blockset* b, const sxg_smoo
 
 int sxg_blockset_split(const sxg_graph* g, const sxg_blockset* in, double block_group_identity, double length_ratio_min, uint64_t min_dedup_depth,
                        sxg_split_fn split, sxg_split_free_fn split_free, void* ctx, sxg_blockset** out, int64_t* n_split, int64_t* n_too_long) {
-    return guarded([&] { return blockset_split(g, in, block_group_identity, length_ratio_min, min_dedup_depth, split, split_free, ctx, out, n_split, n_too_long); });
+    return guarded([&] { return blockset_split(g, in, block_group_identity, length_ratio_min, min_dedup_depth, split, nullptr, split_free, ctx, out, n_split, n_too_long); });
+}
+
+int sxg_blockset_split_mash(const sxg_graph* g, const sxg_blockset* in, double block_group_identity, double length_ratio_min, uint64_t min_dedup_depth,
+                            uint64_t min_len_mash, uint64_t min_depth_mash, double block_group_est_identity, int32_t kmer_size,
+                            sxg_split_mash_fn split, sxg_split_free_fn split_free, void* ctx, sxg_blockset** out, int64_t* n_split,
+                            int64_t* n_too_long) {
+    const mash_opts_t mash{min_len_mash, min_depth_mash, block_group_est_identity, kmer_size, split};
+    return guarded([&] { return blockset_split(g, in, block_group_identity, length_ratio_min, min_dedup_depth, nullptr, &mash, split_free, ctx, out, n_split, n_too_long); });
 }
 
 // blockset_t from the caller's own blocks (src/blocks.hpp:29-43,70-120): block k owns ranges

@@ -88,11 +88,18 @@ class SplitOut(C.Structure):
                 ("n_pairs", _i64p), ("status", _i32p), ("_owner", C.c_void_p)]
 
 
+class SplitMash(C.Structure):
+    """sxg_poa_split_mash: the k-mer size and, per block, the least length of a sequence compared by its k-mer set (0: the
+    block runs the edit-based walk only) and the estimated-identity threshold."""
+    _fields_ = [("kmer_size", C.c_int32), ("min_len", _i32p), ("est_identity", C.POINTER(C.c_double))]
+
+
+MASH_SORT_TILE = 1024   # SXG_POA_MASH_SORT_TILE: k-mers a workgroup sorts on chip at once
 SPLIT_PANEL = 512   # SXG_POA_SPLIT_PANEL: columns of the second sequence a wavefront sweeps at once
 MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
 ST_TOO_LONG = 5
 
-EXPORTS = ["sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
+EXPORTS = ["sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
            "sxg_poa_get_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
@@ -146,6 +153,8 @@ def load_library(build_if_missing=True):
     L.sxg_poa_pair_identity_batch.argtypes = [vp, C.c_int64, _i64p, _u8p, C.c_int64, _i32p, _i32p, _u8p, _i32p, _i32p, _i32p, _i32p]
     L.sxg_poa_split_batch.argtypes = [vp, C.POINTER(SplitIn), C.POINTER(SplitOut)]
     L.sxg_poa_split_free.argtypes = [C.POINTER(SplitOut)]
+    L.sxg_poa_kmer_jaccard_batch.argtypes = [vp, C.c_int64, _i64p, _u8p, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint64)]
+    L.sxg_poa_split_mash_batch.argtypes = [vp, C.POINTER(SplitIn), C.POINTER(SplitMash), C.POINTER(SplitOut), _i64p]
     L.sxg_poa_split_free.restype = None
     L.sxg_xxh64.restype = C.c_uint64
     L.sxg_xxh64.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64]
@@ -503,6 +512,52 @@ class PoaEngine:
             grp = _arr(out.group, int(blk_off[-1]), np.int32)
             ng, npairs, st = _arr(out.n_groups, nb, np.int32), _arr(out.n_pairs, nb, np.int64), _arr(out.status, nb, np.int32)
             return [(grp[blk_off[b]:blk_off[b + 1]], int(ng[b]), int(npairs[b]), int(st[b])) for b in range(nb)]
+        finally:
+            self.lib.sxg_poa_split_free(C.byref(out))
+
+    def kmer_jaccard(self, seqs, pairs, k, want_sets=False):
+        """sxg_poa_kmer_jaccard_batch.  seqs: code arrays; pairs: (a, b) indices into seqs.  Returns (set_size, inter): the
+        number of distinct canonical k-mers of every sequence and the size of the intersection of every pair (int32
+        arrays); with want_sets also the sorted uint64 set of every sequence, as a list."""
+        bases, seq_off = self._flat(seqs)
+        ns, n = len(seqs), len(pairs)
+        pa = np.ascontiguousarray([p[0] for p in pairs], np.int32) if n else np.zeros(1, np.int32)
+        pb = np.ascontiguousarray([p[1] for p in pairs], np.int32) if n else np.zeros(1, np.int32)
+        size, inter = np.zeros(max(ns, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        kmers = np.zeros(max(int(seq_off[-1]), 1), np.uint64) if want_sets else None
+        rc = self.lib.sxg_poa_kmer_jaccard_batch(self.h, ns, _p(seq_off, C.c_int64), _p(bases, C.c_uint8), int(k), n, _p(pa, C.c_int32),
+                                                 _p(pb, C.c_int32), _p(size, C.c_int32), _p(inter, C.c_int32),
+                                                 _p(kmers, C.c_uint64) if want_sets else None)
+        if rc:
+            raise self._err("sxg_poa_kmer_jaccard_batch")
+        if want_sets:
+            return size[:ns], inter[:n], [kmers[seq_off[s]:seq_off[s] + size[s]].copy() for s in range(ns)]
+        return size[:ns], inter[:n]
+
+    def split_mash(self, blocks, identity, length_ratio_min, kmer_size, min_len, est_identity=None, check=True):
+        """sxg_poa_split_mash_batch: split() with the mash-based branch.  min_len: one value or one per block, 0 = that block
+        runs the edit-based walk only; est_identity: one value or one per block, None = identity.  Returns one (groups,
+        n_groups, n_pairs, n_mash, status) per block."""
+        nb = len(blocks)
+        bases, seq_off = self._flat([x for blk in blocks for x in blk])
+        blk_off = np.zeros(nb + 1, np.int32)
+        if nb:
+            blk_off[1:] = np.cumsum([len(b) for b in blocks])
+        per_block = lambda v, dt: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (nb,)) if nb else np.zeros(1), dt)
+        ident, ratio = per_block(identity, np.float64), per_block(length_ratio_min, np.float64)
+        est = ident.copy() if est_identity is None else per_block(est_identity, np.float64)
+        ml = per_block(min_len, np.int32)
+        si = SplitIn(nb, _p(blk_off, C.c_int32), _p(seq_off, C.c_int64), _p(bases, C.c_uint8), _p(ident, C.c_double), _p(ratio, C.c_double))
+        sm = SplitMash(int(kmer_size), _p(ml, C.c_int32), _p(est, C.c_double))
+        nm = np.zeros(max(nb, 1), np.int64)
+        out = SplitOut()
+        rc = self.lib.sxg_poa_split_mash_batch(self.h, C.byref(si), C.byref(sm), C.byref(out), _p(nm, C.c_int64))
+        try:
+            if rc and (check or rc != -4):
+                raise self._err("sxg_poa_split_mash_batch")
+            grp = _arr(out.group, int(blk_off[-1]), np.int32)
+            ng, npairs, st = _arr(out.n_groups, nb, np.int32), _arr(out.n_pairs, nb, np.int64), _arr(out.status, nb, np.int32)
+            return [(grp[blk_off[b]:blk_off[b + 1]], int(ng[b]), int(npairs[b]), int(nm[b]), int(st[b])) for b in range(nb)]
         finally:
             self.lib.sxg_poa_split_free(C.byref(out))
 

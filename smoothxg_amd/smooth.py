@@ -15,6 +15,7 @@ RUN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.BatchIn), C.POINTER(_po
 FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.BatchOut))
 SPLIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitOut))
 SPLIT_FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.SplitOut))
+SPLIT_MASH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitMash), C.POINTER(_poa.SplitOut), C.POINTER(C.c_int64))
 
 
 class SmoothParams(C.Structure):
@@ -31,7 +32,7 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_blockset_free", "sxg_blockset_size", "sxg_block_collect_text", "sxg_block_graph_gfa",
            "sxg_smooth_gfa", "sxg_adaptive_poa_scores", "sxg_block_identity_threshold",
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
-           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_merge_default_params", "sxg_smooth_maf_gfa"]
+           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa"]
 
 
 class MergeParams(C.Structure):
@@ -72,6 +73,8 @@ def load_library():
     L.sxg_blockset_break.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
     L.sxg_blockset_break_ex.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_double, C.c_uint64, C.c_int, C.POINTER(vp)]
     L.sxg_blockset_split.argtypes = [vp, vp, C.c_double, C.c_double, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.sxg_blockset_split_mash.argtypes = [vp, vp, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, C.c_int32, vp, vp, vp,
+                                          C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.sxg_blockset_free.argtypes = [vp]
     L.sxg_blockset_size.restype = C.c_int64
     L.sxg_blockset_size.argtypes = [vp]
@@ -123,6 +126,13 @@ def gpu_splitter(engine):
     engine handle -- the split provider of Smoother.split_blocks."""
     L = engine.lib
     return C.cast(L.sxg_poa_split_batch, C.c_void_p), C.cast(L.sxg_poa_split_free, C.c_void_p), engine.h
+
+
+def gpu_mash_splitter(engine):
+    """(split, free, ctx) backed by the GPU engine: sxg_poa_split_mash_batch / sxg_poa_split_free and the engine handle --
+    the mash split provider of Smoother.split_blocks_mash."""
+    L = engine.lib
+    return C.cast(L.sxg_poa_split_mash_batch, C.c_void_p), C.cast(L.sxg_poa_split_free, C.c_void_p), engine.h
 
 
 class Smoother:
@@ -190,6 +200,22 @@ class Smoother:
         nb, ns, nl = C.c_void_p(), C.c_int64(), C.c_int64()
         if self.L.sxg_blockset_split(self.g, self.b, float(block_id_min), float(ratio_min), int(min_dedup_depth), split, fre, ctx,
                                      C.byref(nb), C.byref(ns), C.byref(nl)):
+            raise SmoothError(self.L.sxg_smooth_last_error().decode())
+        self.L.sxg_blockset_free(self.b)
+        self.b = nb
+        return ns.value, nl.value
+
+    def split_blocks_mash(self, splitter, block_id_min, ratio_min=0.0, min_dedup_depth=0, min_len_mash=200, min_depth_mash=12000,
+                          est_identity=0.0, kmer_size=17):
+        """split_blocks with the mash-based branch (sxg_blockset_split_mash; -L, -D, -e and -k of the reference, with its
+        defaults): a block of at least min_depth_mash dedup'd sequences (0: every block) compares its sequences of at least
+        min_len_mash bases by their k-mer sets; est_identity <= 0 means block_id_min.  splitter: a mash split provider
+        (gpu_mash_splitter).  REPLACES the blockset; returns as split_blocks does."""
+        split, fre, ctx = splitter
+        nb, ns, nl = C.c_void_p(), C.c_int64(), C.c_int64()
+        if self.L.sxg_blockset_split_mash(self.g, self.b, float(block_id_min), float(ratio_min), int(min_dedup_depth), int(min_len_mash),
+                                          int(min_depth_mash), float(est_identity), int(kmer_size), split, fre, ctx,
+                                          C.byref(nb), C.byref(ns), C.byref(nl)):
             raise SmoothError(self.L.sxg_smooth_last_error().decode())
         self.L.sxg_blockset_free(self.b)
         self.b = nb
