@@ -2,9 +2,9 @@
 // traceback that DERIVES the alignment from stored values.
 //
 // Same semantics (S1-S5) and the same row-uniform structure as poa_dp.hip.h, but every VGPR
-// holds TWO cells: lane t owns strip "lo" = columns [t*W, (t+1)*W) and strip "hi" = columns
-// [T*W + t*W, T*W + (t+1)*W); the low / high 16 bits of a register are the two strips, so every
-// add/max serves two cells.  Measured on MI355X (profiles/ubench/valu_rate.hip): a wave64
+// holds TWO cells: lane t owns two ADJACENT strips, "lo" = columns [2t*W, (2t+1)*W) and "hi" = columns
+// [(2t+1)*W, (2t+2)*W) (round 10; before that the two strips of a lane lay 64 strips apart); the low / high 16 bits of a
+// register are the two strips, so every add/max serves two cells.  Measured on MI355X (profiles/ubench/valu_rate.hip): a wave64
 // integer VALU instruction issues every 4 cycles whether it is 32-bit or packed 16-bit, and the
 // 32-bit sweep is bound by exactly that issue rate -- packing is the lever.
 //
@@ -107,7 +107,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t p16_rsrc(const void* base, con
 }
 
 // ---- the traceback plane of the packed sweep: a band of strips per row -------------------------
-// Strip s = columns [s*W, (s+1)*W) (s < T: lo strips, s >= T: hi strips).  Row r keeps the BS strips
+// Strip s = columns [s*W, (s+1)*W) (even s: the lo strip of lane s / 2 mod 64, odd s: its hi strip).  Row r keeps the BS strips
 // starting at band_first_strip(hint of r), strip s in slot s mod BS.  A row's cells are laid out in GROUPS of four
 // columns-in-strip: [group][slot][column of the group], i.e. cell (r, column j), k = j % W, slot = (j / W) % BS is the dword
 //     plane[(r * W + 4 * (k / 4)) * BS + slot * gw(k / 4) + k % 4]  =  H int16 | (H - oF) << 16 | (H - oO) << 24,
@@ -264,10 +264,13 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     int* lds = (int*)smem;
     // (TFIX = 64: a one-wave class -- no left or right neighbour, the mailbox code folds away: 1.7 % on 8000 x 16 x 1 kbp)
     const int t = threadIdx.x, lane = t & 63, wv = ONEW ? 0 : __builtin_amdgcn_readfirstlane(t >> 6);
-    // Wave w owns the 128 strips [128 w, 128 w + 128): lane l its strips 128 w + l (low halves) and 128 w + 64 + l (high
+    // Wave w owns the 128 strips [128 w, 128 w + 128): lane l its strips 128 w + 2 l (low halves) and 128 w + 2 l + 1 (high
     // halves).  A wave's columns are contiguous, so the ONLY thing that crosses a wave boundary inside a row is what crosses
     // one column boundary: the gap states entering the wave's first column and the diagonal's source left of it.
-    const int s_lo = wv * 128 + lane, s_hi = s_lo + 64;
+    // (Round 10: ADJACENT strips in a lane.  With strips l and 64 + l the low and the high halves were two separate 64-element
+    //  prefix problems per gap piece, stitched by a v_readlane; now a lane's 2 W columns are contiguous, the wave is ONE prefix
+    //  problem over the lanes, and what enters a high strip is lane-local.)
+    const int s_lo = wv * 128 + 2 * lane, s_hi = s_lo + 1;
     const int j0 = s_lo * W, j0h = s_hi * W;   // first columns of my two strips
     // scoring values are block-uniform: keep them (and everything derived) in SGPRs
     // DS: the class is compiled FOR smoothxg's default scores 1,4,6,2,26,1 (src/main.cpp:322-327) -- the six values and everything
@@ -313,7 +316,8 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     // w-1 has handed over, through a ring of P16_MBOX mailboxes in LDS, the three values that cross its left edge in row i:
     // E and Q entering its first column and H of the column left of it (one 16-byte word {E, Q, H, row}, written and read
     // by single LDS instructions; the row number is the "full" flag).  Everything else a wave reads it wrote itself: rows
-    // in the ring are lane-private, and a stored row carries the left-neighbour column of every lane as one more word.
+    // in the ring are lane-private, and a stored row carries the left-neighbour columns of every lane's two strips (the last
+    // column of the lane before it, and of its own low strip) as one more word.
     // Waves drift apart by up to P16_MBOX rows (a writer checks every P16_MBOX / 2 rows that its reader has freed the
     // slots it is about to reuse), so a wave that waits -- for a stored predecessor row, for its SIMD -- delays its
     // successors only once that slack is used up: the per-row cost is the AVERAGE over the waves, not the maximum that
@@ -692,19 +696,23 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
         if (SW) { a = pk_max(a, B2); if (CVX) b = pk_max(b, B2); }
         a = P16_DEC(a, Gm, G2);
         if (CVX) b = P16_DEC(b, Qm, Q2);
-        // ---- carries (32-bit), inside the wave.  Wave-local strip index u: lo strips 0..63, then hi strips 64..127; what
-        // came in through the mailbox is strip u = -1.  y_u = a_u - u*W*e;  E entering strip u = max_{u'<u} y_u' + (u-1)*W*e
+        // ---- carries (32-bit), inside the wave.  Wave-local strip index u = 2 lane (lo strip), 2 lane + 1 (hi strip); what
+        // came in through the mailbox is strip u = -1.  y_u = a_u - u*W*e;  E entering strip u = max_{u'<u} y_u' + (u-1)*W*e.
+        // The strips left of a lane's pair are those of the lanes before it: ONE inclusive scan per gap piece over the lanes'
+        // max(y_lo, y_hi), shifted by a lane and joined with the mailbox, is X = max_{u' < 2 lane} y_u'; the hi strip adds its
+        // own lane's y_lo.  (max is associative: the same values as the two scans per piece of the 64-apart layout.)
         // (the lane's offsets are rebuilt from an opaque copy of the lane every row: hoisted out of the loop
         // they are six more loop-invariant VGPRs, which the allocator spills and reloads per row --
         // and a scratch reload is an in-order vmcnt wait behind every store still in flight)
         int tt = lane;
         asm volatile("" : "+v"(tt));
         const int tWe = __mul24(tt, We), tWc = __mul24(tt, Wc);
-        int ya_lo = pk_lo(a) - tWe, ya_hi = pk_hi(a) - tWe - 64 * We;
-        int yb_lo = CVX ? pk_lo(b) - tWc : NEG, yb_hi = CVX ? pk_hi(b) - tWc - 64 * Wc : NEG;
+        const int ya_lo = pk_lo(a) - 2 * tWe, ya_hi = pk_hi(a) - 2 * tWe - We;
+        const int yb_lo = CVX ? pk_lo(b) - 2 * tWc : NEG, yb_hi = CVX ? pk_hi(b) - 2 * tWc - Wc : NEG;
+        int xa = max(ya_lo, ya_hi), xb = max(yb_lo, yb_hi);
         if (!(EXP & 8)) {
-        ya_lo = sxg_wave_incl_max(ya_lo); ya_hi = sxg_wave_incl_max(ya_hi);
-        if (CVX) { yb_lo = sxg_wave_incl_max(yb_lo); yb_hi = sxg_wave_incl_max(yb_hi); }
+        xa = sxg_wave_incl_max(xa);
+        if (CVX) xb = sxg_wave_incl_max(xb);
         }
         RP_MARK(1);  // pass 1 + in-wave scan
         // what crosses my left edge in this row: {E, Q entering my first column, H of the column left of it, row}
@@ -718,15 +726,12 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
             if (lane == 0) prog[wv] = i;
         }
         RP_MARK(2);  // waiting for the left neighbour
-        {
-            const int ta = max(__builtin_amdgcn_readlane(ya_lo, 63), in_e), tb = max(__builtin_amdgcn_readlane(yb_lo, 63), in_q);
-            ya_lo = max(sxg_wave_shr1(ya_lo, NEG * 2), in_e); ya_hi = max(sxg_wave_shr1(ya_hi, NEG * 2), ta);
-            yb_lo = max(sxg_wave_shr1(yb_lo, NEG * 2), in_q); yb_hi = max(sxg_wave_shr1(yb_hi, NEG * 2), tb);
-        }
-        const int Ein_lo = max(ya_lo + tWe - We, FLOORV);
-        const int Ein_hi = max(ya_hi + tWe + 63 * We, FLOORV);
-        const int Qin_lo = !CVX ? FLOORV : max(yb_lo + tWc - Wc, FLOORV);
-        const int Qin_hi = !CVX ? FLOORV : max(yb_hi + tWc + 63 * Wc, FLOORV);
+        xa = max(sxg_wave_shr1(xa, NEG * 2), in_e);   // max over every strip left of my lo strip, the mailbox's included
+        xb = max(sxg_wave_shr1(xb, NEG * 2), in_q);
+        const int Ein_lo = max(xa + 2 * tWe - We, FLOORV);
+        const int Ein_hi = max(max(xa, ya_lo) + 2 * tWe, FLOORV);
+        const int Qin_lo = !CVX ? FLOORV : max(xb + 2 * tWc - Wc, FLOORV);
+        const int Qin_hi = !CVX ? FLOORV : max(max(xb, yb_lo) + 2 * tWc, FLOORV);
         int E = pk2(Ein_lo, Ein_hi), Q = pk2(Qin_lo, Qin_hi);
 
         // ---- pass 2: final H
@@ -761,15 +766,12 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
                 rowmax = t_[0];
             }
         }
-        // hand my last column to the right neighbour: inside the wave by a lane shift (lane 0's hi strip begins where lane
-        // 63's lo strip ends; the column left of its lo strip came in through the mailbox); lane 63's hi strip is the wave's
-        // right edge -- E, Q after its last column and its H go into the next wave's mailbox of this row
+        // hand my last column to the right neighbour: my hi strip begins where my own lo strip ends, my lo strip where the hi
+        // strip of the lane before me ends (lane 0: what came in through the mailbox) -- a lane shift and one v_alignbit;
+        // lane 63's hi strip is the wave's right edge -- E, Q after its last column and its H go into the next wave's mailbox
+        // of this row
         const int xh = Hc[W - 1];
-        int lh = sxg_wave_shr1(xh, 0);
-        {
-            const int x63 = __builtin_amdgcn_readlane(xh, 63);
-            if (lane == 0) lh = pk2(in_h, pk_lo(x63));
-        }
+        const int lh = (int)__builtin_amdgcn_alignbit((unsigned)xh, (unsigned)sxg_wave_shr1(xh, in_h << 16), 16);
         RP_MARK(3);  // carry combine + pass 2
         if (wv + 1 < NW && !(EXP & 16)) {
             if ((i & (P16_MBOX / 2 - 1)) == 0)   // the slots of the next P16_MBOX / 2 rows: has my reader freed them?
@@ -798,16 +800,15 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
 
         RP_MARK(5);  // hand-over + end-cell bookkeeping
         // ---- outgoing candidates (see p16_pack_row), ring store, band store
-        // band of this row: strips [bs0, bs0 + BS); my wave covers lo strips [128 wv, 128 wv + 64) and the
-        // hi strips 64 further on.  (wave-uniform tests; the lane test is ONE exec mask around all W stores)
+        // band of this row: strips [bs0, bs0 + BS); my wave covers the strips [128 wv, 128 wv + 128), lo and hi strips
+        // alternating: a wave that overlaps the band stores both halves.  (wave-uniform test; the lane tests pick the slot)
         const int bs0 = band_first_strip(hint, W, BS, T);
         const int w0 = wv << 7;
-        const bool band_lo = !(EXP & 1) && (w0 + 63 >= bs0) && (w0 < bs0 + BS);
-        const bool band_hi = !(EXP & 1) && (w0 + 127 >= bs0) && (w0 + 64 < bs0 + BS);
+        const bool band_any = !(EXP & 1) && (w0 + 127 >= bs0) && (w0 < bs0 + BS);
         const bool ring = !(EXP & 2) && (flags & ROW_STORE) != 0;
         const __amdgpu_buffer_rsrc_t rs_ring = p16_rsrc((const void*)((SXG_GLOBAL const char*)g_pool + (size_t)(ring && myslot >= 0 ? myslot : 0) * (size_t)RB), RB);
         const __amdgpu_buffer_rsrc_t rs_plane = p16_rsrc((const void*)(g_tb + (size_t)i * (size_t)(SD * BS)), SD * BS * 4);
-        const bool in_lo = (unsigned)(w0 + tt - bs0) < (unsigned)BS, in_hi = (unsigned)(w0 + 64 + tt - bs0) < (unsigned)BS;
+        const bool in_lo = (unsigned)(w0 + 2 * tt - bs0) < (unsigned)BS, in_hi = (unsigned)(w0 + 2 * tt + 1 - bs0) < (unsigned)BS;
         const unsigned sl_lo = soff & 0xffffu, sl_hi = soff >> 16;   // strip s lives in slot s mod BS of its row
         // (CB = 2) the H left of my strips as the plane row keeps it: strip 0 has no left neighbour -- its own first column,
         // whose step is then 0
@@ -843,7 +844,7 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
                     __builtin_amdgcn_raw_buffer_store_b32((unsigned)p16_row_encode<CVX, SW>(Hc[k], k ? Hc[k ? k - 1 : 0] : lhs, (CF), (CO), DFu, RC), rs_ring, ut8 >> 1, k * T * 4, 0); \
                 __builtin_amdgcn_raw_buffer_store_b32((unsigned)lhs, rs_ring, ut8 >> 1, TW * 4, 0);         \
             }                                                                                               \
-            if (band_lo || band_hi) {                                                                       \
+            if (band_any) {                                                                                 \
                 /* delta codes of my two strips (see P16Delta): both halves of a register at once */       \
                 int code_[W], prev_ = lhs;                                                                  \
                 _Pragma("unroll") for (int k = 0; k < W; ++k) {                                             \
@@ -851,20 +852,16 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
                     prev_ = Hc[k];                                                                          \
                 }                                                                                           \
                 /* dword x of a strip: halfwords 2x, 2x + 1 of (left H, code 0, ..., code W-1) */            \
-                if (band_lo)                                                                                \
-                    plane_store_strip<SD>(rs_plane, in_lo ? sl_lo : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
+                plane_store_strip<SD>(rs_plane, in_lo ? sl_lo : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
                         return __builtin_amdgcn_perm((unsigned)(2 * x < W ? code_[2 * x < W ? 2 * x : 0] : 0), (unsigned)(x ? code_[x ? 2 * x - 1 : 0] : lhs), 0x05040100u); }); \
-                if (band_hi)                                                                                \
-                    plane_store_strip<SD>(rs_plane, in_hi ? sl_hi : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
+                plane_store_strip<SD>(rs_plane, in_hi ? sl_hi : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
                         return __builtin_amdgcn_perm((unsigned)(2 * x < W ? code_[2 * x < W ? 2 * x : 0] : 0), (unsigned)(x ? code_[x ? 2 * x - 1 : 0] : lhs), 0x07060302u); }); \
             }                                                                                               \
         } else {                                                                                            \
-        if (band_lo) {                                                                                      \
+        if (band_any) {                                                                                     \
                 plane_store_strip<W>(rs_plane, in_lo ? sl_lo : P16_SLOT_OOB, BS, [&](const int k) -> unsigned { \
                     const u32x2 w = p16_pack_row<CVX, SW>(Hc[k], CF, CO);                                   \
                     return __builtin_amdgcn_perm(w.y, w.x, 0x05040100u); });                                \
-        }                                                                                                   \
-        if (band_hi) {                                                                                      \
                 plane_store_strip<W>(rs_plane, in_hi ? sl_hi : P16_SLOT_OOB, BS, [&](const int k) -> unsigned { \
                     const u32x2 w = p16_pack_row<CVX, SW>(Hc[k], CF, CO);                                   \
                     return __builtin_amdgcn_perm(w.y, w.x, 0x07060302u); });                                \
