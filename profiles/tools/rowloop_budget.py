@@ -22,18 +22,19 @@ subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-
 lines = open(out).read().split("\n")
 start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and KSUB in l and ":" in l)
 end = next(i for i in range(start + 1, len(lines)) if lines[i].startswith(".Lfunc_end"))
-blocks, cur = [], {"name": "entry", "ins": [], "depth": 0}
+blocks, cur = [], {"name": "entry", "ins": [], "depth": 0, "hdrs": set()}
 blocks.append(cur)
 for l in lines[start + 1:end]:
     m = re.match(r"^(\.LBB\d+_\d+):", l)
     if m:
-        cur = {"name": m.group(1), "ins": [], "depth": 0}
+        cur = {"name": m.group(1), "ins": [], "depth": 0, "hdrs": set(re.findall(r"(?:Header=|Parent Loop )(BB\d+_\d+)", l))}
         blocks.append(cur)
         continue
     t = l.strip()
     m = re.search(r"Depth=(\d+)", t)
     if t.startswith(";") and m:
         cur["depth"] = max(cur["depth"], int(m.group(1)))
+        cur["hdrs"] |= set(re.findall(r"(?:Header=|Parent Loop )(BB\d+_\d+)", t))
         continue
     if t and not t.startswith(";") and not t.startswith("."):
         cur["ins"].append(t.split(";")[0].strip())
@@ -67,6 +68,9 @@ tot = None
 # the row loop: from the first block LLVM marks as inside a loop (the header) to the last block that branches back to it
 hdr = next(i for i, b in enumerate(blocks) if b["depth"] >= 1)
 back = max(i for i, b in enumerate(blocks) if any(x.startswith(("s_cbranch", "s_branch")) and x.split()[-1] == blocks[hdr]["name"] for x in b["ins"]))
+# (round 11: the compiler may lay blocks of the loop out BEHIND the block with the back edge -- the on-chip row copy of the
+#  W = 11 class, for one: everything up to the last block LLVM marks as inside the header's loop is listed)
+back = max([back] + [i for i, b in enumerate(blocks) if blocks[hdr]["name"][2:] in b["hdrs"]])
 print("row loop: %s .. %s" % (blocks[hdr]["name"], blocks[back]["name"]))
 print("%-12s %2s %5s %5s %4s %4s %4s %5s %4s  %s" % ("block", "d", "valu", "salu", "lds", "vmem", "nop", "lane", "mov", "ends with"))
 for b in blocks[hdr:back + 1]:

@@ -93,7 +93,7 @@ __device__ __forceinline__ void p16_unpack_row(u32x2 w, int& h, int& of, int& oo
     oo = BIASED ? (int)((unsigned)h - (unsigned)dq) : pk_sub(h, dq);
 }
 
-// 2-byte plane cells (CB = 2): P16Delta, poa_rowcode.h
+// 2-byte plane cells (CB = 2): row codes (P16RowCode; the banded sweep: delta codes, P16Delta), poa_rowcode.h
 // dwords of one strip of a row: W + 1 halfwords
 __host__ __device__ constexpr int p16_slot_dwords(int W, int CB) { return CB == 2 ? (W + 2) / 2 : W; }
 
@@ -234,7 +234,7 @@ __device__ __forceinline__ int band_first_strip(const int hint_col, const int W,
 // (the kernel runs it in front of the real one), so that the difference between two builds prices a part of the row:
 // 1 = no band stores, 2 = no ring stores, 4 = no end-cell bookkeeping, 8 = no carry scans, 16 = no mailbox exchange,
 // 32 = every row takes the register-predecessor path (no fetch, no fold), 64 = no pass 2, 128 = no pass 1.
-// CB: bytes per plane cell (2: delta codes, see P16Delta; 4: H | H - oF | H - oO).
+// CB: bytes per plane cell (2: the stored rows' code, see P16RowCode; 4: H | H - oF | H - oO).
 // End cell of a LOCAL alignment (round 5): every lane keeps, per strip, ONE 32-bit key -- the strip's greatest H so far in the
 // upper half, 0xffff minus the row that first reached it in the lower -- updated with a max per row (5 instructions; rounds 2-4
 // compared, voted and searched the strip's columns in every row that improved any lane, i.e. nearly every row of the waves the
@@ -291,18 +291,13 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     const int We = W * e, Wc = W * c;
     const int BS = __builtin_amdgcn_readfirstlane(B.band_strips);
     constexpr int SD = p16_slot_dwords(W, CB);   // dwords of one strip in a plane row
-    // (CB = 2) the field widths of the plane's delta code
+    // (CB = 2) the field widths of the 2-byte cell code
     Scoring SD_ = S;
     if (DS) { SD_.m = P16_DEF_M; SD_.n = P16_DEF_N; SD_.g = P16_DEF_G; SD_.e = P16_DEF_E; SD_.q = P16_DEF_Q; SD_.c = P16_DEF_C; SD_.convex = 1; }
     const P16Delta DF = p16_delta_of(SD_);
-    // ... and what reading a row back out of the plane needs (full-width planes only, see ring_plane below)
     const int dbH_ = __builtin_amdgcn_readfirstlane(DF.bH), dbF_ = __builtin_amdgcn_readfirstlane(DF.bF);
-    const int D_SH1 = pk2(dbH_, dbH_), D_SH2 = pk2(dbH_ + dbF_, dbH_ + dbF_);
-    const int D_MH = pk2((1 << dbH_) - 1, (1 << dbH_) - 1), D_MF = pk2((1 << dbF_) - 1, (1 << dbF_) - 1);
-    const int d_cst_ = g + ((-e) << dbH_) + ((CVX ? -c : 0) << (dbH_ + dbF_));
-    const int D_CST = pk2(d_cst_, d_cst_);
-    const int D_EA = pk2(-e, -e), D_CA = pk2(-c, -c);
-    // (CB = 2) stored rows: the row code (poa_rowcode.h); the field widths are the plane's
+    // (CB = 2) the ONE code of a cell (round 11): the row code (P16RowCode, poa_rowcode.h) is what the ring, the on-chip row
+    // copies and the plane hold
     P16Delta DFu = DF;
     DFu.bH = dbH_; DFu.bF = dbF_; DFu.bO = __builtin_amdgcn_readfirstlane(DF.bO);
     DFu.g = g; DFu.eabs = -e; DFu.cabs = -c;
@@ -555,8 +550,9 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
     } while (0)
 
 // ... or, with ring_plane, the row's strips out of its plane row: H of the column left of the strips, then per column the
-// code's three fields; HS_/FS_/OS_[k] receive the row's H and outgoing candidates (FO_ = false: H only, for a sibling)
-#define P16_FETCH_PLANE(p_, FO_, HS_, FS_, OS_, hl_)                                                        \
+// row code of my two strips, one v_perm picking the halves out of the two strips' dwords; HS_/FS_/OS_[k] receive the row's H
+// and outgoing candidates -- the same p16_row_decode as a row out of the ring
+#define P16_FETCH_PLANE(p_, HS_, FS_, OS_, hl_)                                                             \
     do {                                                                                                    \
         const __amdgpu_buffer_rsrc_t rsp_ = p16_rsrc((const void*)(g_tb + (size_t)(p_) * (size_t)(SD * BS)), SD * BS * 4); \
         unsigned dl_[SD], dh_[SD];                                                                          \
@@ -567,13 +563,9 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
         int run_ = (int)__builtin_amdgcn_perm(dh_[0], dl_[0], 0x05040100u);                                 \
         hl_ = t == 0 ? (int)(((unsigned)run_ & 0xffff0000u) | ((unsigned)FLOORV & 0xffffu)) : run_;         \
         _Pragma("unroll") for (int k = 0; k < W; ++k) {                                                     \
-            const int cn_ = pk_sub((int)__builtin_amdgcn_perm(dh_[(k + 1) >> 1], dl_[(k + 1) >> 1], ((k + 1) & 1) ? 0x07060302u : 0x05040100u), D_CST); \
-            run_ = pk_add(pk_add(run_, cn_ & D_MH), G2);                                                    \
+            const unsigned cn_ = __builtin_amdgcn_perm(dh_[(k + 1) >> 1], dl_[(k + 1) >> 1], ((k + 1) & 1) ? 0x07060302u : 0x05040100u); \
+            p16_row_decode<CVX, SW>(cn_, run_, FS_[k], OS_[k], RC);                                         \
             HS_[k] = run_;                                                                                  \
-            if (FO_) {                                                                                      \
-                FS_[FO_ ? k : 0] = pk_sub(pk_sub(run_, pk_lshr(cn_, D_SH1) & D_MF), D_EA);                  \
-                if (CVX) OS_[FO_ ? k : 0] = pk_sub(pk_sub(run_, pk_lshr(cn_, D_SH2)), D_CA);                \
-            }                                                                                               \
         }                                                                                                   \
     } while (0)
 
@@ -596,7 +588,7 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
             const bool regbase = (flags & ROW_REGPRED) != 0;
             if (!regbase) {
                 int hl;
-                if (ring_plane && s0 >= 0 && p0 != 0) P16_FETCH_PLANE(p0, true, Hp, Fp, Op, hl);
+                if (ring_plane && s0 >= 0 && p0 != 0) P16_FETCH_PLANE(p0, Hp, Fp, Op, hl);
                 else if constexpr (CB == 2) {
                     unsigned wr[W];
                     P16_FETCH(p0, s0, wr, hl);
@@ -620,7 +612,7 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
         int hl;                                                                                             \
         if constexpr (CB == 2) {                                                                            \
             int hs_[W], fs_[W], os_[W];                                                                     \
-            if (ring_plane && (sl_) >= 0 && (p_) != 0) P16_FETCH_PLANE(p_, true, hs_, fs_, os_, hl);        \
+            if (ring_plane && (sl_) >= 0 && (p_) != 0) P16_FETCH_PLANE(p_, hs_, fs_, os_, hl);              \
             else { unsigned wr_[W]; P16_FETCH(p_, sl_, wr_, hl); P16_DECODE(wr_, hl, hs_, fs_, os_); }      \
             _Pragma("unroll") for (int k = 0; k < W; ++k) {                                                 \
                 Fp[k] = pk_max(Fp[k], fs_[k]);                                                              \
@@ -833,29 +825,29 @@ __device__ SXG_P16_INLINE DpResult dp_fill_p16(const Scoring S, const RowsView R
         }                                                                                                   \
         if constexpr (CB == 2) {                                                                            \
             const bool copy_lds = ring && myslot <= -2, copy_hbm = ring && myslot > -2 && !ring_plane;      \
-            /* a stored row: the row codes (P16RowCode) of my two strips, and the left word */              \
-            if (copy_lds) {                                                                                 \
-                P16_LDS_ROW(la_, lf_, -2 - myslot);                                                         \
+            /* ONE code per cell (P16RowCode), both halves of a register at once, computed once per row: a stored row \
+               and the band cells of the plane are the same words (wave-uniform tests: no lane sits anything out) */ \
+            if (copy_lds || copy_hbm || band_any) {                                                         \
+                int code_[W];                                                                               \
                 _Pragma("unroll") for (int k = 0; k < W; ++k)                                               \
-                    la_[k * 64] = (unsigned)p16_row_encode<CVX, SW>(Hc[k], k ? Hc[k ? k - 1 : 0] : lhs, (CF), (CO), DFu, RC); \
-                *lf_ = (unsigned)lhs;                                                                       \
-            } else if (copy_hbm) {                                                                          \
-                _Pragma("unroll") for (int k = 0; k < W; ++k)                                               \
-                    __builtin_amdgcn_raw_buffer_store_b32((unsigned)p16_row_encode<CVX, SW>(Hc[k], k ? Hc[k ? k - 1 : 0] : lhs, (CF), (CO), DFu, RC), rs_ring, ut8 >> 1, k * T * 4, 0); \
-                __builtin_amdgcn_raw_buffer_store_b32((unsigned)lhs, rs_ring, ut8 >> 1, TW * 4, 0);         \
-            }                                                                                               \
-            if (band_any) {                                                                                 \
-                /* delta codes of my two strips (see P16Delta): both halves of a register at once */       \
-                int code_[W], prev_ = lhs;                                                                  \
-                _Pragma("unroll") for (int k = 0; k < W; ++k) {                                             \
-                    code_[k] = p16_plane_code<CVX, SW>(Hc[k], prev_, (CF), (CO), DFu);                      \
-                    prev_ = Hc[k];                                                                          \
+                    code_[k] = p16_row_encode<CVX, SW>(Hc[k], k ? Hc[k ? k - 1 : 0] : lhs, (CF), (CO), DFu, RC); \
+                /* a stored row: the codes of my two strips as they stand, and the left word */             \
+                if (copy_lds) {                                                                             \
+                    P16_LDS_ROW(la_, lf_, -2 - myslot);                                                     \
+                    _Pragma("unroll") for (int k = 0; k < W; ++k) la_[k * 64] = (unsigned)code_[k];         \
+                    *lf_ = (unsigned)lhs;                                                                   \
+                } else if (copy_hbm) {                                                                      \
+                    _Pragma("unroll") for (int k = 0; k < W; ++k)                                           \
+                        __builtin_amdgcn_raw_buffer_store_b32((unsigned)code_[k], rs_ring, ut8 >> 1, k * T * 4, 0); \
+                    __builtin_amdgcn_raw_buffer_store_b32((unsigned)lhs, rs_ring, ut8 >> 1, TW * 4, 0);     \
                 }                                                                                           \
-                /* dword x of a strip: halfwords 2x, 2x + 1 of (left H, code 0, ..., code W-1) */            \
-                plane_store_strip<SD>(rs_plane, in_lo ? sl_lo : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
-                        return __builtin_amdgcn_perm((unsigned)(2 * x < W ? code_[2 * x < W ? 2 * x : 0] : 0), (unsigned)(x ? code_[x ? 2 * x - 1 : 0] : lhs), 0x05040100u); }); \
-                plane_store_strip<SD>(rs_plane, in_hi ? sl_hi : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
-                        return __builtin_amdgcn_perm((unsigned)(2 * x < W ? code_[2 * x < W ? 2 * x : 0] : 0), (unsigned)(x ? code_[x ? 2 * x - 1 : 0] : lhs), 0x07060302u); }); \
+                if (band_any) {                                                                             \
+                    /* dword x of a strip: halfwords 2x, 2x + 1 of (left H, code 0, ..., code W-1) */        \
+                    plane_store_strip<SD>(rs_plane, in_lo ? sl_lo : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
+                            return __builtin_amdgcn_perm((unsigned)(2 * x < W ? code_[2 * x < W ? 2 * x : 0] : 0), (unsigned)(x ? code_[x ? 2 * x - 1 : 0] : lhs), 0x05040100u); }); \
+                    plane_store_strip<SD>(rs_plane, in_hi ? sl_hi : P16_SLOT_OOB, BS, [&](const int x) -> unsigned { \
+                            return __builtin_amdgcn_perm((unsigned)(2 * x < W ? code_[2 * x < W ? 2 * x : 0] : 0), (unsigned)(x ? code_[x ? 2 * x - 1 : 0] : lhs), 0x07060302u); }); \
+                }                                                                                           \
             }                                                                                               \
         } else {                                                                                            \
         if (band_any) {                                                                                     \
@@ -963,8 +955,9 @@ enum : int { TBM_FLAG = 208, TBM_ROW = 209, TBM_DELTA = 210, TBM_RANGE = 211 /* 
 
 // BANDED (poa_band16.hip.h): a row keeps exactly the strips of its band, max(0, hint - w) / W .. (hint + w) / W, and a
 // cell outside the band does not exist (it reads as -inf and is never a miss).
-// CB = 2: the plane holds delta codes (P16Delta); the helpers below rebuild the cells the walk asks for -- H by summing a
-// strip's steps from its left end -- in the round-4 word format (H | H - oF | H - oO), so the walk itself is the same code.
+// CB = 2: the plane holds 2-byte codes (row codes; BANDED: delta codes -- poa_rowcode.h); the helpers below rebuild the cells
+// the walk asks for -- H by summing a strip's steps from its left end -- in the round-4 word format (H | H - oF | H - oO), so the
+// walk itself is the same code.
 // j < 0 on entry: the sweep of a local alignment names the STRIP of the end cell, -(strip + 1); the column is the first
 // of that strip's cells in row i that holds the best score.
 // STRICT: the caller admitted the alignment under the strict range rule (every cell above P16_NWFLOOR: nothing is ever clamped,
@@ -1012,19 +1005,17 @@ __device__ __noinline__ int traceback_p16(const RowsView R, const DpBuffers B, c
     // (CB = 2) fields of a cell's code
     const P16Delta DF = p16_delta_of(S_);
     const int dbH = __builtin_amdgcn_readfirstlane(DF.bH), dbF = __builtin_amdgcn_readfirstlane(DF.bF);
-    const unsigned dmH = (1u << dbH) - 1u, dmF = (1u << dbF) - 1u;
-    const int dG = __builtin_amdgcn_readfirstlane(DF.g), dE = __builtin_amdgcn_readfirstlane(DF.eabs), dC = __builtin_amdgcn_readfirstlane(DF.cabs);
-    // The sweep adds the raw step and distances into the code; taking their least values off first (mod 2^16) leaves three
-    // non-negative fields side by side.
-    const unsigned dCst = (unsigned)(dG + (dE << dbH) + ((CVX ? dC : 0) << (dbH + dbF))) & 0xffffu;
-    auto d_norm = [&](const unsigned raw16) -> unsigned { return (raw16 - dCst) & 0xffffu; };
-    // normalised code -> step of H; the cell word given H
-    auto d_step = [&](const unsigned code) -> int { return (int)(code & dmH) + dG; };
-    auto d_word = [&](const int h, const unsigned code) -> uint32_t {
-        return ((uint32_t)h & 0xffffu) | ((((code >> dbH) & dmF) + (unsigned)dE) << 16) | (((code >> (dbH + dbF)) + (unsigned)(CVX ? dC : 0)) << 24);
+    // Which code the plane holds: the full-matrix sweep writes row codes (round 11: the ONE code of its stored rows and its
+    // plane), the banded sweep its delta codes.  Both decode through poa_rowcode.h: p16_code_step (one column: the step of H and
+    // the two distances) and p16_strip_decode (column k of a strip, summing the steps from its left end).
+    constexpr bool DELTA = BANDED;
+    P16Delta DT;
+    DT.bH = dbH; DT.bF = dbF; DT.bO = __builtin_amdgcn_readfirstlane(DF.bO);
+    DT.g = __builtin_amdgcn_readfirstlane(DF.g); DT.eabs = __builtin_amdgcn_readfirstlane(DF.eabs); DT.cabs = __builtin_amdgcn_readfirstlane(DF.cabs);
+    // the cell word the walk reads, given H and the distances H - oF, H - oO
+    auto d_word = [&](const int h, const int df, const int dq) -> uint32_t {
+        return ((uint32_t)h & 0xffffu) | ((uint32_t)df << 16) | ((uint32_t)dq << 24);
     };
-    // halfword hw (0 = the H left of the strip, 1 + k = code of column k) of a strip whose dwords are d[0..SD)
-    auto d_half = [&](const unsigned (&d)[SD], const int hw) -> unsigned { return (hw & 1) ? d[hw >> 1] >> 16 : d[hw >> 1] & 0xffffu; };
     // outputs and letters through global pointers: a FLAT store also counts on lgkmcnt, and the walk
     // waits on lgkmcnt for its LDS reads every step -- i.e. it would wait for the previous step's store to
     // reach HBM
@@ -1080,14 +1071,11 @@ __device__ __noinline__ int traceback_p16(const RowsView R, const DpBuffers B, c
         if constexpr (CB == 2) {
             // lanes 0 .. SD-1 fetch the strip's dwords; the steps up to column k are summed on the scalar unit
             const unsigned dw = lane < SD ? g_plane[(size_t)p * (size_t)(SD * BS) + (size_t)plane_cell_in_row(SD, BS, s % BS, min(lane, SD - 1))] : 0u;
-            int h = (int)(short)(TBU(__builtin_amdgcn_readlane((int)dw, 0)) & 0xffffu);
-            unsigned cd = 0;
-            for (int t2 = 0; t2 <= k; ++t2) {
-                const unsigned d = TBU(__builtin_amdgcn_readlane((int)dw, (t2 + 1) >> 1));
-                cd = d_norm(((t2 + 1) & 1) ? d >> 16 : d & 0xffffu);
-                h += d_step(cd);
-            }
-            return d_word(h, cd);
+            int h, of, oo;
+            p16_strip_decode<CVX, DELTA>([&](const int hw) -> unsigned {
+                    const unsigned d = TBU(__builtin_amdgcn_readlane((int)dw, hw >> 1));
+                    return (hw & 1) ? d >> 16 : d & 0xffffu; }, k, h, of, oo, DT);
+            return d_word(h, h - of, h - oo);
         }
         return TBU(g_plane[plane_cell<W>((size_t)p, BS, s % BS, k)]);
     };
@@ -1161,14 +1149,13 @@ __device__ __noinline__ int traceback_p16(const RowsView R, const DpBuffers B, c
                 for (int x2 = 0; x2 < TBW_COLS; ++x2) v[x2] = 0u;
 #pragma unroll
                 for (int si = 0; si < NSW; ++si) {
-                    int h = (int)(short)(R_.cells[si * SD] & 0xffffu);
+                    int h = (int)(short)(R_.cells[si * SD] & 0xffffu), df = 0, dq = 0;
                     const int xb = (s0w + si) * W - c0;   // window place of the strip's first column
 #pragma unroll
                     for (int k = 0; k < W; ++k) {
                         const unsigned dwk = R_.cells[si * SD + ((1 + k) >> 1)];
-                        const unsigned cd = d_norm(((1 + k) & 1) ? dwk >> 16 : dwk & 0xffffu);
-                        h += d_step(cd);
-                        if ((unsigned)(xb + k) < (unsigned)TBW_COLS && s0w + si <= (BANDED ? last_strip : 2 * T - 1)) en[xb + k] = d_word(h, cd);
+                        p16_code_step<CVX, DELTA>(((1 + k) & 1) ? dwk >> 16 : dwk & 0xffffu, h, df, dq, DT);
+                        if ((unsigned)(xb + k) < (unsigned)TBW_COLS && s0w + si <= (BANDED ? last_strip : 2 * T - 1)) en[xb + k] = d_word(h, df, dq);
                     }
                 }
             } else {
@@ -1259,10 +1246,10 @@ __device__ __noinline__ int traceback_p16(const RowsView R, const DpBuffers B, c
             int kf = -1;
             if constexpr (CB == 2) {
                 const unsigned dw = lane < SD ? g_plane[(size_t)i * (size_t)(SD * BS) + (size_t)plane_cell_in_row(SD, BS, s % BS, min(lane, SD - 1))] : 0u;
-                int h = (int)(short)(TBU(__builtin_amdgcn_readlane((int)dw, 0)) & 0xffffu);
+                int h = (int)(short)(TBU(__builtin_amdgcn_readlane((int)dw, 0)) & 0xffffu), df = 0, dq = 0;
                 for (int t2 = 0; t2 < W && kf < 0; ++t2) {
                     const unsigned d = TBU(__builtin_amdgcn_readlane((int)dw, (t2 + 1) >> 1));
-                    h += d_step(d_norm(((t2 + 1) & 1) ? d >> 16 : d & 0xffffu));
+                    p16_code_step<CVX, DELTA>(((t2 + 1) & 1) ? d >> 16 : d & 0xffffu, h, df, dq, DT);
                     if (h == hv) kf = t2;
                 }
             } else {
@@ -1434,9 +1421,8 @@ __device__ __noinline__ int traceback_p16(const RowsView R, const DpBuffers B, c
                             if (act && inb) {
                                 unsigned raw[SD];
                                 plane_load_slot<SD>(g_plane + (size_t)i * (size_t)(SD * BS), BS, s % BS, raw);
-                                int h = (int)(short)(raw[0] & 0xffffu);
-#pragma unroll
-                                for (int t2 = 0; t2 < W; ++t2) if (t2 <= k) h += d_step(d_norm(d_half(raw, 1 + t2)));
+                                int h, of, oo;
+                                p16_strip_decode<CVX, DELTA, W>([&](const int hw) -> unsigned { return p16_strip_half(raw, hw); }, k, h, of, oo, DT);
                                 hval = h;
                             }
                         } else

@@ -1,6 +1,10 @@
-// poa_rowcode.h -- the 16-bit cell codes of the packed sweep's 2-byte classes (CB = 2): the traceback plane's delta code
-// (P16Delta) and the stored-row code of the row ring and its on-chip copies.  Host-compilable (tests/test_rowcode.py
-// round-trips every representable cell of a score set on the CPU); the device forms are the same functions.
+// poa_rowcode.h -- the 16-bit cell codes of the packed sweep's 2-byte classes (CB = 2).  Since round 11 the full-matrix sweep
+// has ONE code: the stored-row code (P16RowCode) is what the row ring, its on-chip copies AND the traceback plane hold, so a
+// row that is both stored and inside its band is encoded once.  The delta code (P16Delta / p16_plane_code, round 5) remains
+// the plane format of the banded sweep (poa_band16.hip.h) and the value the unbiased (global) row code is derived from; both
+// codes share the field widths of P16Delta.  p16_code_step / p16_strip_decode are what every reader of a plane strip -- the
+// traceback, the sweep's read-back of stored rows -- decodes with.  Host-compilable (tests/test_rowcode.py and
+// tests/test_planecode.py round-trip every representable cell of a score set on the CPU); the device forms are the same functions.
 #pragma once
 #include "poa_types.h"
 
@@ -117,6 +121,48 @@ SXG_HD void p16_row_decode(const unsigned w, int& h, int& of, int& oo, const P16
         const int o = (int)(w >> R.sho) & R.mo;
         oo = BIASED ? (int)((unsigned)h + (unsigned)o - (unsigned)R.ko) : p16w_sub(p16w_add(h, o), R.ko);
     }
+}
+
+// ---- a strip of a plane row, one cell at a time (the traceback; round 11) ------------------------------------------
+// A strip is W + 1 halfwords: the H left of the strip (strip 0, and every strip of the banded sweep: its own first H, whose
+// step is then 0), then the W codes -- row codes in the full-matrix sweep's plane, delta codes (DELTA) in the banded sweep's.
+// These are the scalar forms, one 16-bit code at a time in ordinary int arithmetic; H comes back sign-extended, biased as stored.
+// halfword hw of a strip whose dwords are d[]
+SXG_HD unsigned p16_strip_half(const unsigned* const d, const int hw) { return (hw & 1) ? d[hw >> 1] >> 16 : d[hw >> 1] & 0xffffu; }
+// One column: h enters as the H of the column to the left and leaves as this column's; df, dq receive the distances H - oF,
+// H - oO to its outgoing candidates (dq = 0 without the second gap piece).
+template <bool CVX, bool DELTA = false>
+SXG_HD void p16_code_step(unsigned code, int& h, int& df, int& dq, const P16Delta& D) {
+    const unsigned mH = (1u << D.bH) - 1u, mF = (1u << D.bF) - 1u, mO = (1u << D.bO) - 1u;
+    if (DELTA) {
+        // the sweep adds the raw step and distances into the code; taking their least values off first (mod 2^16) leaves
+        // three non-negative fields side by side
+        code = (code - (unsigned)(D.g + (D.eabs << D.bH) + ((CVX ? D.cabs : 0) << (D.bH + D.bF)))) & 0xffffu;
+        h += (int)(code & mH) + D.g;
+        df = (int)((code >> D.bH) & mF) + D.eabs;
+        dq = (int)(code >> (D.bH + D.bF)) + (CVX ? D.cabs : 0);
+    } else {
+        code &= 0xffffu;
+        h += (int)(code & mH) + D.g;
+        df = D.eabs + (int)(mF - ((code >> D.bH) & mF));
+        dq = CVX ? D.cabs + (int)(mO - ((code >> (D.bH + D.bF)) & mO)) : 0;
+    }
+}
+// Column k of a strip (0 <= k < W): sums the steps from the strip's left end; `half(hw)` returns halfword hw of the strip.
+// W > 0: unrolled over a strip of W columns (strips held in registers); W = 0: a plain loop up to k.
+template <bool CVX, bool DELTA = false, int W = 0, class HALF>
+SXG_HD void p16_strip_decode(HALF half, const int k, int& h, int& of, int& oo, const P16Delta& D) {
+    int df = 0, dq = 0;
+    h = (int)(short)(half(0) & 0xffffu);
+    if (W > 0) {
+#if defined(__clang__)
+#pragma unroll
+#endif
+        for (int t = 0; t < W; ++t) if (t <= k) p16_code_step<CVX, DELTA>(half(1 + t), h, df, dq, D);
+    } else {
+        for (int t = 0; t <= k; ++t) p16_code_step<CVX, DELTA>(half(1 + t), h, df, dq, D);
+    }
+    of = h - df; oo = h - dq;
 }
 
 }  // namespace sxg

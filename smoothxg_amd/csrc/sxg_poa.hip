@@ -160,8 +160,8 @@ static int p16_lds_rows(const int T, const int W, const int CB) {
     return std::max(0, std::min(8, rows));
 }
 
-// Plane cell format of the packed sweep for a score set: 2-byte delta codes when the three fields fit 16 bits (poa_dp16.hip.h,
-// P16Delta), the 4-byte cells of rounds 2-4 otherwise.  SXG_POA_CELL_BYTES=4 forces the latter (A/B runs, tests).
+// Plane cell format of the packed sweep for a score set: 2-byte codes when the three fields fit 16 bits (poa_rowcode.h:
+// the stored rows' code, field widths of P16Delta), the 4-byte cells of rounds 2-4 otherwise.  SXG_POA_CELL_BYTES=4 forces the latter (A/B runs, tests).
 static int plane_cell_bytes(const Scoring& S) {
     if (const char* e = getenv("SXG_POA_CELL_BYTES")) if (atoi(e) == 4) return 4;
     return p16_delta_fits(S) ? 2 : 4;
