@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-/* 5 (addition, no number change): sxg_poa_kmer_jaccard_batch, sxg_poa_split_mash_batch and struct sxg_poa_split_mash -- the
+/* 5 (addition, no number change): sxg_poa_path_sgd_order and struct sxg_poa_sgd_in -- the path-guided SGD node order of prep
+ *    (src/prep.cpp:11-163) on the device, decree Y.
+ * 5 (addition, no number change): sxg_poa_kmer_jaccard_batch, sxg_poa_split_mash_batch and struct sxg_poa_split_mash -- the
  *    mash-based branch of the identity split (src/breaks.cpp:388-471) on the device, decrees M1-M5.
  * 5 (addition, no number change: no struct or existing entry point changed): sxg_poa_pair_identity_batch, sxg_poa_split_batch,
  *    sxg_poa_split_free and their two structs -- the identity split of break_blocks (src/breaks.cpp:335-586) on the device.
@@ -411,6 +413,54 @@ typedef struct sxg_poa_split_mash {
 /* sxg_poa_split_batch's contract plus M1-M5; n_mash: [n_blocks] set comparisons run, or NULL; out is freed by sxg_poa_split_free */
 int sxg_poa_split_mash_batch(sxg_poa_handle *h, const sxg_poa_split_in *in, const sxg_poa_split_mash *mash,
                              sxg_poa_split_out *out, int64_t *n_mash);
+
+/* The node order of prep (src/prep.cpp:11-163: odgi's path_linear_sgd_order, called from src/main.cpp:423-433 before every
+ * iteration unless -n), decree Y of DESIGN.md section 9.  odgi is absent from the snapshot and its hogwild updates are not
+ * reproducible, so the order is fixed by decree, bit for bit:
+ *   Y1  state: X[n], an int64 in units of 2^-20 bp, starts as (sum of len of the nodes before n) << 20.  SXG_E_INVALID if the
+ *       total length >= 2^40, the steps S >= 2^32 or the nodes N >= 2^31.  Orientation plays no part.
+ *   Y2  the schedule is the caller's: eta[iter_max] (double) and cooling_start.  The host library computes what prep.cpp asks
+ *       for (sxg_graph_prep: eta_max = (steps of the longest path)^2, eps = 0.01, lambda = ln(eta_max / eps) / (iter_max - 1),
+ *       eta[t] = eta_max * exp(-lambda t), iter_max = 100, cooling_start = iter_max / 2, terms_per_iter = (uint64)(term_updates
+ *       * S)); the device never calls exp.
+ *   Y3  counter-based random numbers.  mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *       x = (x ^ x >> 27) * 0x94D049BB133111EB; return x ^ x >> 31 (mod 2^64).  Term k of iteration it:
+ *       base = mix(seed ^ (it << 40) ^ k), r1 = mix(base), r2 = mix(r1), r3 = mix(r2).
+ *   Y4  the pair.  a = r1 mod S is a flat step; p its path (the last path that starts at or before a), n its step count, ia the
+ *       index of a in it.  If (r2 & 1) or it >= cooling_start the second step is drawn log-uniformly by octave (the integer
+ *       stand-in for odgi's Zipf with theta 0.99): nb = max(1, bitlength(maxsteps - 1)) with maxsteps the steps of the longest
+ *       path, bits = (r2 >> 1) mod nb, j = (1 << bits) + ((r2 >> 8) & ((1 << bits) - 1)), ib = ia + j if bit 7 of r2 is set,
+ *       else ia - j; outside [0, n) the other direction is taken, then clamped to [0, n - 1].  Otherwise ib = r3 mod n.
+ *       Node ends: pa = step_pos[a] + len[node of a] if bit 62 of r3 is set, else step_pos[a]; pb likewise for b with bit 63;
+ *       d = |pa - pb|.  The term is skipped if d == 0 or the two nodes are equal.
+ *   Y5  the update for nodes i (of a) and j (of b), in IEEE double, every operation rounded once (no contraction, no fast-math):
+ *       dx = (double)(X[i] - X[j]) / 2^20, mag = |dx|, sgn = the sign of dx, or when dx == 0: -1 if i < j, else +1;
+ *       mu = min(eta[it] / d, 1); delta = mu * (mag - d) / 2; q = llrint(delta * sgn * 2^20), half to even;
+ *       D[i] -= q, D[j] += q.
+ *   Y6  the terms of an iteration run in batches of B = max(1, N div 8) consecutive k (the last one partial); every term of a
+ *       batch reads the X of the batch's start; the q are summed into D with 64-bit INTEGER atomic adds (integer sums do not
+ *       depend on the order of arrival: no float atomics); at the batch's end X += D, D = 0.
+ *   Y7  the new order is the nodes sorted by (X, old rank).
+ * Two paths with the same results: with 16 * N bytes of dynamic LDS (N <= SXG_POA_SGD_LDS_NODES) one workgroup keeps X and D on
+ * chip for the whole sort -- batches separated by __syncthreads, ONE launch, which therefore lasts as long as the sort: mode 0
+ * chooses it only when iter_max * terms_per_iter <= SXG_POA_SGD_LDS_TERMS (seconds), and falls back to the other path if the
+ * runtime refuses the dynamic LDS; mode 1 asks for it whatever the term count --; otherwise one launch of the term kernel (one
+ * thread per term) and one of the apply kernel per batch, on the handle's stream.  No cooperative launch, no grid-wide wait,
+ * no captured graph.  The scratch comes out of the handle's memory budget; the call runs inside a ROCTx range and fills
+ * kernel_ms, n_slots / dp_launches (the number of launches) and device_bytes of sxg_poa_stats.  Y7's sort runs on the host.
+ * Not restated: odgi's groom pass and its final topological_order pass. */
+#define SXG_POA_SGD_LDS_NODES 8192
+#define SXG_POA_SGD_LDS_TERMS (1ull << 30)
+typedef struct sxg_poa_sgd_in {
+    int64_t n_nodes; const int32_t *node_len;      /* nodes in rank order */
+    int64_t n_paths; const int64_t *path_off;      /* [n_paths+1] flat steps of every path */
+    const int32_t *step_node; const int64_t *step_pos; /* [path_off[n_paths]] node rank; bp offset of the step in its path */
+    int32_t iter_max, cooling_start; const double *eta; /* [iter_max] */
+    uint64_t terms_per_iter, seed;
+    int32_t mode;   /* 0 = choose, 1 = LDS path (SXG_E_INVALID if it does not fit), 2 = global path */
+} sxg_poa_sgd_in;
+/* order: [n_nodes] old ranks in the new order; x: [n_nodes] the final X by old rank, or NULL. */
+int sxg_poa_path_sgd_order(sxg_poa_handle *h, const sxg_poa_sgd_in *in, int32_t *order, int64_t *x);
 
 int sxg_poa_get_stats(sxg_poa_handle *h, sxg_poa_stats *out);
 /* Cap on device memory the handle may use for scratch arenas (bytes; 0 = default 3/4 of free). */

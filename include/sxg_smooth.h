@@ -233,6 +233,40 @@ void sxg_merge_default_params(sxg_merge_params *mp);
 int sxg_smooth_maf_gfa(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p, const sxg_merge_params *mp,
                        sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, char **out_gfa, char **out_maf, int64_t *n_flipped);
 
+/* prep (src/prep.cpp:11-163, called from src/main.cpp:423-433 before every iteration unless -n): the graph is sorted by
+ * path-guided SGD and chopped to nodes of at most max_node_length bases, so that block discovery -- a sweep over the nodes in
+ * rank order -- meets the nodes in the order the paths walk them (an addition to ABI 2, no existing struct changed).  odgi is
+ * absent from the snapshot: the sort is decree Y of include/sxg_poa.h, the chop decree C of DESIGN.md section 9.  This library
+ * cannot sort by itself, as it cannot align: the order comes from a sort provider with exactly sxg_poa_path_sgd_order's
+ * contract (ctx is its handle), called once, on the calling thread.
+ *   sxg_graph_prep flattens the graph (nodes in rank order, every path as flat steps with their bp offsets), computes the
+ *   schedule Y2 -- eta_max = (steps of the longest path)^2 (1 without paths), lambda = ln(eta_max / eps) / (iter_max - 1) (0 when
+ *   iter_max == 1), eta[t] = eta_max * exp(-lambda t), cooling_start = (int)(iter_max * cooling), terms_per_iter =
+ *   (uint64)(term_updates * steps) --, calls the provider, gives the nodes the ids 1..N in the new order and chops:
+ *   C   a node longer than max_node_length becomes ceil(len / max) consecutive nodes of max bases each, the last one taking the
+ *       rest; ids are renumbered 1..N' in order; a forward step becomes the pieces in order, a reverse step the pieces in reverse
+ *       order, each reversed; an edge attaches to the end piece its orientation touches (leaving n+: the last piece, leaving n-:
+ *       the first, entering n+: the first, entering n-: the last), in the orientation the L line was written in; the piece-to-
+ *       piece edges k+ -> (k+1)+ are added.  Output: the H line, S lines in id order, L lines sorted by (from, from-orientation,
+ *       to, to-orientation; + before -) with duplicates removed, P lines in input order.
+ *   sxg_graph keeps the L lines as read for this call (16 bytes per line, also in graphs that are never prepped).
+ *   term_updates * steps must stay below 2^63, nodes below 2^31 and steps below 2^32 (decree Y1): SXG_E_INVALID otherwise.
+ *   max_node_length 0 = do not chop.  out / out_gfa: either may be NULL; release with sxg_graph_free / sxg_smooth_free. */
+typedef struct sxg_prep_params {
+    uint32_t struct_size;     /* sizeof(sxg_prep_params) of the caller's header */
+    int32_t max_node_length;  /* src/main.cpp:426 (odgi chop to 100), default 100 */
+    double term_updates;      /* path_sgd_term_updates: terms per iteration as a multiple of the path steps, default 1 */
+    int32_t iter_max;         /* default 100 */
+    int32_t mode;             /* handed to the provider: 0 = choose, 1 = LDS path, 2 = global path; default 0 */
+    double eps;               /* default 0.01 */
+    double cooling;           /* the share of the iterations before cooling starts, default 0.5 */
+    uint64_t seed;            /* default SXG_PREP_SEED */
+} sxg_prep_params;
+#define SXG_PREP_SEED 9399220ull
+void sxg_prep_default_params(sxg_prep_params *pp);
+typedef int (*sxg_sgd_fn)(void *ctx, const sxg_poa_sgd_in *in, int32_t *order, int64_t *x);
+int sxg_graph_prep(const sxg_graph *g, const sxg_prep_params *pp, sxg_sgd_fn sort, void *ctx, sxg_graph **out, char **out_gfa);
+
 #ifdef __cplusplus
 }
 #endif

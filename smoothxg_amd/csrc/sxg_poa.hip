@@ -26,6 +26,7 @@
 #include "poa_kern_tables.hip.h"   // kernel classes by geometry; instantiated in the kern_*.hip translation units
 #include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
+#include "poa_sgd.hip.h"           // the path-guided SGD node order of prep: argument struct and launchers (kernels in kern_sgd.hip)
 
 
 // ---------------------------------------------------------------------------------------
@@ -2701,6 +2702,114 @@ extern "C" int sxg_poa_kmer_jaccard_batch(sxg_poa_handle* h, int64_t n_seqs, con
     if (kmers && seq_off[n_seqs] > 0) HIPCHK(hipMemcpy(kmers, B.sets.p, 8 * (size_t)seq_off[n_seqs], hipMemcpyDeviceToHost));
     split_stats(h, ms, 0, n_slots, dev_bytes);
     h->stats.dp_launches = n_pairs ? 2 : 1;
+    return SXG_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The path-guided SGD node order of prep (src/prep.cpp:11-163): decree Y (include/sxg_poa.h).  Kernels in
+// poa_sgd.hip.h / kern_sgd.hip; here the validation, Y1's start coordinates, the choice of the path, the batch loop of the global
+// path (one term launch + one apply launch per batch, on the handle's stream) and Y7's sort.
+static_assert(SXG_POA_SGD_LDS_NODES == SXG_SGD_LDS_NODES, "LDS bound of the header");
+extern "C" int sxg_poa_path_sgd_order(sxg_poa_handle* h, const sxg_poa_sgd_in* in, int32_t* order, int64_t* x) {
+    if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
+    const int64_t N = in->n_nodes, P = in->n_paths;
+    if (N < 0 || P < 0 || N >= (1ll << 31) || P >= (1ll << 31)) return fail(SXG_E_INVALID, "path_sgd_order: node or path count out of range");
+    if (N > 0 && (!in->node_len || !order)) return fail(SXG_E_INVALID, "path_sgd_order: node_len or order is NULL");
+    if (P > 0 && !in->path_off) return fail(SXG_E_INVALID, "path_sgd_order: path_off is NULL");
+    if (in->mode < 0 || in->mode > 2) return fail(SXG_E_INVALID, "path_sgd_order: mode must be 0, 1 or 2");
+    if (in->iter_max < 0 || in->cooling_start < 0) return fail(SXG_E_INVALID, "path_sgd_order: negative iteration count");
+    if (in->iter_max > 0 && !in->eta) return fail(SXG_E_INVALID, "path_sgd_order: eta is NULL");
+    std::vector<int64_t> X((size_t)std::max<int64_t>(N, 1));
+    int64_t total = 0;
+    for (int64_t n = 0; n < N; ++n) {                                                   // Y1
+        if (in->node_len[n] < 0) return fail(SXG_E_INVALID, "path_sgd_order: negative node length");
+        X[(size_t)n] = total << SXG_SGD_SHIFT;
+        total += in->node_len[n];
+        if (total >= (1ll << 40)) return fail(SXG_E_INVALID, "path_sgd_order: total node length reaches 2^40");
+    }
+    const int64_t S = P > 0 ? in->path_off[P] : 0;
+    int64_t maxsteps = 0;
+    if (P > 0) {
+        if (in->path_off[0] != 0) return fail(SXG_E_INVALID, "path_off[0] must be 0");
+        for (int64_t p = 0; p < P; ++p) {
+            if (in->path_off[p + 1] < in->path_off[p]) return fail(SXG_E_INVALID, "path_off not monotone");
+            maxsteps = std::max(maxsteps, in->path_off[p + 1] - in->path_off[p]);
+        }
+        if (S >= (1ll << 32)) return fail(SXG_E_INVALID, "path_sgd_order: 2^32 steps or more");
+        if (S > 0 && (!in->step_node || !in->step_pos)) return fail(SXG_E_INVALID, "path_sgd_order: step arrays are NULL");
+        for (int64_t s = 0; s < S; ++s)
+            if (in->step_node[s] < 0 || in->step_node[s] >= N || in->step_pos[s] < 0 || in->step_pos[s] >= (1ll << 41))
+                return fail(SXG_E_INVALID, "path_sgd_order: step " + std::to_string(s) + " names no node or lies beyond 2^41 bp");
+    }
+    // mode 0 takes the LDS path when the nodes fit AND the whole sort is at most SXG_POA_SGD_LDS_TERMS terms: one workgroup in
+    // one launch runs them all, and a launch should end in seconds.  Beyond that (or if the runtime refuses the dynamic LDS) the
+    // choice is the global path, which gives the same bits.
+    const bool few_terms = in->iter_max == 0 || in->terms_per_iter <= SXG_POA_SGD_LDS_TERMS / (uint64_t)in->iter_max;
+    bool lds = in->mode == 1 || (in->mode == 0 && N <= SXG_SGD_LDS_NODES && few_terms);
+    if (in->mode == 1 && N > SXG_SGD_LDS_NODES) return fail(SXG_E_INVALID, "path_sgd_order: the LDS path holds at most " + std::to_string(SXG_SGD_LDS_NODES) + " nodes");
+    RoctxRange range("sxg_poa_path_sgd_order");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    if (N == 0) return SXG_OK;
+    const uint64_t terms = S > 0 ? in->terms_per_iter : 0;
+    const uint64_t B = (uint64_t)std::max<int64_t>(1, N / 8);                           // Y6
+    uint64_t launches = 0;
+    if (terms > 0 && in->iter_max > 0) {
+        const uint64_t batches = (terms + B - 1) / B;
+        if (lds) {
+            if (int e = sxg_sgd_prepare_lds(16 * (size_t)N)) {
+                if (in->mode == 1) return fail(SXG_E_NODEVICE, "path_sgd_order: " + std::to_string(16 * (size_t)N) + " bytes of dynamic LDS refused (HIP error " + std::to_string(e) + ")");
+                (void)hipGetLastError();
+                lds = false;
+            }
+        }
+        if (!lds && batches > (1ull << 40) / (uint64_t)in->iter_max) return fail(SXG_E_INVALID, "path_sgd_order: too many batches");
+        const size_t dev_bytes = 16 * (size_t)N + 4 * (size_t)N + 8 * (size_t)(P + 1) + 12 * (size_t)S + 8 * (size_t)in->iter_max;
+        if ((uint64_t)dev_bytes > arena_budget(h)) return fail(SXG_E_NOMEM, "memory budget too small for the node coordinates and the path steps");
+        SplitBufs Bf;
+        if (int rc = split_up(h, Bf.a, in->node_len, (size_t)N)) return rc;
+        if (int rc = split_up(h, Bf.b, in->path_off, (size_t)(P + 1))) return rc;
+        if (int rc = split_up(h, Bf.c, in->step_node, (size_t)S)) return rc;
+        if (int rc = split_up(h, Bf.d, in->step_pos, (size_t)S)) return rc;
+        if (int rc = split_up(h, Bf.e, in->eta, (size_t)in->iter_max)) return rc;
+        if (int rc = split_up(h, Bf.f, X.data(), (size_t)N)) return rc;
+        if (int rc = Bf.g.ensure(8 * (size_t)N)) return rc;
+        HIPCHK(hipMemsetAsync(Bf.g.p, 0, 8 * (size_t)N, h->stream));
+        SgdArgs A;
+        A.node_len = Bf.a.as<int32_t>(); A.path_off = Bf.b.as<int64_t>(); A.step_node = Bf.c.as<int32_t>(); A.step_pos = Bf.d.as<int64_t>();
+        A.eta = Bf.e.as<double>(); A.X = Bf.f.as<unsigned long long>(); A.D = Bf.g.as<unsigned long long>();
+        A.n_nodes = (int32_t)N; A.n_paths = (int32_t)P; A.S = (uint64_t)S; A.iter_max = in->iter_max; A.cooling_start = in->cooling_start;
+        int nb = 0;
+        for (uint64_t v = (uint64_t)(maxsteps - 1); v; v >>= 1) ++nb;                   // Y4: bitlength(maxsteps - 1)
+        A.nb = std::max(nb, 1);
+        A.terms_per_iter = terms; A.seed = in->seed; A.B = B;
+        const int threads = lds ? (int)std::min<uint64_t>(1024, (std::min<uint64_t>(B, terms) + 63) / 64 * 64) : SXG_SGD_TERM_THREADS;
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        if (lds) {
+            sxg_sgd_launch_lds(A, threads, 16 * (size_t)N, h->stream);
+            launches = 1;
+        } else {
+            for (int it = 0; it < in->iter_max; ++it)
+                for (uint64_t k0 = 0; k0 < terms; k0 += B) {
+                    sxg_sgd_launch_terms(A, it, k0, (uint32_t)std::min<uint64_t>(B, terms - k0), h->stream);
+                    sxg_sgd_launch_apply(A, h->stream);
+                    launches += 2;
+                }
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipEventSynchronize(h->ev1));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        HIPCHK(hipMemcpy(X.data(), Bf.f.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+        h->stats.kernel_ms = ms; h->stats.dom_kernel_ms = ms; h->stats.dp_launches = launches; h->stats.n_slots = (int32_t)std::min<uint64_t>(launches, 0x7fffffff);
+        h->stats.device_bytes = dev_bytes; h->stats.dom_threads = threads;
+    }
+    std::vector<int32_t> ord((size_t)N);                                                // Y7: by (X, old rank)
+    for (int64_t n = 0; n < N; ++n) ord[(size_t)n] = (int32_t)n;
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return X[(size_t)a] < X[(size_t)b]; });
+    memcpy(order, ord.data(), 4 * (size_t)N);
+    if (x) memcpy(x, X.data(), 8 * (size_t)N);
     return SXG_OK;
 }
 

@@ -11,6 +11,7 @@
 // odgi's unchop / topological_order / to_gfa are absent from the reference snapshot; they are
 // restated by decree and mirrored line for line by oracle/smooth_oracle.py.
 #include "../../include/sxg_smooth.h"
+#include "prep_host.h"   // flatten, schedule, apply, chop of sxg_graph_prep (a header of its own: tests build it stand-alone)
 
 #include <omp.h>
 #include <sys/mman.h>
@@ -68,6 +69,7 @@ struct sxg_graph {
     std::vector<std::vector<handle_t>> right_of, left_of;          // by node rank: follow_edges(n+, false / true)
     std::vector<std::vector<std::pair<uint32_t, uint32_t>>> on_node;  // (path, step) of every visit, path-major
     std::vector<uint64_t> vec_off;
+    std::vector<std::pair<handle_t, handle_t>> edges;   // the L lines as written (what prep re-writes)
     std::string sequence(handle_t h) const { return rev(h) ? revcomp(seq[nid(h)]) : seq[nid(h)]; }
     std::string path_sequence(size_t p) const {
         std::string s;
@@ -1990,6 +1992,7 @@ int sxg_graph_from_gfa(const char* text, size_t len, sxg_graph** out) {
         const handle_t A = mk(ia->second, l.ar), Bh = mk(ib->second, l.br);   // edge A -> B  ==  flip(B) -> flip(A)
         if (!rev(A)) g->right_of[nid(A)].push_back(Bh); else g->left_of[nid(A)].push_back(flip(Bh));
         if (!rev(Bh)) g->left_of[nid(Bh)].push_back(A); else g->right_of[nid(Bh)].push_back(flip(A));
+        g->edges.emplace_back(A, Bh);
     }
     for (size_t p = 0; p < g->steps.size(); ++p)
         for (size_t st = 0; st < g->steps[p].size(); ++st) g->on_node[nid(g->steps[p][st])].emplace_back((uint32_t)p, (uint32_t)st);
@@ -1999,6 +2002,42 @@ int sxg_graph_from_gfa(const char* text, size_t len, sxg_graph** out) {
 void sxg_graph_free(sxg_graph* g) { delete g; }
 int64_t sxg_graph_node_count(const sxg_graph* g) { return g ? (int64_t)g->seq.size() : 0; }
 int64_t sxg_graph_path_count(const sxg_graph* g) { return g ? (int64_t)g->pname.size() : 0; }
+
+// ---------------------------------------------------------------------------------------------
+// prep (src/prep.cpp:11-163): flatten -> schedule Y2 -> the provider's order -> ids in that order -> chop (decree C) -> GFA.
+// Mirrored by tests/prep_ref.py.
+void sxg_prep_default_params(sxg_prep_params* pp) {
+    if (!pp) return;
+    pp->struct_size = (uint32_t)sizeof(sxg_prep_params);
+    pp->max_node_length = 100;                                       // src/main.cpp:426
+    pp->term_updates = 1.0; pp->iter_max = 100; pp->mode = 0;        // src/prep.cpp:45-63
+    pp->eps = 0.01; pp->cooling = 0.5;
+    pp->seed = SXG_PREP_SEED;
+}
+
+int sxg_graph_prep(const sxg_graph* g, const sxg_prep_params* pp, sxg_sgd_fn sort, void* ctx, sxg_graph** out, char** out_gfa) {
+    if (out) *out = nullptr;
+    if (out_gfa) *out_gfa = nullptr;
+    if (!g || !pp || !sort) return fail(SXG_E_INVALID, "NULL argument");
+    if (pp->struct_size != sizeof(sxg_prep_params))
+        return fail(SXG_E_INVALID, "sxg_prep_params was not initialised by sxg_prep_default_params of this library's header");
+    if (pp->max_node_length < 0 || pp->iter_max < 0 || !(pp->term_updates >= 0) || !(pp->eps > 0) || !(pp->cooling >= 0 && pp->cooling <= 1) ||
+        pp->mode < 0 || pp->mode > 2)
+        return fail(SXG_E_INVALID, "sxg_prep_params: value out of range");
+    std::string o, err;
+    if (int rc = sxg_prep::run(sxg_prep::graph_view{g->seq, g->pname, g->steps, g->pos, g->edges}, *pp, sort, ctx, o, err)) return fail(rc, err);
+    if (out) {
+        if (int rc = sxg_graph_from_gfa(o.data(), o.size(), out)) return rc;
+    }
+    if (out_gfa) {
+        *out_gfa = dup_out(o);
+        if (!*out_gfa) {
+            if (out) { sxg_graph_free(*out); *out = nullptr; }
+            return fail(SXG_E_NOMEM, "out of memory");
+        }
+    }
+    return SXG_OK;
+}
 
 int sxg_blockset_by_path_windows(const sxg_graph* g, uint64_t target_bp, sxg_blockset** out) {
     if (!g || !out || target_bp == 0) return fail(SXG_E_INVALID, "bad argument");

@@ -94,12 +94,20 @@ class SplitMash(C.Structure):
     _fields_ = [("kmer_size", C.c_int32), ("min_len", _i32p), ("est_identity", C.POINTER(C.c_double))]
 
 
+class SgdIn(C.Structure):
+    """sxg_poa_sgd_in: the flattened graph, the schedule and the seed of the path-guided SGD node order (decree Y)."""
+    _fields_ = [("n_nodes", C.c_int64), ("node_len", _i32p), ("n_paths", C.c_int64), ("path_off", _i64p), ("step_node", _i32p),
+                ("step_pos", _i64p), ("iter_max", C.c_int32), ("cooling_start", C.c_int32), ("eta", C.POINTER(C.c_double)),
+                ("terms_per_iter", C.c_uint64), ("seed", C.c_uint64), ("mode", C.c_int32)]
+
+
+SGD_LDS_NODES = 8192   # SXG_POA_SGD_LDS_NODES: nodes the one-workgroup path of the SGD order keeps on chip
 MASH_SORT_TILE = 1024   # SXG_POA_MASH_SORT_TILE: k-mers a workgroup sorts on chip at once
 SPLIT_PANEL = 512   # SXG_POA_SPLIT_PANEL: columns of the second sequence a wavefront sweeps at once
 MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
 ST_TOO_LONG = 5
 
-EXPORTS = ["sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
+EXPORTS = ["sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
            "sxg_poa_get_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
@@ -156,6 +164,7 @@ def load_library(build_if_missing=True):
     L.sxg_poa_kmer_jaccard_batch.argtypes = [vp, C.c_int64, _i64p, _u8p, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint64)]
     L.sxg_poa_split_mash_batch.argtypes = [vp, C.POINTER(SplitIn), C.POINTER(SplitMash), C.POINTER(SplitOut), _i64p]
     L.sxg_poa_split_free.restype = None
+    L.sxg_poa_path_sgd_order.argtypes = [vp, C.POINTER(SgdIn), _i32p, _i64p]
     L.sxg_xxh64.restype = C.c_uint64
     L.sxg_xxh64.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64]
     _lib = L
@@ -560,6 +569,28 @@ class PoaEngine:
             return [(grp[blk_off[b]:blk_off[b + 1]], int(ng[b]), int(npairs[b]), int(nm[b]), int(st[b])) for b in range(nb)]
         finally:
             self.lib.sxg_poa_split_free(C.byref(out))
+
+    # -- the node order of prep (src/prep.cpp:11-163) ----------------------------------------
+    def path_sgd_order(self, node_len, path_off, step_node, step_pos, eta, cooling_start, terms_per_iter, seed, mode=0, want_x=True):
+        """sxg_poa_path_sgd_order (decree Y).  node_len: bases of every node in rank order; path_off / step_node / step_pos:
+        the paths as flat steps (node rank, bp offset in the path); eta: the learning rate of every iteration (None reaches
+        the library as NULL); mode: 0 = choose, 1 = LDS path, 2 = global path.  Returns (order, x): the old ranks in the new
+        order (int32) and the final coordinates by old rank (int64, units of 2^-20 bp; None unless want_x)."""
+        def arr(a, t):   # (an empty array has no address worth passing)
+            a = np.ascontiguousarray(a, t)
+            return a if len(a) else np.zeros(1, t)
+        n, n_paths = len(node_len), len(path_off) - 1
+        node_len, path_off, step_node, step_pos = arr(node_len, np.int32), arr(path_off, np.int64), arr(step_node, np.int32), arr(step_pos, np.int64)
+        si = SgdIn(n, _p(node_len, C.c_int32), n_paths, _p(path_off, C.c_int64), _p(step_node, C.c_int32), _p(step_pos, C.c_int64),
+                   1, int(cooling_start), None, int(terms_per_iter), int(seed), int(mode))
+        if eta is not None:
+            si.iter_max = len(eta)
+            eta = arr(eta, np.float64)
+            si.eta = _p(eta, C.c_double)
+        order, x = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64)
+        if self.lib.sxg_poa_path_sgd_order(self.h, C.byref(si), _p(order, C.c_int32), _p(x, C.c_int64) if want_x else None):
+            raise self._err("sxg_poa_path_sgd_order")
+        return order[:n], (x[:n] if want_x else None)
 
     # -- stand-alone Align(sequence, graph) --------------------------------------------
     def align(self, problems, params, check=True):

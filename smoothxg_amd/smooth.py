@@ -16,6 +16,7 @@ FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.BatchOut))
 SPLIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitOut))
 SPLIT_FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.SplitOut))
 SPLIT_MASH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitMash), C.POINTER(_poa.SplitOut), C.POINTER(C.c_int64))
+SGD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SgdIn), C.POINTER(C.c_int32), C.POINTER(C.c_int64))
 
 
 class SmoothParams(C.Structure):
@@ -32,7 +33,14 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_blockset_free", "sxg_blockset_size", "sxg_block_collect_text", "sxg_block_graph_gfa",
            "sxg_smooth_gfa", "sxg_adaptive_poa_scores", "sxg_block_identity_threshold",
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
-           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa"]
+           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa",
+           "sxg_prep_default_params", "sxg_graph_prep"]
+
+
+class PrepParams(C.Structure):
+    """sxg_prep_params: the knobs of prep (src/prep.cpp, src/main.cpp:423-433) with the reference's defaults."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_node_length", C.c_int32), ("term_updates", C.c_double), ("iter_max", C.c_int32),
+                ("mode", C.c_int32), ("eps", C.c_double), ("cooling", C.c_double), ("seed", C.c_uint64)]
 
 
 class MergeParams(C.Structure):
@@ -86,6 +94,9 @@ def load_library():
                                      C.POINTER(C.c_int64)]
     L.sxg_block_maf_rows.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
     L.sxg_block_maf.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
+    L.sxg_prep_default_params.restype = None
+    L.sxg_prep_default_params.argtypes = [C.POINTER(PrepParams)]
+    L.sxg_graph_prep.argtypes = [vp, C.POINTER(PrepParams), vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.sxg_adaptive_poa_scores.restype = None
     L.sxg_adaptive_poa_scores.argtypes = [C.c_float, C.POINTER(C.c_int32 * 6), C.POINTER(C.c_int32 * 6)]
     L.sxg_block_identity_threshold.argtypes = [vp, vp, C.c_int64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -133,6 +144,67 @@ def gpu_mash_splitter(engine):
     the mash split provider of Smoother.split_blocks_mash."""
     L = engine.lib
     return C.cast(L.sxg_poa_split_mash_batch, C.c_void_p), C.cast(L.sxg_poa_split_free, C.c_void_p), engine.h
+
+
+def gpu_sorter(engine):
+    """(sort, ctx) backed by the GPU engine: sxg_poa_path_sgd_order of libsxgpoa.so and the engine handle -- the sort
+    provider of prep_gfa."""
+    return C.cast(engine.lib.sxg_poa_path_sgd_order, C.c_void_p), engine.h
+
+
+def python_sorter(fn):
+    """(sort, ctx) around a Python function fn(node_len, path_off, step_node, step_pos, eta, cooling_start, terms_per_iter,
+    seed) -> order (or (order, x)), the arrays being numpy copies of what the library flattened: for tests and experiments,
+    the production provider is gpu_sorter.  The tuple keeps the callback alive."""
+    import numpy as np
+
+    def view(ptr, n, dtype):
+        return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+
+    def call(ctx, inp, order, x):
+        try:
+            a = inp.contents
+            path_off = view(a.path_off, a.n_paths + 1, np.int64) if a.n_paths else np.zeros(1, np.int64)
+            n_steps = int(path_off[-1])
+            res = fn(view(a.node_len, a.n_nodes, np.int32), path_off, view(a.step_node, n_steps, np.int32), view(a.step_pos, n_steps, np.int64),
+                     view(a.eta, a.iter_max, np.float64), a.cooling_start, a.terms_per_iter, a.seed)
+            ord_ = np.asarray(res[0] if isinstance(res, tuple) else res, np.int32)
+            if len(ord_) != a.n_nodes:
+                return -1
+            for k in range(a.n_nodes):
+                order[k] = int(ord_[k])
+            return 0
+        except Exception:   # (an exception must not cross the C frames)
+            return -1
+    cb = SGD_FN(call)
+    return C.cast(cb, C.c_void_p), None, cb
+
+
+def prep_gfa(text, sorter, **params):
+    """prep (sxg_graph_prep): the GFA sorted by path-guided SGD -- the order comes from `sorter`, gpu_sorter(engine) in
+    production -- and chopped to nodes of at most max_node_length bases.  params: fields of sxg_prep_params
+    (max_node_length, term_updates, iter_max, eps, cooling, seed, mode).  A prepped smoothing iteration is
+    Smoother(prep_gfa(text, gpu_sorter(engine)), discover=...)."""
+    L = load_library()
+    pp = PrepParams()
+    L.sxg_prep_default_params(C.byref(pp))
+    for k, v in params.items():
+        if k not in dict(PrepParams._fields_) or k == "struct_size":
+            raise TypeError("prep_gfa: no such parameter: " + k)
+        setattr(pp, k, v)
+    data = text.encode() if isinstance(text, str) else text
+    g, out = C.c_void_p(), C.c_void_p()
+    if L.sxg_graph_from_gfa(data, len(data), C.byref(g)):
+        raise SmoothError(L.sxg_smooth_last_error().decode())
+    try:
+        if L.sxg_graph_prep(g, C.byref(pp), sorter[0], sorter[1], None, C.byref(out)):
+            raise SmoothError(L.sxg_smooth_last_error().decode())
+        try:
+            return C.string_at(out).decode()
+        finally:
+            L.sxg_smooth_free(out)
+    finally:
+        L.sxg_graph_free(g)
 
 
 class Smoother:
