@@ -250,6 +250,18 @@ typedef struct sxg_poa_stats {
     double bg_ms;          /* HIP-event time of the block-graph kernel (want_block_graph), not part of kernel_ms */
 } sxg_poa_stats;
 
+/* Packed sweep, strip width per alignment (the classes with a second width W2 = W - 1 run every alignment whose sequence fits
+ * T * 2 * W2 columns in strips of W2 columns; SXG_POA_WIDTH2=0 switches that off): what the sweeps of the last execute ran at,
+ * summed over its launches from the slots' counters.  Index 0: the geometry's width W, 1: the second width.  A repeated sweep
+ * (hint shift after a band miss) counts again. */
+typedef struct sxg_poa_width_stats {
+    uint64_t sweeps[2];       /* sweeps (alignments and their repeats) */
+    uint64_t swept_cols[2];   /* columns of those sweeps' geometries, T * 2 * width each */
+    uint64_t swept_cells[2];  /* graph rows x columns of those sweeps */
+    uint64_t hint_shift_repeats; /* sweeps repeated inside the kernel with shifted hints */
+    int32_t dom_width, dom_width2; /* strip widths of the dominant launch (dom_width2 = 0: one width only) */
+} sxg_poa_width_stats;
+
 int sxg_poa_abi_version(void);
 /* Measurement aids (no counterpart in the reference; SURVEY sections 5 and 8d).
  * _measure_copy: a streaming device-to-device copy of `bytes` bytes on this engine's device and stream, timed with HIP events over
@@ -463,6 +475,7 @@ typedef struct sxg_poa_sgd_in {
 int sxg_poa_path_sgd_order(sxg_poa_handle *h, const sxg_poa_sgd_in *in, int32_t *order, int64_t *x);
 
 int sxg_poa_get_stats(sxg_poa_handle *h, sxg_poa_stats *out);
+int sxg_poa_get_width_stats(sxg_poa_handle *h, sxg_poa_width_stats *out);
 /* Cap on device memory the handle may use for scratch arenas (bytes; 0 = default 3/4 of free). */
 int sxg_poa_set_memory_budget(sxg_poa_handle *h, uint64_t bytes);
 

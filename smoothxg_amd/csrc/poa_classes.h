@@ -13,6 +13,9 @@ struct Variant {
     int W, NW, TMAX, RM;
     int CB = 4;
     bool DS = false;   // the class compiled for smoothxg's default scores (packed sweep, 2-byte cells, convex)
+    // second strip width of the launch's class (class_w2; 0 = none): an alignment whose sequence fits T * 2 * W2 columns sweeps
+    // strips of W2 columns.  Follows from the class (prepare_plan sets it); not part of a geometry's identity (operator==).
+    int W2 = 0;
     constexpr int T() const { return 64 * NW; }
     constexpr int Lpad() const { return 64 * NW * W * (RM >= 2 ? 2 : 1); }
     constexpr bool operator==(const Variant& o) const { return W == o.W && NW == o.NW && TMAX == o.TMAX && RM == o.RM && CB == o.CB && DS == o.DS; }
@@ -58,7 +61,9 @@ constexpr ClassTraits class_traits(int TMAX, int W, int RM, int CB) {
 // The assignment to parts balances the build; a part's classes are instantiated row by row, width by width, row mode by row mode.
 enum ClassKind { CLASS_BLOCK = 0, CLASS_ALIGN = 1 };
 enum : unsigned { CLS_LOCAL = 1, CLS_GLOBAL = 2, CLS_BOTH = 3, CLS_DS = 4 };
-struct ClassRow { int part; ClassKind kind; unsigned rms; int cb, tmax; unsigned widths, modes; };
+// widths2: the widths W of the row whose classes are also compiled for strips of W - 1 columns (the second width, picked per
+// alignment inside the block kernel -- poa_kernels.hip.h)
+struct ClassRow { int part; ClassKind kind; unsigned rms; int cb, tmax; unsigned widths, modes; unsigned widths2 = 0; };
 constexpr unsigned cw(int w) { return 1u << w; }   // a strip width / a row mode as a bit of ClassRow::widths / rms
 constexpr unsigned RM0 = cw(0), RM1 = cw(1), RM2 = cw(2), RM3 = cw(3), RM01 = RM0 | RM1;
 constexpr unsigned cw_range(int lo, int hi) { unsigned m = 0; for (int w = lo; w <= hi; ++w) m |= cw(w); return m; }
@@ -75,8 +80,10 @@ constexpr ClassRow kClasses[] = {
     {1, CLASS_ALIGN, RM01, 4, 1024, cw(8) | cw(12), CLS_BOTH},
     // parts 2, 3: packed sweep, block kernels, 2-byte delta plane cells, 4 / 8 and 16 waves
     // (the long classes, 16 waves of 10, 12, 13 columns, exist for local alignment only: a global score of such lengths does not fit int16)
-    {2, CLASS_BLOCK, RM2, 2, 256, cw_range(4, 12), CLS_BOTH | CLS_DS},
-    {3, CLASS_BLOCK, RM2, 2, 512, cw_range(8, 12), CLS_BOTH | CLS_DS},
+    // (W = 9 .. 12 with the second width W - 1: sequences of 4.6-6.1 kbp and 9.2-12.3 kbp, whose blocks mix lengths on either side
+    //  of a width's columns)
+    {2, CLASS_BLOCK, RM2, 2, 256, cw_range(4, 12), CLS_BOTH | CLS_DS, cw_range(9, 12)},
+    {3, CLASS_BLOCK, RM2, 2, 512, cw_range(8, 12), CLS_BOTH | CLS_DS, cw_range(9, 12)},
     {3, CLASS_BLOCK, RM2, 2, 1024, cw(8), CLS_BOTH | CLS_DS},
     {3, CLASS_BLOCK, RM2, 2, 1024, cw(10) | cw(12) | cw(13), CLS_LOCAL | CLS_DS},
     // parts 4, 5: ... 4-byte plane cells (score sets whose deltas do not fit 16 bits); no class of its own for one to three waves
@@ -106,6 +113,13 @@ constexpr int class_row(ClassKind kind, const Variant& v, bool sw) {
     }
     return -1;
 }
+// The second strip width of the class of geometry v (0: the class has none), and the width an alignment of `len` letters runs
+// at on T threads: the narrowest of W2 and W that covers it (a sequence beyond W's columns is ST_TOO_LONG, tested against W).
+constexpr int class_w2(ClassKind kind, const Variant& v, bool sw) {
+    const int r = class_row(kind, v, sw);
+    return r >= 0 && (kClasses[r].widths2 & cw(v.W)) ? v.W - 1 : 0;
+}
+constexpr int width_for_len(int W, int W2, int T, int len) { return W2 != 0 && len + 1 <= T * 2 * W2 ? W2 : W; }
 // (cvx: both gap models of a row are built; a geometry that asks for the default-score class of a row without one runs the general class)
 constexpr bool class_built(const Variant& v, bool /*cvx*/, bool sw, ClassKind kind = CLASS_BLOCK) { return class_row(kind, v, sw) >= 0; }
 

@@ -120,6 +120,7 @@ SXG_HD int group_end(const GraphView& G, int leader, int n_old) {
 // keep_order = false (round 6): the caller re-sorts the graph right behind this call (decree S7', spoa_resort below, which
 // neither reads nor keeps the incrementally kept order): the slots of the new nodes, the shift of the old ones and the copy of
 // the order -- the gathers through the groups' ranks and two passes over all nodes -- are left out.
+// (Reads the walk's result, posnode, per sequence POSITION: the strip width the sweep and its traceback ran at does not reach it.)
 template <class Ctx>
 SXG_HD_PHASE void add_alignment(Ctx& c, const GraphView& G_, const uint8_t* seq_, int len,
                           uint32_t weight, int32_t* path_out_, const bool keep_order = true) {
@@ -692,6 +693,7 @@ SXG_HD void spoa_resort_par(Ctx& c, const GraphView& G, WP W, const int n, const
 
 // lst / lst_cap: bytes of the workgroup's LDS the re-sort may use (the per-node words); n_static: ids below it are the
 // block's first sequence (a chain) -- 0 when the caller does not know; len, n_prev, full: see spoa_resort_par.
+// (Graph only; the LDS it uses is the launch's, sized for the larger of a dual-width class's two sweep layouts: no strip width here.)
 template <class Ctx, class LdsP>
 SXG_HD_PHASE void spoa_resort(Ctx& c, const GraphView& G_, LdsP lst, const int lst_cap, const int n_static, const int len, const int n_prev,
                               const bool full, unsigned long long* rprof = nullptr) {
@@ -707,6 +709,8 @@ struct RowCaps {
     int pool_slots; // row-pool slots
     int step_cap;   // fold steps of the step-mask plane (sum over multi-pred rows of np-1)
     int lds_rows;   // packed sweep: stored rows the workgroup can keep in LDS at a time (0: every stored row goes to the ring)
+                    // (one count for both strip widths of a dual-width class: finish_rows numbers on-chip copies as
+                    //  stored-row number mod lds_rows, whatever width the sweep then runs at)
 };
 
 // Second half of row preparation, shared by the block kernel (graph -> rows) and the
@@ -718,6 +722,7 @@ struct RowCaps {
 // carries the hints of the first two predecessors where the ring slots would be;
 // 3 = banded sweep with the ADAPTIVE band (decree B4) -- R.tbx holds remain() of every row; the bands follow from the
 // sweep itself, which leaves every finished row's band and best-cell columns in words 6 and 7 of its descriptor.
+// Independent of the packed sweep's strip width: slots are counted in rows (caps.pool_slots, caps.lds_rows), hints are columns.
 template <class Ctx>
 // (finish_rows keeps reading its view through the reference: with the scalar copy the 32-bit kernels trip the AMDGPU back-end
 //  assertion on the shared-aperture null check that WgCtx's comment in poa_dp.hip.h describes)
@@ -869,6 +874,8 @@ SXG_HD_PHASE void rows_remain(Ctx& c, const GraphView& G, int N, SXG_GP int32_t*
 
 // Rank-space CSR + per-row DP metadata of the current graph.  Returns a status code
 // (identical on every thread).
+// (The packed sweep's band hints written here are COLUMNS, xpos of the row's node: the same rows serve a sweep at either of a
+//  dual-width class's strip widths, and a repeat after a hint shift.)
 template <class Ctx>
 SXG_HD_PHASE int prep_rows(Ctx& c, const GraphView& G_, const RowsView& R_, const RowCaps& caps, const int hinted = 0) {
     const GraphView G = sxg_scalar_view(G_);

@@ -38,7 +38,7 @@ template <class Args, int PART, int R, int W, int RM> constexpr bool class_here(
 template <class Args, int R, int W, int RM, bool CVX, bool SW, bool DS> static KernelFn<Args> class_kernel() {
     constexpr ClassRow c = kClasses[R];
     if constexpr (std::is_same_v<Args, AlignArgs>) return poa_align_kernel<c.tmax, W, CVX, RM, SW>;
-    else return poa_block_kernel<c.tmax, W, CVX, RM, SW, c.cb, DS>;
+    else return poa_block_kernel<c.tmax, W, CVX, RM, SW, c.cb, DS, (c.widths2 & cw(W)) != 0 ? W - 1 : 0>;   // (the second width: class_w2)
 }
 // the kernel of a class for (cvx, sw, ds): only the modes its row lists are instantiated
 template <class Args, int R, int W, int RM> static KernelFn<Args> pick_mode(bool cvx, bool sw, bool ds) {

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/sxg_poa.h"
@@ -29,6 +30,9 @@ struct SlotLayout {  // byte offsets inside one slot arena (all 16-byte aligned)
     int nodes_cap, rows_cap, pool_slots, step_cap, scratch_len, Lpad, word_bytes, threads;
     int band_strips;  // packed sweep: strips per row in the traceback plane (0 = not the packed sweep)
     int lds_rows;     // packed sweep: stored rows the workgroup's LDS holds on chip (set by prepare_plan)
+    // packed sweep with a second strip width (poa_classes.h::class_w2): W2 > 0 = alignments that fit T * 2 * W2 columns sweep strips
+    // of W2 columns, with band_strips2 strips per plane row; 0 = every alignment at the geometry's width
+    int W2, band_strips2;
 };
 
 inline size_t lay(size_t& cur, size_t bytes) {
@@ -41,14 +45,18 @@ inline size_t lay(size_t& cur, size_t bytes) {
 // codes, W + 1 halfwords per strip; 4: one dword per cell)
 // spoa_scratch: the launch holds blocks that ask for spoa's depth-first order (S7'): stacks, records and the kept state of the
 // re-sort, ~104 bytes per node of nodes_cap -- left out of every other arena
+// W2, band_strips2: the second strip width of the launch's alignments and its strips per plane row (0: none).  The plane is sized
+// for the larger of the two (strips x dwords per strip); pool, row 0 and park for the geometry's own width, whose rows are the longer.
 inline SlotLayout make_layout(int nodes_cap, int rows_cap, int pool_slots, int step_cap, int threads, int Lpad,
-                              int word_bytes, bool pairs, int band_strips = 0, int cell_bytes = 4, bool spoa_scratch = false) {
+                              int word_bytes, bool pairs, int band_strips = 0, int cell_bytes = 4, bool spoa_scratch = false,
+                              int W2 = 0, int band_strips2 = 0) {
     SlotLayout L;
     memset(&L, 0, sizeof(L));
     L.nodes_cap = nodes_cap; L.rows_cap = rows_cap; L.pool_slots = pool_slots;
     L.step_cap = step_cap; L.threads = threads; L.Lpad = Lpad; L.word_bytes = word_bytes;
     L.band_strips = band_strips;
     const bool packed = band_strips > 0;
+    L.W2 = packed ? W2 : 0; L.band_strips2 = L.W2 ? band_strips2 : 0;
     const size_t C = (size_t)nodes_cap + 4, S = (size_t)std::max(nodes_cap, Lpad) + 4, Rr = (size_t)rows_cap + 4;
     L.scratch_len = (int)S;
     size_t cur = 0;
@@ -71,7 +79,9 @@ inline SlotLayout make_layout(int nodes_cap, int rows_cap, int pool_slots, int s
     L.r_preds = lay(cur, 4 * C); L.r_slot = lay(cur, 4 * Rr); L.r_tbx = lay(cur, 4 * Rr);
     L.r_sseq = lay(cur, 4 * Rr); L.r_row_node = lay(cur, 4 * Rr); L.r_meta = lay(cur, 32 * Rr);
     // traceback plane: one byte per cell, or (packed sweep) one dword per cell of the row's band of strips
-    L.tb = lay(cur, ((size_t)rows_cap + 1) * (packed ? (size_t)band_strips * (size_t)p16_slot_dwords(Lpad / (2 * threads), cell_bytes) * 4 : (size_t)Lpad));
+    size_t plane_row = packed ? (size_t)band_strips * (size_t)p16_slot_dwords(Lpad / (2 * threads), cell_bytes) * 4 : (size_t)Lpad;
+    if (L.W2) plane_row = std::max(plane_row, (size_t)L.band_strips2 * (size_t)p16_slot_dwords(L.W2, cell_bytes) * 4);
+    L.tb = lay(cur, ((size_t)rows_cap + 1) * plane_row);
     L.steps = lay(cur, packed ? 256 : (size_t)std::max(step_cap, 1) * 3 * threads * 4);
     // (a stored row of the packed sweep ends with one more word per lane: the column left of the lane's strips; its 2-byte
     //  classes store 2 bytes per column, dp16_row_bytes)
@@ -83,6 +93,48 @@ inline SlotLayout make_layout(int nodes_cap, int rows_cap, int pool_slots, int s
     if (pairs) { L.pair_row = lay(cur, 4 * (Rr + Lpad)); L.pair_pos = lay(cur, 4 * (Rr + Lpad)); }
     L.total = cur;
     return L;
+}
+
+// On-chip copies of stored rows a packed-sweep workgroup gets (SlotLayout::lds_rows): what is left of its share of the CU's
+// 160 KB of LDS when as many workgroups share the CU as its registers allow (128 VGPRs: 16 waves per CU).
+// (Round 4: giving the workgroups of a launch that does not fill the chip -- 1000 two-wave blocks: four per CU where eight
+//  fit -- the LDS the absent ones leave, i.e. 8 on-chip rows instead of 2-3, was measured on c2: 59.6 ms against 57.4 ms.  Dropped.)
+inline int p16_lds_rows(const int T, const int W, const int CB) {
+    if (const char* e = getenv("SXG_POA_LDS_ROWS")) return std::max(0, std::min(8, atoi(e)));
+    const int wg_per_cu = std::max(1, 16 / std::max(T / 64, 1));
+    const int share = (160 * 1024) / wg_per_cu - 512;   // (allocation granularity)
+    const int rows = (share - dp16_lds_bytes(T, W, 0, CB)) / dp16_row_bytes(T, W, CB);
+    return std::max(0, std::min(8, rows));
+}
+
+// strips per plane row of the packed sweep: ~1100 columns around the backbone hint (SXG_POA_BAND_COLS narrows it -- a test
+// knob that makes tracebacks miss their band, so that the in-kernel hint shift and the wide-plane re-run are exercised)
+inline int plane_strips_p16(int T, int W) {
+    if (const char* e = getenv("SXG_POA_BAND_COLS")) {
+        const int cols = std::max(atoi(e), W);
+        return std::min(plane_round4((cols + W - 1) / W), 2 * T);
+    }
+    return p16_band_strips(T, W);
+}
+
+// SXG_POA_WIDTH2=0: no launch uses its class's second strip width
+inline bool width2_enabled() {
+    const char* e = getenv("SXG_POA_WIDTH2");
+    return !(e && atoi(e) == 0);
+}
+
+// What the host gives a packed launch of T threads with strips of W columns and the second width W2 (0: none): strips per plane
+// row at either width (wide_band: the every-strip plane of a band-miss re-run), the on-chip row copies -- the count of the
+// geometry's own width, whose rows are the longer: the second width's fit as well -- and the dynamic LDS, the larger of the two
+// layouts.  (prepare_plan in sxg_poa.hip; tests/csrc/width2_check.cpp checks it against what a sweep at either width needs.)
+struct P16LaunchSizes { int strips, strips2, lds_rows, smem; };
+inline P16LaunchSizes p16_launch_sizes(int T, int W, int W2, int CB, bool wide_band) {
+    P16LaunchSizes s;
+    s.strips = wide_band ? 2 * T : plane_strips_p16(T, W);
+    s.strips2 = W2 ? (wide_band ? 2 * T : plane_strips_p16(T, W2)) : 0;
+    s.lds_rows = p16_lds_rows(T, W, CB);
+    s.smem = std::max(dp16_lds_bytes(T, W, s.lds_rows, CB), W2 ? dp16_lds_bytes(T, W2, s.lds_rows, CB) : 0);
+    return s;
 }
 
 struct SlotViews {
@@ -172,8 +224,11 @@ __host__ __device__ constexpr int sxg_min_waves(int TMAX, int W, int RM) { retur
 
 // CB: bytes per cell of the packed sweep's traceback plane (poa_dp16.hip.h: 2 = delta codes, 4 = H and the two distances)
 // DS: packed sweep compiled for smoothxg's default scores (see dp_fill_p16); the host launches it only for blocks that have them
-template <int TMAX, int W, bool CVX, int RM, bool SW, int CB = 4, bool DS = false>
+// W2: the class's second strip width (0 = none), for the alignments whose sequence it covers -- see the packed sweep below;
+// the launch says in lay.W2 whether it is used (0, or W2)
+template <int TMAX, int W, bool CVX, int RM, bool SW, int CB = 4, bool DS = false, int W2 = 0>
 __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_kernel(const BlockArgs A) {
+    static_assert(W2 == 0 || (RM == 2 && W2 < W), "a second strip width: packed sweep, narrower than the first");
     constexpr bool H16 = RM != 1;
     constexpr int CPL = RM >= 2 ? 2 * W : W;  // columns per lane
     constexpr ClassTraits CT = class_traits(TMAX, W, RM, CB);
@@ -214,7 +269,7 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
         }
         unsigned long long tc0 = clock64(), tc1;
         const unsigned long long tblk0 = tc0;
-        int band_drift = 0, band_min = 0;   // packed sweep, adaptive band: largest drift of the block's walks, least width after a repeat
+        int band_drift = 0, band_min = 0;   // packed sweep, adaptive band: largest drift of the block's walks, least width after a repeat (both in columns)
 #define PROF(k) do { if (t == 0) { tc1 = clock64(); prof[k] += tc1 - tc0; tc0 = tc1; } } while (0)
         for (int s = s0; s < s1 && status == ST_OK; ++s) {
             const int64_t so = A.seq_off[s];
@@ -224,7 +279,7 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
             __syncthreads();
             const int N = *V.G.n_nodes;
             int score = 0;
-            if (RM != 3 && len + 1 > T * CPL) { status = ST_TOO_LONG; break; }
+            if (RM != 3 && len + 1 > T * CPL) { status = ST_TOO_LONG; break; }   // (against W, whatever the second width)
             if (N + len > A.lay.nodes_cap || *V.G.n_edges + len > A.lay.nodes_cap) { status = ST_NODES_OVERFLOW; break; }
             // (the packed full-matrix sweep clamps instead and lets the traceback decide: see P16_NWFLOOR)
             if (RM != 1 && RM != 2 && !S.sw &&
@@ -271,49 +326,75 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                     // strips, the later ones as many as the largest drift of the block's earlier walks asks for, and
                     // after a repeat at least twice the width that missed.  A plane that keeps every strip is not
                     // narrowed (ring_plane classes read stored rows back from it).
-                    const int bs_cap = A.lay.band_strips;
-                    int bs = bs_cap;
-                    if (A.band_floor > 0 && bs_cap < 2 * T && s - s0 > A.band_full)
-                        bs = max(p16_drift_strips(band_drift, A.band_margin, W, A.band_floor, bs_cap), band_min);
-                    for (int att = 0;; ++att) {
-                        V.B.band_strips = bs;
-                        if (t == 0) { prof[47] += (unsigned long long)bs; prof[48] += 1; }
+                    // The strip width follows the ALIGNMENT (round 12): a class with a second width W2 (class_w2, poa_classes.h)
+                    // sweeps a sequence that fits T * 2 * W2 columns in strips of W2 -- every row of a sweep costs all the columns
+                    // of its geometry, and a block's later, costlier alignments are its shorter sequences.  Sweep and traceback of
+                    // one alignment share the width (the end strip and the plane's layout are in strips of it), and so does a
+                    // repeat.  Everything counted in strips takes it: the layout's band (band_strips / band_strips2), the adaptive
+                    // band, the doubling after a repeat (band_floor: see below); band_drift and band_min are columns.  Nothing else depends on it:
+                    // prep_rows / finish_rows and the row descriptors (hints are columns, on-chip slot numbers are stored-row
+                    // numbers mod lds_rows, one count for both widths), add_alignment and spoa_resort never see a strip, and
+                    // dp_fill_p16 lays out its LDS (mailboxes, row copies, letters) and its rows in HBM from its own W on every
+                    // call -- a stored row lives inside one sweep.
+                    auto sweep = [&](auto wk_) {
+                        constexpr int Wk = decltype(wk_)::value;
+                        constexpr int narrow = Wk != W ? 1 : 0;
+                        const int bs_cap = narrow ? A.lay.band_strips2 : A.lay.band_strips;
+                        int bs = bs_cap;
+                        // (band_floor stays a count of STRIPS at either width, deliberately: 48 strips are 528 columns at W = 11 and
+                        //  480 at W2 = 10 -- the floor the W = 10 class, where it was measured as well, has always run with; it bounds
+                        //  speed, not results: a walk that leaves the band is repeated)
+                        if (A.band_floor > 0 && bs_cap < 2 * T && s - s0 > A.band_full)
+                            bs = max(p16_drift_strips(band_drift, A.band_margin, Wk, A.band_floor, bs_cap), min(plane_round4((band_min + Wk - 1) / Wk), bs_cap));
+                        for (int att = 0;; ++att) {
+                            V.B.band_strips = bs;
+                            if (t == 0) {
+                                prof[47] += (unsigned long long)bs; prof[48] += 1;
+                                prof[49 + narrow] += 1; prof[51 + narrow] += (unsigned long long)(T * 2 * Wk); prof[53 + narrow] += (unsigned long long)N * (unsigned long long)(T * 2 * Wk);
+                            }
 #ifdef SXG_EXP
-                        // (development: a sweep with parts switched off in front of the real one -- see dp_fill_p16's EXP)
-                        if (att == 0) { res = dp_fill_p16<W, CVX, SW, CB, CT.rp, CT.tfix, DS, SXG_EXP>(S, V.R, N, seq, len, V.B, smem); __syncthreads(); if (res.best == 0x7fffffff) break; }
+                            // (development: a sweep with parts switched off in front of the real one -- see dp_fill_p16's EXP)
+                            if (att == 0) { res = dp_fill_p16<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS, SXG_EXP>(S, V.R, N, seq, len, V.B, smem); __syncthreads(); if (res.best == 0x7fffffff) break; }
 #endif
-                        res = dp_fill_p16<W, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
-                        __syncthreads();
-                        PROF(2);
-                        if (t == 0) { lds[TBM_FLAG] = 0; lds[TBM_RANGE] = 0; }
-                        __syncthreads();
-                        if (t < 64 && res.bi >= 0)
-                            traceback_p16<false, W, CVX, false, CB>(V.R, V.B, S, seq, len, res.best, T, min(256, (len << 8) / max(N, 1)), res.bi, res.bj,
-                                                                    V.G.posnode, nullptr, nullptr, smem);
-                        __syncthreads();
-                        PROF(3);
-                        if (lds[TBM_RANGE]) { status = ST_RANGE_OVERFLOW; break; }
-                        if (!lds[TBM_FLAG]) break;
-                        if (att == 5) { status = ST_BAND_MISS; break; }
-                        const int mrow = lds[TBM_ROW], mdelta = lds[TBM_DELTA];
-                        __syncthreads();
-                        for (int r2 = t; r2 < mrow; r2 += T) V.R.meta[8 * (size_t)r2 + 7] += mdelta;
-                        for (int i2 = t; i2 < len; i2 += T) V.G.posnode[i2] = -1;
-                        if (t == 0) prof[27] += 1;
-                        band_min = bs = min(plane_round4(2 * bs), bs_cap);
-                        __syncthreads();
-                    }
-                    if (status != ST_OK) break;
-                    // drift of this walk: |DP column - backbone hint| of every aligned letter (column j + 1 aligns to
-                    // node posnode[j], whose row's hint is its xpos)
-                    if (A.band_floor > 0 && bs_cap < 2 * T) {
-                        int d = 0;
-                        for (int j2 = t; j2 < len; j2 += T) {
-                            const int v = V.G.posnode[j2];
-                            if (v >= 0) d = max(d, abs(j2 + 1 - V.G.xpos[v]));
+                            res = dp_fill_p16<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
+                            __syncthreads();
+                            PROF(2);
+                            if (t == 0) { lds[TBM_FLAG] = 0; lds[TBM_RANGE] = 0; }
+                            __syncthreads();
+                            if (t < 64 && res.bi >= 0)
+                                traceback_p16<false, Wk, CVX, false, CB>(V.R, V.B, S, seq, len, res.best, T, min(256, (len << 8) / max(N, 1)), res.bi, res.bj,
+                                                                         V.G.posnode, nullptr, nullptr, smem);
+                            __syncthreads();
+                            PROF(3);
+                            if (lds[TBM_RANGE]) { status = ST_RANGE_OVERFLOW; break; }
+                            if (!lds[TBM_FLAG]) break;
+                            if (att == 5) { status = ST_BAND_MISS; break; }
+                            const int mrow = lds[TBM_ROW], mdelta = lds[TBM_DELTA];
+                            __syncthreads();
+                            for (int r2 = t; r2 < mrow; r2 += T) V.R.meta[8 * (size_t)r2 + 7] += mdelta;
+                            for (int i2 = t; i2 < len; i2 += T) V.G.posnode[i2] = -1;
+                            if (t == 0) prof[27] += 1;
+                            bs = min(plane_round4(2 * bs), bs_cap);
+                            band_min = bs * Wk;
+                            __syncthreads();
                         }
-                        band_drift = max(band_drift, ctx.reduce_max(d));
-                    }
+                        if (status != ST_OK) return;
+                        // drift of this walk: |DP column - backbone hint| of every aligned letter (column j + 1 aligns to
+                        // node posnode[j], whose row's hint is its xpos)
+                        if (A.band_floor > 0 && bs_cap < 2 * T) {
+                            int d = 0;
+                            for (int j2 = t; j2 < len; j2 += T) {
+                                const int v = V.G.posnode[j2];
+                                if (v >= 0) d = max(d, abs(j2 + 1 - V.G.xpos[v]));
+                            }
+                            band_drift = max(band_drift, ctx.reduce_max(d));
+                        }
+                    };
+                    if constexpr (W2 != 0) {
+                        if (width_for_len(W, A.lay.W2, T, len) != W) sweep(std::integral_constant<int, W2>{});
+                        else sweep(std::integral_constant<int, W>{});
+                    } else sweep(std::integral_constant<int, W>{});
+                    if (status != ST_OK) break;
                 } else {
                     dp_fill<W, CVX, H16, SW>(S, V.R, N, seq, len, V.B, smem, A.park_in_lds != 0, A.pf_off, res);
                     __syncthreads();

@@ -118,6 +118,8 @@ struct RowsView {
 
 // What the DP needs to start a row, gathered into 32 bytes so the sweep reads it from an
 // LDS-staged chunk instead of chasing four dependent global loads per row.
+// (Nothing here is counted in strips: rows, pool slots, and the band hint, which is a COLUMN -- a packed sweep of either of a
+//  class's two strip widths reads the same descriptors.)
 struct RowMeta {
     int pb;        // offset of the predecessor list in RowsView::preds
     int info;      // np | code << 16 | flags << 24

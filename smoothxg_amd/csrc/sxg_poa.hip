@@ -149,18 +149,6 @@ static int fail(int code, const std::string& msg) {
                         std::string(#x) + ": " + hipGetErrorString(_e));                       \
     } while (0)
 
-// On-chip copies of stored rows a packed-sweep workgroup gets (SlotLayout::lds_rows): what is left of its share of the CU's
-// 160 KB of LDS when as many workgroups share the CU as its registers allow (128 VGPRs: 16 waves per CU).
-// (Round 4: giving the workgroups of a launch that does not fill the chip -- 1000 two-wave blocks: four per CU where eight
-//  fit -- the LDS the absent ones leave, i.e. 8 on-chip rows instead of 2-3, was measured on c2: 59.6 ms against 57.4 ms.  Dropped.)
-static int p16_lds_rows(const int T, const int W, const int CB) {
-    if (const char* e = getenv("SXG_POA_LDS_ROWS")) return std::max(0, std::min(8, atoi(e)));
-    const int wg_per_cu = std::max(1, 16 / std::max(T / 64, 1));
-    const int share = (160 * 1024) / wg_per_cu - 512;   // (allocation granularity)
-    const int rows = (share - dp16_lds_bytes(T, W, 0, CB)) / dp16_row_bytes(T, W, CB);
-    return std::max(0, std::min(8, rows));
-}
-
 // Plane cell format of the packed sweep for a score set: 2-byte codes when the three fields fit 16 bits (poa_rowcode.h:
 // the stored rows' code, field widths of P16Delta), the 4-byte cells of rounds 2-4 otherwise.  SXG_POA_CELL_BYTES=4 forces the latter (A/B runs, tests).
 static int plane_cell_bytes(const Scoring& S) {
@@ -339,6 +327,7 @@ struct sxg_poa_handle {
     std::vector<int64_t> bg_node_o, bg_edge_o;
     std::vector<int32_t> bg_counts;
     sxg_poa_stats stats{};
+    sxg_poa_width_stats wstats{};   // packed sweeps of the last execute per strip width (sxg_poa_get_width_stats)
     // multi-GPU (sxg_poa_batch_run_sharded): communicator of this rank, result blob of the local shard, and -- on the
     // root -- the blobs of the other ranks, delivered by RCCL
     ncclComm_t comm = nullptr;
@@ -503,6 +492,12 @@ extern "C" int sxg_poa_get_stats(sxg_poa_handle* h, sxg_poa_stats* out) {
     return SXG_OK;
 }
 
+extern "C" int sxg_poa_get_width_stats(sxg_poa_handle* h, sxg_poa_width_stats* out) {
+    if (!h || !out) return fail(SXG_E_INVALID, "NULL argument");
+    *out = h->wstats;
+    return SXG_OK;
+}
+
 static uint64_t arena_budget(sxg_poa_handle* h) {
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 8ull << 30;
@@ -636,16 +631,6 @@ struct LaunchPlan {
     int smem = 0, pf_off = -1; bool park_lds = true; uint64_t cells = 0, bytes = 0; float ms = 0;
 };
 
-// strips per plane row of the packed sweep: ~1100 columns around the backbone hint (SXG_POA_BAND_COLS narrows it -- a test
-// knob that makes tracebacks miss their band, so that the in-kernel hint shift and the wide-plane re-run are exercised)
-static int plane_strips_p16(int T, int W) {
-    if (const char* e = getenv("SXG_POA_BAND_COLS")) {
-        const int cols = std::max(atoi(e), W);
-        return std::min(plane_round4((cols + W - 1) / W), 2 * T);
-    }
-    return p16_band_strips(T, W);
-}
-
 // Adaptive band of the packed sweep (BlockArgs::band_floor): the later alignments of a block keep
 // 2 (ceil((drift + margin) / W) + 1) strips per plane row, at least `floor`, at most the layout's.  SXG_POA_BAND_ADAPT =
 // "floor,margin,full" sets the three (full: alignments of a block that keep the layout's width); "0" keeps the layout's width
@@ -702,19 +687,24 @@ static void prepare_plan(sxg_poa_handle* h, LaunchPlan& P, int attempt) {
     if (rows_cap >= (1 << 20)) rows_cap = (1 << 20) - 1;
     const int wb = V.RM == 1 ? 8 : 4;
     if (V.RM == 3) pool_slots = 1;   // (the banded sweep has no row ring: predecessors come from the plane)
-    P.lay = make_layout(nodes_cap, rows_cap, pool_slots, step_cap, V.T(), Lpad, wb, false,
-                        V.RM == 3 ? (any_adaptive ? BAND_WIN : band_plane_strips(maxlen, V.W)) : (V.RM == 2 ? (P.wide_band ? 2 * V.T() : plane_strips_p16(V.T(), V.W)) : 0),
-                        V.RM >= 2 ? V.CB : 4, any_spoa);
     // (a class compiled for a plane that keeps every strip -- class_traits' rp == 2 -- gives way when the launch's plane was narrowed,
     //  SXG_POA_BAND_COLS: class_tmax)
-    P.variant.TMAX = class_tmax(V.W, V.NW, V.RM, V.CB, P.lay.band_strips == 2 * V.T());
+    const int strips1 = V.RM == 3 ? (any_adaptive ? BAND_WIN : band_plane_strips(maxlen, V.W)) : (V.RM == 2 ? p16_launch_sizes(V.T(), V.W, 0, V.CB, P.wide_band).strips : 0);
+    P.variant.TMAX = class_tmax(V.W, V.NW, V.RM, V.CB, strips1 == 2 * V.T());
+    // The class's second strip width, for the alignments it covers (poa_kernels.hip.h).  SXG_POA_WIDTH2=0: every alignment runs at
+    // the geometry's width -- the A/B inside one build, and a test knob: the width changes speed, never results.
+    P.variant.W2 = width2_enabled() ? class_w2(CLASS_BLOCK, P.variant, P.sw) : 0;
+    // strips per plane row at either width, on-chip rows and dynamic LDS of a packed launch: p16_launch_sizes
+    const P16LaunchSizes LS = p16_launch_sizes(V.T(), V.W, P.variant.W2, V.CB, P.wide_band);
+    P.lay = make_layout(nodes_cap, rows_cap, pool_slots, step_cap, V.T(), Lpad, wb, false, strips1, V.RM >= 2 ? V.CB : 4, any_spoa,
+                        V.RM == 2 ? P.variant.W2 : 0, LS.strips2);
     P.kern = block_kernel(P.variant, P.cvx, P.sw);
     const int tfix = class_traits(P.variant.TMAX, V.W, V.RM, V.CB).tfix;
     if (tfix && tfix != V.T()) { P.kern = nullptr; P.why = "kernel class compiled for " + std::to_string(tfix) + " threads asked to run at " + std::to_string(V.T()); }
     if (!P.kern && P.why.empty()) P.why = "no kernel class built for this geometry";   // (launch_plan fails this launch)
     P.smem = dp_lds_launch_bytes(Lpad, wb);
     P.park_lds = dp_park_in_lds(Lpad, wb);
-    if (V.RM == 2) { P.lay.lds_rows = p16_lds_rows(V.T(), V.W, V.CB); P.smem = dp16_lds_bytes(V.T(), V.W, P.lay.lds_rows, V.CB); P.park_lds = true; }
+    if (V.RM == 2) { P.lay.lds_rows = LS.lds_rows; P.smem = LS.smem; P.park_lds = true; }
     if (V.RM == 3) { P.smem = band_lds_bytes(V.W); P.park_lds = true; }
     P.pf_off = (V.RM < 2 && getenv("SXG_POA_PREFETCH")) ? dp_pf_offset(Lpad, wb, V.T()) : -1;
     if (P.pf_off >= 0) P.smem += dp_pf_bytes(Lpad, wb, V.T());
@@ -810,6 +800,21 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     return SXG_OK;
 }
 
+// Packed sweep: what the launch's sweeps ran at, from the slot headers (words 27 and 49..54 of the counters the kernel keeps
+// there -- poa_kernels.hip.h), gathered with one strided copy.
+static int width_stats_of(const LaunchPlan& P, const PlanRes& R, sxg_poa_width_stats& w) {
+    if (P.variant.RM != 2 || P.n_slots <= 0) return SXG_OK;
+    constexpr int K0 = 27, K1 = 55;
+    std::vector<unsigned long long> v((size_t)P.n_slots * (K1 - K0));
+    HIPCHK(hipMemcpy2D(v.data(), (K1 - K0) * 8, R.arena.as<uint8_t>() + P.lay.hdr + 64 + K0 * 8, P.lay.total, (K1 - K0) * 8, (size_t)P.n_slots, hipMemcpyDeviceToHost));
+    for (int64_t sl = 0; sl < P.n_slots; ++sl) {
+        const unsigned long long* c = v.data() + (size_t)sl * (K1 - K0);
+        w.hint_shift_repeats += c[27 - K0];
+        for (int k = 0; k < 2; ++k) { w.sweeps[k] += c[49 + k - K0]; w.swept_cols[k] += c[51 + k - K0]; w.swept_cells[k] += c[53 + k - K0]; }
+    }
+    return SXG_OK;
+}
+
 static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt) {
     const Variant V = P.variant;
     unsigned long long acc[8] = {0}, smin = ~0ull, smax = 0;
@@ -830,6 +835,11 @@ static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt)
         }
         fprintf(stderr, "[sxg]   band: %llu sweeps, mean width %.1f strips of %d (%.0f columns), %llu hint-shift repeats\n", nsw,
                 (double)wsum / (double)std::max(nsw, 1ull), P.lay.band_strips, (double)wsum / (double)std::max(nsw, 1ull) * V.W, rep);
+        // (with a second width the band line's strips are a mix of both widths' and its columns an upper bound)
+        sxg_poa_width_stats w{};
+        if (int rcw = width_stats_of(P, R, w)) return rcw;
+        fprintf(stderr, "[sxg]   width: W=%d %llu sweeps %llu columns %.4g cells; W2=%d %llu sweeps %llu columns %.4g cells\n", V.W, (unsigned long long)w.sweeps[0],
+                (unsigned long long)w.swept_cols[0], (double)w.swept_cells[0], P.lay.W2, (unsigned long long)w.sweeps[1], (unsigned long long)w.swept_cols[1], (double)w.swept_cells[1]);
     }
     if (const char* path = getenv("SXG_POA_SLOT_CSV")) {  // per-slot placement and wall-clock span
         if (FILE* f = fopen(path, "a")) {
@@ -973,6 +983,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
     HIPCHK(hipSetDevice(h->device));
     const RoctxRange range_("sxg_poa_batch_execute");
     h->stats = sxg_poa_stats{};
+    h->wstats = sxg_poa_width_stats{};
     const bool dbg = getenv("SXG_POA_DEBUG") != nullptr;
     auto T0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
@@ -1025,11 +1036,16 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         // config 2 (three launches of 1-2 waves per block) still lose 15 % apart.  So: wide geometries merge only within 8 %,
         // the others within 25 % as before.
         const double merge_env = getenv("SXG_POA_MERGE") ? atof(getenv("SXG_POA_MERGE")) : 0.0;
+        const bool merge_w2 = getenv("SXG_POA_MERGE_WIDTH2") && atoi(getenv("SXG_POA_MERGE_WIDTH2")) != 0 && width2_enabled();
         for (size_t i = 0; i < plans.size(); ++i)
             for (size_t j = i + 1; j < plans.size();) {
                 const LaunchPlan &a = plans[i], &b = plans[j];
+                // (round 12, SXG_POA_MERGE_WIDTH2=1: a geometry whose strip width IS the second width of a wider one's class at the same
+                //  wave count joins it -- inside that launch its alignments all run at their own width, so the reason above is gone and
+                //  the cost-ordered dealing over CUs sees all blocks.  Off by default: see DESIGN section 5, round 12.)
+                const bool join_w2 = merge_w2 && a.variant.NW == b.variant.NW && b.variant.W == class_w2(CLASS_BLOCK, a.variant, a.sw);
                 if (same_kind(a.variant, b.variant) && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
-                    (double)b.variant.Lpad() >= (merge_env > 0 ? merge_env : (a.variant.Lpad() >= 4096 ? 0.92 : 0.75)) * (double)a.variant.Lpad()) {
+                    (join_w2 || (double)b.variant.Lpad() >= (merge_env > 0 ? merge_env : (a.variant.Lpad() >= 4096 ? 0.92 : 0.75)) * (double)a.variant.Lpad())) {
                     plans[i].work.insert(plans[i].work.end(), b.work.begin(), b.work.end());
                     plans.erase(plans.begin() + (long)j);
                 } else ++j;
@@ -1074,7 +1090,10 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         // running side by side should end together, so their WAVES are made proportional to their
         // work (cost model of SURVEY 8e): slots_p = lambda * cost_p / waves_per_slot_p, with the largest
         // lambda that respects the arena budget and the wave capacity of the device.
-        // (a block swept by a wider geometry than its own -- merged launches -- costs the columns of THAT geometry)
+        // (a block swept by a wider geometry than its own -- merged launches -- costs the columns of THAT geometry.  A launch of a
+        //  dual-width class is priced at its full width as well, which overestimates it: most of its alignments sweep W2, and the
+        //  headline's W = 11 launch now ends ~2 % before the W = 10 launch beside it.  Pricing by the per-alignment width is left
+        //  to a later round -- DESIGN section 5, round 12.)
         std::vector<double> pcost(plans.size(), 0.0);
         for (size_t i = 0; i < plans.size(); ++i)
             for (int b : plans[i].work)
@@ -1153,6 +1172,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
             h->stats.dp_launches += 1;
             h->stats.n_slots += (int)plans[i].n_slots;
             h->stats.device_bytes += (uint64_t)plans[i].n_slots * plans[i].lay.total;
+            if (int rcw = width_stats_of(plans[i], *h->planres[i], h->wstats)) return rcw;
             if (dbg) debug_plan(h, plans[i], *h->planres[i], attempt);
         }
         lap("launches");
@@ -1221,6 +1241,8 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
             h->stats.dom_threads = pl.variant.T(); h->stats.dom_cols_per_lane = pl.variant.W * (pl.variant.RM >= 2 ? 2 : 1);
             h->stats.dom_row_mode = pl.variant.RM;
             h->stats.dom_clock_mhz = pl.clock_mhz;
+            // (dom_cols_per_lane stays the class's W: an upper bound of the columns a dual-width launch's alignments swept)
+            h->wstats.dom_width = pl.variant.W; h->wstats.dom_width2 = pl.lay.W2;
         }
     }
     lap("accounting");

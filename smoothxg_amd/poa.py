@@ -69,6 +69,12 @@ class Stats(C.Structure):
                 ("dom_row_mode", C.c_int32), ("dom_clock_mhz", C.c_int32), ("bg_ms", C.c_double)]
 
 
+class WidthStats(C.Structure):
+    """sxg_poa_width_stats: the packed sweeps of the last execute per strip width ([0] the geometry's, [1] the second width)."""
+    _fields_ = [("sweeps", C.c_uint64 * 2), ("swept_cols", C.c_uint64 * 2), ("swept_cells", C.c_uint64 * 2),
+                ("hint_shift_repeats", C.c_uint64), ("dom_width", C.c_int32), ("dom_width2", C.c_int32)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("n_seqs", C.c_int64), ("n_bases", C.c_int64),
                 ("status", C.c_void_p), ("n_nodes", C.c_void_p), ("n_edges", C.c_void_p),
@@ -110,7 +116,7 @@ ST_TOO_LONG = 5
 EXPORTS = ["sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
-           "sxg_poa_get_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
+           "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
            "sxg_poa_comm_attach", "sxg_poa_comm_destroy", "sxg_poa_batch_run_sharded", "sxg_poa_batch_run_sharded_local",
            "sxg_poa_batch_upload_sharded", "sxg_poa_batch_execute_sharded", "sxg_poa_batch_download_sharded", "sxg_poa_sharded_info",
            "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available"]
@@ -144,6 +150,7 @@ def load_library(build_if_missing=True):
     L.sxg_poa_align_batch.argtypes = [vp, C.POINTER(AlignIn), C.POINTER(AlignOut)]
     L.sxg_poa_align_free.argtypes = [C.POINTER(AlignOut)]
     L.sxg_poa_get_stats.argtypes = [vp, C.POINTER(Stats)]
+    L.sxg_poa_get_width_stats.argtypes = [vp, C.POINTER(WidthStats)]
     L.sxg_poa_set_memory_budget.argtypes = [vp, C.c_uint64]
     L.sxg_poa_measure_copy.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
     L.sxg_poa_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
@@ -285,7 +292,13 @@ class PoaEngine:
     def stats(self):
         s = Stats()
         self.lib.sxg_poa_get_stats(self.h, C.byref(s))
-        return {f[0]: getattr(s, f[0]) for f in Stats._fields_}
+        st = {f[0]: getattr(s, f[0]) for f in Stats._fields_}
+        # packed sweeps per strip width: "width_*" is a pair (at the geometry's width, at the class's second width)
+        w = WidthStats()
+        self.lib.sxg_poa_get_width_stats(self.h, C.byref(w))
+        st.update(width_sweeps=tuple(w.sweeps), width_swept_cols=tuple(w.swept_cols), width_swept_cells=tuple(w.swept_cells),
+                  hint_shift_repeats=w.hint_shift_repeats, dom_width=w.dom_width, dom_width2=w.dom_width2)
+        return st
 
     def device_view(self):
         """Raw HBM pointers of the executed batch's results (see sxg_poa_device_view)."""
