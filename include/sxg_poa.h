@@ -426,6 +426,46 @@ typedef struct sxg_poa_split_mash {
 int sxg_poa_split_mash_batch(sxg_poa_handle *h, const sxg_poa_split_in *in, const sxg_poa_split_mash *mash,
                              sxg_poa_split_out *out, int64_t *n_mash);
 
+/* The identity estimate of the adaptive scores (-a; A14, src/smooth.cpp:1972-2069) for every block of a batch, decree Q of
+ * DESIGN.md section 9 (an addition to ABI 5).  The estimate itself is include/sxg_smooth.h's (sxg_block_identity_threshold: exact
+ * Jaccard of canonical k-mer sets -> mash distance -> the 30 % percentile of the sorted pair identities, floored at 0.7); this
+ * call computes it without a logarithm and without a float, in exact integers:
+ *   Q1  the sets are M1's (2 bits per letter, 1 <= k <= 32, a window with code 4 contributes nothing), built by the sketch kernel
+ *       of the mash split.  A sequence of block b takes part iff its length is at least min_len (the caller passes 8 * k);
+ *       n_used[b] counts them; the letters arrive coded (0..3, anything else = 4: the caller codes either case of A C G T).
+ *   Q2  for every pair i < j of a block's taking-part sequences: inter = |K_i n K_j|, uni = |K_i| + |K_j| - inter, and the pair's
+ *       key is uni ? ((uint64)inter << 32) / uni : 0.  Sequences are at most SXG_POA_MAX_SEQ_LEN long, so uni < 2^16, two different
+ *       J = inter / uni differ by more than 2^-32, and the key order is exactly the order of J; equal keys mean equal J.
+ *   Q3  with P = n_used (n_used - 1) / 2 and idx = (size_t)((double)(P - 1) * percentile), computed on the host in double, block b
+ *       returns (inter[b], uni[b]) of a pair whose key is the idx-th smallest (0-based) of its P keys.  Which pair among those of
+ *       equal J is unspecified (equal J give the same float); it is the same from run to run.
+ *   Q4  the pair identity f(J) = (float)(1 - (-ln(2J / (1 + J)) / k)) (0 at J = 0) is non-decreasing in J for J > 0, and the pairs
+ *       with f <= 0 -- J = 0, and very small J at small k -- are a lower set in both orders, every one of which ends at the floor;
+ *       so max(0.7f, f(J of the idx-th key)) is max(0.7f, sorted f [idx]), bit for bit.
+ *   Q5  the float is computed once per block, by the host library, from (inter, uni): identity_from_counts of sxg_smooth.cpp, the
+ *       expression its own all-pairs estimator uses.
+ * One workgroup per sequence builds the sets (ONE launch for the batch); one wavefront per pair -- the pairs are enumerated on the
+ * device from per-block prefix sums, the host sends no pair lists -- intersects two sets by the merge-path partition of the mash
+ * split and writes one word (key << 16 | uni); one workgroup per block finds the idx-th smallest word by a radix select over LDS
+ * histograms (no sort; deterministic).  The sets (8 bytes per taking-part base) and the words (8 bytes per pair) come out of the
+ * handle's memory budget: blocks run in rounds, in order, as many as their words fit beside the sets; sets that do not fit, or a
+ * single block whose words do not, are SXG_E_NOMEM (a block of the depth cap, 1000 ranges, needs 4 MB of words).
+ * SXG_E_INVALID: kmer_size outside 1..32, min_len < kmer_size, a percentile outside [0, 1], more than 65536 taking-part
+ * sequences in a block.  A block with a taking-part sequence longer than SXG_POA_MAX_SEQ_LEN gets SXG_ST_TOO_LONG (inter = uni =
+ * 0) and the call returns SXG_E_BLOCK, the other blocks being valid.  Empty blocks and blocks with n_used <= 1 are SXG_ST_OK with
+ * inter = uni = 0.  The call runs inside a ROCTx range; sxg_poa_stats after it: kernel_ms the sum of the kernels, dp_launches
+ * their number (1 + 2 per round), n_slots the wavefronts of the widest pairs launch, device_bytes the sets, the sort scratch and
+ * the words. */
+typedef struct sxg_poa_identity_in {
+    int32_t n_blocks; const int32_t *blk_off; const int64_t *seq_off; const uint8_t *bases; /* codes 0..3, 4 = other */
+    int32_t kmer_size;   /* 1..32 */
+    int32_t min_len;     /* shorter sequences take no part (the caller passes 8 * k); >= kmer_size */
+    double percentile;   /* 0.30 */
+} sxg_poa_identity_in;
+/* caller-allocated [n_blocks] each */
+int sxg_poa_block_identity_batch(sxg_poa_handle *h, const sxg_poa_identity_in *in,
+                                 int32_t *n_used, int32_t *inter, int32_t *uni, int32_t *status);
+
 /* The node order of prep (src/prep.cpp:11-163: odgi's path_linear_sgd_order, called from src/main.cpp:423-433 before every
  * iteration unless -n), decree Y of DESIGN.md section 9.  odgi is absent from the snapshot and its hogwild updates are not
  * reproducible, so the order is fixed by decree, bit for bit:

@@ -190,6 +190,22 @@ void sxg_adaptive_poa_scores(float est_identity_threshold, const int32_t set_sco
 int sxg_block_identity_threshold(const sxg_graph *g, const sxg_blockset *b, int64_t block_id, int32_t kmer_size,
                                  float *est_identity_threshold, int32_t *n_used);
 
+/* A14 for every block at once, and the identity provider (an addition to ABI 2, no struct changed).
+ * Identity provider: exactly sxg_poa_block_identity_batch's contract (decree Q of include/sxg_poa.h: the all-pairs Jaccard
+ * estimate in exact integers, one (inter, uni) per block), ctx is its handle.  This library cannot run a device estimator
+ * by itself, as it cannot align; without a provider it runs the estimator above on the host cores.
+ * sxg_blockset_identity_thresholds: thr / n_used [sxg_blockset_size(b)], caller-allocated.  A block with at most one range or
+ * with more than max_depth ranges (-Y, max_block_depth_for_padding_more: src/smooth.cpp:1982) is not estimated and reports
+ * n_used = 0, thr = 0; thr is defined where n_used > 1.  ident == NULL: sxg_block_identity_threshold's estimator, block by
+ * block over the host threads.  Otherwise the estimated blocks' range sequences (step orientation, unpadded, not dedup'd, coded
+ * here: either case of A C G T is a letter, anything else is code 4) go to the provider in ONE call with min_len = 8 * kmer_size
+ * and percentile = 0.30, and thr = max(0.7f, identity(inter, uni, k)) -- the host estimator's value bit for bit (decree Q4).
+ * A block the provider reports with a status other than SXG_ST_OK falls back to the host estimator; a provider that returns
+ * anything but SXG_OK / SXG_E_BLOCK, a wrong n_used or counts out of range fails the call. */
+typedef int (*sxg_identity_fn)(void *ctx, const sxg_poa_identity_in *in, int32_t *n_used, int32_t *inter, int32_t *uni, int32_t *status);
+int sxg_blockset_identity_thresholds(const sxg_graph *g, const sxg_blockset *b, int32_t kmer_size, uint64_t max_depth,
+                                     sxg_identity_fn ident, void *ctx, float *est_identity_threshold, int32_t *n_used);
+
 /* A9+A10 for one block given its POA result: the normalised block graph as GFA text. */
 int sxg_block_graph_gfa(const sxg_graph *g, const sxg_blockset *b, int64_t block_id,
                         const sxg_smooth_params *p, sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx,
@@ -215,6 +231,14 @@ int sxg_block_maf(const sxg_graph *g, const sxg_blockset *b, int64_t block_id, c
 int sxg_smooth_gfa(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p,
                    sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, char **out_gfa);
 
+/* The same iteration with an identity provider for -a (ident == NULL: sxg_smooth_gfa itself).  With adaptive_poa_params the
+ * estimates of ALL blocks come from one provider call (sxg_blockset_identity_thresholds' rules), made on the calling thread
+ * BEFORE the chunk pipeline starts: the POA provider runs in a thread of its own, usually on the same engine handle, and the
+ * two are never in flight together.  Without adaptive_poa_params the identity provider is never called. */
+int sxg_smooth_gfa_adaptive(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p,
+                            sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, sxg_identity_fn ident, void *ident_ctx,
+                            char **out_gfa);
+
 /* A13 + 8f-4: the iteration with the in-order MAF consumer of smooth_and_lace (src/smooth.cpp:1600-1919): every
  * block's MAF rows are merged into groups of blocks whose path ranges continue one another (contiguous-path Jaccard
  * >= the threshold, -M / -J), a block that joins a group in the opposite orientation is FLIPPED -- its block graph is
@@ -232,6 +256,11 @@ typedef struct sxg_merge_params {
 void sxg_merge_default_params(sxg_merge_params *mp);
 int sxg_smooth_maf_gfa(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p, const sxg_merge_params *mp,
                        sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, char **out_gfa, char **out_maf, int64_t *n_flipped);
+
+/* sxg_smooth_maf_gfa with an identity provider for -a: see sxg_smooth_gfa_adaptive. */
+int sxg_smooth_maf_gfa_adaptive(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p, const sxg_merge_params *mp,
+                                sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, sxg_identity_fn ident, void *ident_ctx,
+                                char **out_gfa, char **out_maf, int64_t *n_flipped);
 
 /* prep (src/prep.cpp:11-163, called from src/main.cpp:423-433 before every iteration unless -n): the graph is sorted by
  * path-guided SGD and chopped to nodes of at most max_node_length bases, so that block discovery -- a sweep over the nodes in

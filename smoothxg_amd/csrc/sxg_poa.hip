@@ -26,6 +26,7 @@
 #include "poa_kern_tables.hip.h"   // kernel classes by geometry; instantiated in the kern_*.hip translation units
 #include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
+#include "poa_identity.hip.h"      // the identity estimate of -a on those sets: all pairs of a block, the percentile's pair (kern_split.hip)
 #include "poa_sgd.hip.h"           // the path-guided SGD node order of prep: argument struct and launchers (kernels in kern_sgd.hip)
 
 
@@ -2724,6 +2725,143 @@ extern "C" int sxg_poa_kmer_jaccard_batch(sxg_poa_handle* h, int64_t n_seqs, con
     if (kmers && seq_off[n_seqs] > 0) HIPCHK(hipMemcpy(kmers, B.sets.p, 8 * (size_t)seq_off[n_seqs], hipMemcpyDeviceToHost));
     split_stats(h, ms, 0, n_slots, dev_bytes);
     h->stats.dp_launches = n_pairs ? 2 : 1;
+    return SXG_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The identity estimate of the adaptive scores (A14, src/smooth.cpp:1972-2069): decree Q (include/sxg_poa.h).
+// Kernels in poa_identity.hip.h / kern_split.hip on the sets of poa_mash.hip.h; here the validation, the sequences that take
+// part (the device sees no others), Q3's ranks, the rounds and the timing.  Memory: the sets (8 bytes per base that takes part
+// + 4 per sequence) and the words of a round (8 bytes per pair) share the handle's budget -- the sort scratch of the sketch is
+// bounded by it on its own, as in the split calls --; blocks go round after round, in order, as many as their words fit; a
+// block whose words alone do not fit, or sets that do not, are SXG_E_NOMEM.  Everything is enqueued on the handle's stream
+// without a host wait in between: the words' buffer is reused by the next round in stream order.
+extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_identity_in* in, int32_t* n_used, int32_t* inter, int32_t* uni,
+                                            int32_t* status) {
+    if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
+    const int nb = in->n_blocks;
+    if (nb < 0 || (nb > 0 && (!in->blk_off || !in->seq_off || !n_used || !inter || !uni || !status))) return fail(SXG_E_INVALID, "block_identity: NULL arrays");
+    const int k = in->kmer_size;
+    if (k < 1 || k > 32) return fail(SXG_E_INVALID, "kmer_size must be in 1..32");
+    if (in->min_len < k) return fail(SXG_E_INVALID, "min_len must be at least kmer_size");
+    if (!(in->percentile >= 0.0 && in->percentile <= 1.0)) return fail(SXG_E_INVALID, "percentile must be in [0, 1]");
+    if (nb > 0 && (in->blk_off[0] != 0 || in->seq_off[0] != 0)) return fail(SXG_E_INVALID, "blk_off[0] and seq_off[0] must be 0");
+    for (int b = 0; b < nb; ++b)
+        if (in->blk_off[b + 1] < in->blk_off[b]) return fail(SXG_E_INVALID, "blk_off not monotone");
+    const int64_t ns_in = nb ? in->blk_off[nb] : 0;
+    for (int64_t s = 0; s < ns_in; ++s)
+        if (in->seq_off[s + 1] < in->seq_off[s]) return fail(SXG_E_INVALID, "seq_off not monotone");
+    if (ns_in > 0 && in->seq_off[ns_in] > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
+    RoctxRange range("sxg_poa_block_identity_batch");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    // the sequences that take part, block after block: the batch the device sees (a block with one of them too long stays out)
+    std::vector<int32_t> blk_off((size_t)nb + 1, 0);
+    std::vector<int64_t> seq_off{0}, pair_off((size_t)nb + 1, 0), idx((size_t)std::max(nb, 1), 0);
+    std::vector<uint8_t> bases;
+    bases.reserve((size_t)(ns_in ? in->seq_off[ns_in] : 0));
+    bool any_failed = false;
+    int64_t max_pairs = 0;
+    for (int b = 0; b < nb; ++b) {
+        n_used[b] = inter[b] = uni[b] = 0;
+        status[b] = SXG_ST_OK;
+        int64_t used = 0;
+        for (int64_t s = in->blk_off[b]; s < in->blk_off[b + 1]; ++s) {
+            const int64_t len = in->seq_off[s + 1] - in->seq_off[s];
+            if (len < in->min_len) continue;
+            ++used;
+            if (len > SXG_POA_MAX_SEQ_LEN) status[b] = SXG_ST_TOO_LONG;
+        }
+        if (used > 65536) return fail(SXG_E_INVALID, "block " + std::to_string(b) + ": more than 65536 sequences take part (pairs must stay below 2^31)");
+        n_used[b] = (int32_t)used;
+        if (status[b] != SXG_ST_OK) { any_failed = true; used = 0; }
+        if (used > 1) {   // (a block with one sequence, or none, has no pair: nothing of it goes to the device)
+            for (int64_t s = in->blk_off[b]; s < in->blk_off[b + 1]; ++s) {
+                const int64_t o = in->seq_off[s], len = in->seq_off[s + 1] - o;
+                if (len < in->min_len) continue;
+                const size_t at = bases.size();
+                bases.resize(at + (size_t)len);
+                for (int64_t x = 0; x < len; ++x) bases[at + (size_t)x] = in->bases[o + x] > 4 ? 4 : in->bases[o + x];
+                seq_off.push_back((int64_t)bases.size());
+            }
+            const int64_t P = used * (used - 1) / 2;
+            pair_off[(size_t)b + 1] = P;
+            idx[(size_t)b] = (int64_t)sxg_identity_idx((uint64_t)P, in->percentile);
+            max_pairs = std::max(max_pairs, P);
+        }
+        blk_off[(size_t)b + 1] = (int32_t)(seq_off.size() - 1);
+    }
+    for (int b = 0; b < nb; ++b) pair_off[(size_t)b + 1] += pair_off[(size_t)b];
+    const int64_t ns = (int64_t)seq_off.size() - 1, nbases = seq_off.back();
+    if (ns > 0) {
+        const uint64_t budget = arena_budget(h);
+        const uint64_t sets_bytes = 8ull * (uint64_t)nbases + 4ull * (uint64_t)ns;
+        if (sets_bytes + 8ull * (uint64_t)max_pairs > budget)
+            return fail(SXG_E_NOMEM, "memory budget too small for the k-mer sets (" + std::to_string(sets_bytes) + " bytes) and the pairs of the deepest block (" +
+                                         std::to_string(8 * max_pairs) + " bytes)");
+        const int64_t words_cap = (int64_t)std::min<uint64_t>((budget - sets_bytes) / 8, 0x7fffffffull);   // (a round's pair index is an int32)
+        // rounds: consecutive blocks while their words fit
+        std::vector<int32_t> round_end;
+        for (int b = 0, b0 = 0; b < nb; ++b) {
+            if (pair_off[(size_t)b + 1] - pair_off[(size_t)b0] > words_cap) { round_end.push_back(b); b0 = b; }
+            if (b + 1 == nb) round_end.push_back(nb);
+        }
+        int64_t round_pairs = 0;
+        for (size_t r = 0, b0 = 0; r < round_end.size(); b0 = (size_t)round_end[r++]) round_pairs = std::max(round_pairs, pair_off[(size_t)round_end[r]] - pair_off[b0]);
+        SplitBufs B;
+        if (int rc = B.seq_off.ensure(8 * (size_t)(ns + 1))) return rc;
+        if (int rc = B.bases.ensure((size_t)nbases + 16)) return rc;
+        HIPCHK(hipMemcpyAsync(B.seq_off.p, seq_off.data(), 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(B.bases.p, bases.data(), (size_t)nbases, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (int rc = split_up(h, B.a, blk_off.data(), (size_t)nb + 1)) return rc;
+        if (int rc = split_up(h, B.b, pair_off.data(), (size_t)nb + 1)) return rc;
+        if (int rc = split_up(h, B.c, idx.data(), (size_t)nb)) return rc;
+        if (int rc = B.d.ensure(4 * (size_t)nb)) return rc;
+        if (int rc = B.e.ensure(4 * (size_t)nb)) return rc;
+        if (int rc = B.f.ensure(8 * (size_t)std::max<int64_t>(round_pairs, 1))) return rc;
+        if (int rc = B.queue.ensure(4 * round_end.size() + 256)) return rc;
+        HIPCHK(hipMemsetAsync(B.d.p, 0, 4 * (size_t)nb, h->stream));
+        HIPCHK(hipMemsetAsync(B.e.p, 0, 4 * (size_t)nb, h->stream));
+        HIPCHK(hipMemsetAsync(B.queue.p, 0, 4 * round_end.size(), h->stream));
+        std::vector<int32_t> work((size_t)ns);   // (min_len >= k: every sequence here has a window)
+        for (int64_t s = 0; s < ns; ++s) work[(size_t)s] = (int32_t)s;
+        size_t dev_bytes = 0;
+        int per_cu = 1;
+        sxg_identity_occupancy(&per_cu);
+        int64_t pair_slots = 0;
+        uint64_t launches = 1;
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        if (int rc = mash_sketch(h, B, ns, seq_off.data(), work, k, false, &dev_bytes)) return rc;   // Q1: M1's sets, one launch
+        for (size_t r = 0, b0 = 0; r < round_end.size(); b0 = (size_t)round_end[r++]) {
+            const int32_t b1 = round_end[r];
+            const int64_t n_pairs = pair_off[(size_t)b1] - pair_off[b0];
+            if (n_pairs == 0) continue;
+            const int64_t n_slots = std::min<int64_t>(n_pairs, (int64_t)std::max(h->num_cu, 1) * per_cu);
+            pair_slots = std::max(pair_slots, n_slots);
+            IdentityPairArgs A;
+            A.blk_off = B.a.as<int32_t>(); A.seq_off = B.seq_off.as<int64_t>(); A.sets = B.sets.as<unsigned long long>(); A.set_size = B.set_size.as<int32_t>();
+            A.pair_off = B.b.as<int64_t>(); A.b0 = (int32_t)b0; A.b1 = b1; A.n_pairs = (int32_t)n_pairs; A.queue = B.queue.as<int32_t>() + r;
+            A.words = B.f.as<unsigned long long>();
+            sxg_identity_launch_pairs(A, (int)n_slots, h->stream);
+            HIPCHK(hipGetLastError());
+            IdentitySelectArgs S;
+            S.pair_off = B.b.as<int64_t>(); S.idx = B.c.as<int64_t>(); S.b0 = (int32_t)b0; S.words = B.f.as<unsigned long long>();
+            S.inter = B.d.as<int32_t>(); S.uni = B.e.as<int32_t>();
+            sxg_identity_launch_select(S, b1 - (int32_t)b0, h->stream);
+            HIPCHK(hipGetLastError());
+            launches += 2;
+        }
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipEventSynchronize(h->ev1));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        HIPCHK(hipMemcpy(inter, B.d.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(uni, B.e.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        split_stats(h, ms, 0, pair_slots, dev_bytes + B.f.cap);
+        h->stats.dp_launches = launches;   // the sketch + (pairs, select) of every round
+    }
+    if (any_failed) return fail(SXG_E_BLOCK, "a block holds a sequence longer than SXG_POA_MAX_SEQ_LEN");
     return SXG_OK;
 }
 

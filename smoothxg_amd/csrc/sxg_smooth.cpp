@@ -720,18 +720,22 @@ std::vector<uint64_t> canonical_kmers(const std::string& s, int k) {
     v.erase(std::unique(v.begin(), v.end()), v.end());
     return v;
 }
-float mash_identity(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b, int k) {
-    size_t i = 0, j = 0, inter = 0;
-    while (i < a.size() && j < b.size()) {
-        if (a[i] < b[j]) ++i; else if (b[j] < a[i]) ++j; else { ++inter; ++i; ++j; }
-    }
-    const size_t uni = a.size() + b.size() - inter;
+// the identity of a pair from the sizes of the intersection and the union of its k-mer sets (decree Q5: the one expression
+// behind both the all-pairs estimator below and the thresholds made from a device estimator's counts)
+float identity_from_counts(uint64_t inter, uint64_t uni, int k) {
     double dist = 1.0;
     if (inter > 0 && uni > 0) {
         const double J = (double)inter / (double)uni;
         dist = -std::log(2.0 * J / (1.0 + J)) / (double)k;
     }
     return (float)(1.0 - dist);
+}
+float mash_identity(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b, int k) {
+    size_t i = 0, j = 0, inter = 0;
+    while (i < a.size() && j < b.size()) {
+        if (a[i] < b[j]) ++i; else if (b[j] < a[i]) ++j; else { ++inter; ++i; ++j; }
+    }
+    return identity_from_counts(inter, a.size() + b.size() - inter, k);
 }
 // returns the number of sequences that took part; *thr is set when that is > 1
 int identity_threshold(const sxg_graph& g, const std::vector<path_range_t>& ranges, int k, float* thr) {
@@ -760,19 +764,90 @@ void adaptive_scores(float thr, const int32_t in[6], int32_t out[6]) {  // :2032
         if ((double)thr >= cut[t]) { pick = tiers[t]; break; }
     for (int x = 0; x < 6; ++x) out[x] = pick[x];
 }
-// the scores block `ranges` is aligned with (set/default, or its adaptive tier)
-sxg_poa_params block_poa_params(const sxg_graph& g, const std::vector<path_range_t>& ranges, const sxg_smooth_params& p) {
+// the scores of a block whose estimate is known: the tier of `thr` when more than one sequence took part
+sxg_poa_params tier_poa_params(const sxg_smooth_params& p, int n_used, float thr) {
     sxg_smooth_params q = p;
-    if (p.adaptive_poa_params && ranges.size() > 1 && ranges.size() <= p.max_block_depth_for_padding_more) {  // :1982
-        float thr = 0;
-        if (identity_threshold(g, ranges, p.kmer_size > 0 ? p.kmer_size : 17, &thr) > 1) {
-            const int32_t in[6] = {p.poa_m, p.poa_n, p.poa_g, p.poa_e, p.poa_q, p.poa_c};
-            int32_t out[6];
-            adaptive_scores(thr, in, out);
-            q.poa_m = out[0]; q.poa_n = out[1]; q.poa_g = out[2]; q.poa_e = out[3]; q.poa_q = out[4]; q.poa_c = out[5];
-        }
+    if (n_used > 1) {
+        const int32_t in[6] = {p.poa_m, p.poa_n, p.poa_g, p.poa_e, p.poa_q, p.poa_c};
+        int32_t out[6];
+        adaptive_scores(thr, in, out);
+        q.poa_m = out[0]; q.poa_n = out[1]; q.poa_g = out[2]; q.poa_e = out[3]; q.poa_q = out[4]; q.poa_c = out[5];
     }
     return poa_params(q);
+}
+// the scores block `ranges` is aligned with (set/default, or its adaptive tier)
+sxg_poa_params block_poa_params(const sxg_graph& g, const std::vector<path_range_t>& ranges, const sxg_smooth_params& p) {
+    float thr = 0;
+    int n_used = 0;
+    if (p.adaptive_poa_params && ranges.size() > 1 && ranges.size() <= p.max_block_depth_for_padding_more)  // :1982
+        n_used = identity_threshold(g, ranges, p.kmer_size > 0 ? p.kmer_size : 17, &thr);
+    return tier_poa_params(p, n_used, thr);
+}
+// A14 for every block at once: thr / n_used [blocks] (n_used = 0 and thr = 0 for a block that is not estimated: at most one
+// range, or more than max_depth).  ident == nullptr: identity_threshold per block, over the OpenMP team.  Otherwise decree Q:
+// the estimated blocks' range sequences go to the provider in ONE call, coded here -- either case of A C G T is a letter,
+// anything else code 4, exactly as canonical_kmers reads them (the inline coder of the iteration's prepare() takes upper case
+// only and codes PADDED, dedup'd sequences: not this batch) --, and the (inter, uni) it returns per block become thresholds
+// through identity_from_counts.  A block the provider reports with a status other than SXG_ST_OK gets the host estimator.
+int identity_table(const sxg_graph& g, const sxg_blockset& b, int k, uint64_t max_depth, sxg_identity_fn ident, void* ctx, float* thr, int32_t* n_used) {
+    const int64_t nb = (int64_t)b.blocks.size();
+    std::vector<int64_t> sent;
+    for (int64_t q = 0; q < nb; ++q) {
+        thr[q] = 0; n_used[q] = 0;
+        if (b.blocks[(size_t)q].size() > 1 && b.blocks[(size_t)q].size() <= max_depth) sent.push_back(q);
+    }
+    std::vector<char> on_host(sent.size(), ident ? 0 : 1);
+    if (ident && !sent.empty()) {
+        if (sent.size() > 0x7fffffffull) return fail(SXG_E_INVALID, "too many blocks for one identity call");
+        const int64_t n = (int64_t)sent.size();
+        std::vector<int32_t> blk_off((size_t)n + 1, 0);
+        for (int64_t q = 0; q < n; ++q) blk_off[(size_t)q + 1] = blk_off[(size_t)q] + (int32_t)b.blocks[(size_t)sent[(size_t)q]].size();
+        const size_t ns = (size_t)blk_off[(size_t)n];
+        std::vector<int64_t> seq_off(ns + 1, 0);
+        for (int64_t q = 0; q < n; ++q) {
+            const auto& ranges = b.blocks[(size_t)sent[(size_t)q]];
+            for (size_t r = 0; r < ranges.size(); ++r)
+                seq_off[(size_t)blk_off[(size_t)q] + r + 1] = (int64_t)(g.pos[ranges[r].path][ranges[r].end] - g.pos[ranges[r].path][ranges[r].begin]);
+        }
+        for (size_t s = 0; s < ns; ++s) seq_off[s + 1] += seq_off[s];
+        uvec<uint8_t> bases;
+        bases.resize((size_t)seq_off[ns]);
+#pragma omp parallel for schedule(dynamic, 1)
+        for (int64_t q = 0; q < n; ++q) {
+            const auto& ranges = b.blocks[(size_t)sent[(size_t)q]];
+            for (size_t r = 0; r < ranges.size(); ++r) {
+                uint8_t* dst = bases.data() + seq_off[(size_t)blk_off[(size_t)q] + r];
+                for (uint64_t st = ranges[r].begin; st < ranges[r].end; ++st)   // :1985-1991, node sequences in step orientation, no padding
+                    for (char ch : g.sequence(g.steps[ranges[r].path][st])) {
+                        uint8_t c;
+                        switch (ch) { case 'A': case 'a': c = 0; break; case 'C': case 'c': c = 1; break;
+                                      case 'G': case 'g': c = 2; break; case 'T': case 't': c = 3; break; default: c = 4; }
+                        *dst++ = c;
+                    }
+            }
+        }
+        uint8_t dummy = 0;
+        sxg_poa_identity_in in;
+        memset(&in, 0, sizeof(in));
+        in.n_blocks = (int32_t)n; in.blk_off = blk_off.data(); in.seq_off = seq_off.data(); in.bases = bases.empty() ? &dummy : bases.data();
+        in.kmer_size = k; in.min_len = 8 * k; in.percentile = 0.30;   // :1995, :2026
+        std::vector<int32_t> used((size_t)n, 0), inter((size_t)n, 0), uni((size_t)n, 0), status((size_t)n, 0);
+        const int rc = ident(ctx, &in, used.data(), inter.data(), uni.data(), status.data());
+        if (rc != SXG_OK && rc != SXG_E_BLOCK) return fail(rc, "identity provider failed");
+        for (int64_t q = 0; q < n; ++q) {
+            if (status[(size_t)q] != SXG_ST_OK) { on_host[(size_t)q] = 1; continue; }
+            int32_t want = 0;
+            for (int32_t s = blk_off[(size_t)q]; s < blk_off[(size_t)q + 1]; ++s) want += seq_off[(size_t)s + 1] - seq_off[(size_t)s] >= in.min_len ? 1 : 0;
+            if (used[(size_t)q] != want || inter[(size_t)q] < 0 || inter[(size_t)q] > uni[(size_t)q] || uni[(size_t)q] > 0xffff)
+                return fail(SXG_E_INVALID, "identity provider returned counts out of range for block " + std::to_string(sent[(size_t)q]));
+            n_used[sent[(size_t)q]] = want;
+            if (want > 1) thr[sent[(size_t)q]] = std::max((float)0.7, identity_from_counts((uint64_t)inter[(size_t)q], (uint64_t)uni[(size_t)q], k));  // :2026
+        }
+    }
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t q = 0; q < (int64_t)sent.size(); ++q)
+        if (on_host[(size_t)q]) n_used[sent[(size_t)q]] = identity_threshold(g, b.blocks[(size_t)sent[(size_t)q]], k, &thr[sent[(size_t)q]]);
+    return SXG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2191,7 +2266,8 @@ static reaper_t g_reaper;
 static void reap(std::function<void()> fn) { g_reaper.run(std::move(fn)); }
 
 static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp,
-                            sxg_poa_run_fn run, sxg_poa_free_fn fre, void* ctx, char** out_gfa, char** out_maf, int64_t* n_flipped) {
+                            sxg_poa_run_fn run, sxg_poa_free_fn fre, void* ctx, sxg_identity_fn ident, void* ident_ctx, char** out_gfa,
+                            char** out_maf, int64_t* n_flipped) {
     if (!g || !b || !p || !run || !out_gfa) return fail(SXG_E_INVALID, "NULL argument");
     if (int prc = check_params(p)) return prc;
     if (out_maf) *out_maf = nullptr;
@@ -2243,6 +2319,17 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
     for (int64_t c = 0; c < nc; ++c) { chunks[(size_t)c].k0 = nb * c / nc; chunks[(size_t)c].k1 = nb * (c + 1) / nc; }
     double t_collect = 0, t_wait = 0, t_graphs = 0;
     auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
+    // A14 with an identity provider: every block's estimate in ONE provider call, on this thread, BEFORE the pipeline starts --
+    // the POA provider runs in a thread of its own on what is usually the same engine handle, and the two must never be in
+    // flight together.  prepare() then reads the tiers from this table.
+    std::vector<float> ident_thr;
+    std::vector<int32_t> ident_used;
+    if (p->adaptive_poa_params && ident && nb > 0) {
+        ident_thr.assign((size_t)nb, 0); ident_used.assign((size_t)nb, 0);
+        if (int irc = identity_table(*g, *b, p->kmer_size > 0 ? p->kmer_size : 17, p->max_block_depth_for_padding_more, ident, ident_ctx,
+                                     ident_thr.data(), ident_used.data())) return irc;
+        lap("identity estimate");
+    }
     // stage 1: A2-A4 for every block of the chunk, in parallel over blocks as the reference's OpenMP loop
     // (src/smooth.cpp:1931, schedule(dynamic,1)) up to :743; the flat batch is filled in place
     auto prepare = [&](chunk_t& C) {
@@ -2289,7 +2376,9 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
         if (p->adaptive_poa_params) {
             C.pps.resize((size_t)n);
 #pragma omp parallel for schedule(dynamic, 1)
-            for (int64_t k = 0; k < n; ++k) C.pps[(size_t)k] = block_poa_params(*g, b->blocks[(size_t)(k0 + k)], *p);
+            for (int64_t k = 0; k < n; ++k)
+                C.pps[(size_t)k] = ident_used.empty() ? block_poa_params(*g, b->blocks[(size_t)(k0 + k)], *p)
+                                                      : tier_poa_params(*p, ident_used[(size_t)(k0 + k)], ident_thr[(size_t)(k0 + k)]);
         }
         if (C.pps.empty()) C.pps.push_back(poa_params(*p));
         memset(&C.in, 0, sizeof(C.in));
@@ -2972,9 +3061,20 @@ template <class F> static int guarded(F f) {
 }
 extern "C" {
 
+int sxg_smooth_gfa_adaptive(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, sxg_poa_run_fn run, sxg_poa_free_fn fre, void* ctx,
+                            sxg_identity_fn ident, void* ident_ctx, char** out_gfa) {
+    return guarded([&] { return smooth_iteration(g, b, p, nullptr, run, fre, ctx, ident, ident_ctx, out_gfa, nullptr, nullptr); });
+}
 int sxg_smooth_gfa(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, sxg_poa_run_fn run, sxg_poa_free_fn fre, void* ctx,
                    char** out_gfa) {
-    return guarded([&] { return smooth_iteration(g, b, p, nullptr, run, fre, ctx, out_gfa, nullptr, nullptr); });
+    return sxg_smooth_gfa_adaptive(g, b, p, run, fre, ctx, nullptr, nullptr, out_gfa);
+}
+
+int sxg_blockset_identity_thresholds(const sxg_graph* g, const sxg_blockset* b, int32_t kmer_size, uint64_t max_depth, sxg_identity_fn ident, void* ctx,
+                                     float* thr, int32_t* n_used) {
+    if (!g || !b || kmer_size < 1 || kmer_size > 32 || (!b->blocks.empty() && (!thr || !n_used))) return fail(SXG_E_INVALID, "bad argument");
+    const OmpTeamGuard team(host_threads());
+    return guarded([&] { return identity_table(*g, *b, kmer_size, max_depth, ident, ctx, thr, n_used); });
 }
 
 void sxg_merge_default_params(sxg_merge_params* mp) {
@@ -2983,10 +3083,15 @@ void sxg_merge_default_params(sxg_merge_params* mp) {
     mp->max_merged_groups_in_memory = 50; mp->maf_header = nullptr;                                  // src/main.cpp:297-298
 }
 
+int sxg_smooth_maf_gfa_adaptive(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
+                                sxg_poa_free_fn fre, void* ctx, sxg_identity_fn ident, void* ident_ctx, char** out_gfa, char** out_maf,
+                                int64_t* n_flipped) {
+    if (!mp || !out_maf) return fail(SXG_E_INVALID, "NULL argument");
+    return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, ident, ident_ctx, out_gfa, out_maf, n_flipped); });
+}
 int sxg_smooth_maf_gfa(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
                        sxg_poa_free_fn fre, void* ctx, char** out_gfa, char** out_maf, int64_t* n_flipped) {
-    if (!mp || !out_maf) return fail(SXG_E_INVALID, "NULL argument");
-    return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, out_gfa, out_maf, n_flipped); });
+    return sxg_smooth_maf_gfa_adaptive(g, b, p, mp, run, fre, ctx, nullptr, nullptr, out_gfa, out_maf, n_flipped);
 }
 
 int sxg_blockset_split(const sxg_graph* g, const sxg_blockset* in, double block_group_identity, double length_ratio_min, uint64_t min_dedup_depth,

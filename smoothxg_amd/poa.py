@@ -100,6 +100,12 @@ class SplitMash(C.Structure):
     _fields_ = [("kmer_size", C.c_int32), ("min_len", _i32p), ("est_identity", C.POINTER(C.c_double))]
 
 
+class IdentityIn(C.Structure):
+    """sxg_poa_identity_in: blocks of coded sequences for the identity estimate of the adaptive scores (decree Q)."""
+    _fields_ = [("n_blocks", C.c_int32), ("blk_off", _i32p), ("seq_off", _i64p), ("bases", _u8p), ("kmer_size", C.c_int32),
+                ("min_len", C.c_int32), ("percentile", C.c_double)]
+
+
 class SgdIn(C.Structure):
     """sxg_poa_sgd_in: the flattened graph, the schedule and the seed of the path-guided SGD node order (decree Y)."""
     _fields_ = [("n_nodes", C.c_int64), ("node_len", _i32p), ("n_paths", C.c_int64), ("path_off", _i64p), ("step_node", _i32p),
@@ -113,7 +119,7 @@ SPLIT_PANEL = 512   # SXG_POA_SPLIT_PANEL: columns of the second sequence a wave
 MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
 ST_TOO_LONG = 5
 
-EXPORTS = ["sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
+EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
            "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
@@ -171,6 +177,7 @@ def load_library(build_if_missing=True):
     L.sxg_poa_kmer_jaccard_batch.argtypes = [vp, C.c_int64, _i64p, _u8p, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint64)]
     L.sxg_poa_split_mash_batch.argtypes = [vp, C.POINTER(SplitIn), C.POINTER(SplitMash), C.POINTER(SplitOut), _i64p]
     L.sxg_poa_split_free.restype = None
+    L.sxg_poa_block_identity_batch.argtypes = [vp, C.POINTER(IdentityIn), _i32p, _i32p, _i32p, _i32p]
     L.sxg_poa_path_sgd_order.argtypes = [vp, C.POINTER(SgdIn), _i32p, _i64p]
     L.sxg_xxh64.restype = C.c_uint64
     L.sxg_xxh64.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64]
@@ -582,6 +589,25 @@ class PoaEngine:
             return [(grp[blk_off[b]:blk_off[b + 1]], int(ng[b]), int(npairs[b]), int(nm[b]), int(st[b])) for b in range(nb)]
         finally:
             self.lib.sxg_poa_split_free(C.byref(out))
+
+    def block_identity(self, blocks, kmer_size=17, min_len=None, percentile=0.30, check=True):
+        """sxg_poa_block_identity_batch (decree Q): the identity estimate of the adaptive scores.  blocks: list of lists of code
+        arrays (a block's path-range sequences, not dedup'd); min_len: None = 8 * kmer_size.  Returns int32 arrays (n_used,
+        inter, uni, status), one entry per block: the sizes of the intersection and the union of the k-mer sets of the pair
+        at the percentile's rank among the block's pairs ordered by Jaccard index."""
+        nb = len(blocks)
+        bases, seq_off = self._flat([x for blk in blocks for x in blk])
+        blk_off = np.zeros(nb + 1, np.int32)
+        if nb:
+            blk_off[1:] = np.cumsum([len(b) for b in blocks])
+        ii = IdentityIn(nb, _p(blk_off, C.c_int32), _p(seq_off, C.c_int64), _p(bases, C.c_uint8), int(kmer_size),
+                        8 * int(kmer_size) if min_len is None else int(min_len), float(percentile))
+        used, inter, uni, st = (np.zeros(max(nb, 1), np.int32) for _ in range(4))
+        rc = self.lib.sxg_poa_block_identity_batch(self.h, C.byref(ii), _p(used, C.c_int32), _p(inter, C.c_int32), _p(uni, C.c_int32),
+                                                   _p(st, C.c_int32))
+        if rc and (check or rc != -4):
+            raise self._err("sxg_poa_block_identity_batch")
+        return used[:nb], inter[:nb], uni[:nb], st[:nb]
 
     # -- the node order of prep (src/prep.cpp:11-163) ----------------------------------------
     def path_sgd_order(self, node_len, path_off, step_node, step_pos, eta, cooling_start, terms_per_iter, seed, mode=0, want_x=True):

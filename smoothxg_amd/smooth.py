@@ -16,6 +16,8 @@ FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.BatchOut))
 SPLIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitOut))
 SPLIT_FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.SplitOut))
 SPLIT_MASH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitMash), C.POINTER(_poa.SplitOut), C.POINTER(C.c_int64))
+IDENT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.IdentityIn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                       C.POINTER(C.c_int32))
 SGD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SgdIn), C.POINTER(C.c_int32), C.POINTER(C.c_int64))
 
 
@@ -34,7 +36,8 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_smooth_gfa", "sxg_adaptive_poa_scores", "sxg_block_identity_threshold",
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
            "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa",
-           "sxg_prep_default_params", "sxg_graph_prep"]
+           "sxg_prep_default_params", "sxg_graph_prep", "sxg_blockset_identity_thresholds", "sxg_smooth_gfa_adaptive",
+           "sxg_smooth_maf_gfa_adaptive"]
 
 
 class PrepParams(C.Structure):
@@ -92,6 +95,10 @@ def load_library():
     L.sxg_merge_default_params.argtypes = [C.POINTER(MergeParams)]
     L.sxg_smooth_maf_gfa.argtypes = [vp, vp, C.POINTER(SmoothParams), C.POINTER(MergeParams), vp, vp, vp, C.POINTER(vp), C.POINTER(vp),
                                      C.POINTER(C.c_int64)]
+    L.sxg_smooth_gfa_adaptive.argtypes = [vp, vp, C.POINTER(SmoothParams), vp, vp, vp, vp, vp, C.POINTER(vp)]
+    L.sxg_smooth_maf_gfa_adaptive.argtypes = [vp, vp, C.POINTER(SmoothParams), C.POINTER(MergeParams), vp, vp, vp, vp, vp, C.POINTER(vp),
+                                              C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.sxg_blockset_identity_thresholds.argtypes = [vp, vp, C.c_int32, C.c_uint64, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     L.sxg_block_maf_rows.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
     L.sxg_block_maf.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
     L.sxg_prep_default_params.restype = None
@@ -150,6 +157,41 @@ def gpu_sorter(engine):
     """(sort, ctx) backed by the GPU engine: sxg_poa_path_sgd_order of libsxgpoa.so and the engine handle -- the sort
     provider of prep_gfa."""
     return C.cast(engine.lib.sxg_poa_path_sgd_order, C.c_void_p), engine.h
+
+
+def gpu_identifier(engine):
+    """(identify, ctx) backed by the GPU engine: sxg_poa_block_identity_batch of libsxgpoa.so and the engine handle -- the
+    identity provider of Smoother.identity_thresholds and of the `identity` keyword of smooth_gfa / smooth_maf_gfa: with
+    adaptive_poa_params every block's identity estimate then runs on the device, in one call, before the POA calls."""
+    return C.cast(engine.lib.sxg_poa_block_identity_batch, C.c_void_p), engine.h
+
+
+def python_identifier(fn):
+    """(identify, ctx) around a Python function fn(blk_off, seq_off, bases, kmer_size, min_len, percentile) -> (n_used,
+    inter, uni, status) or (n_used, inter, uni, status, return code), one entry per block, the arrays being numpy copies of
+    the batch the library coded: for tests and experiments, the production provider is gpu_identifier.  The tuple keeps the
+    callback alive."""
+    import numpy as np
+
+    def view(ptr, n, dtype):
+        return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+
+    def call(ctx, inp, n_used, inter, uni, status):
+        try:
+            a = inp.contents
+            blk_off = view(a.blk_off, a.n_blocks + 1, np.int32) if a.n_blocks else np.zeros(1, np.int32)
+            seq_off = view(a.seq_off, int(blk_off[-1]) + 1, np.int64) if blk_off[-1] else np.zeros(1, np.int64)
+            res = fn(blk_off, seq_off, view(a.bases, int(seq_off[-1]), np.uint8), a.kmer_size, a.min_len, a.percentile)
+            for dst, src in zip((n_used, inter, uni, status), res[:4]):
+                if len(src) != a.n_blocks:
+                    return -1
+                for k in range(a.n_blocks):
+                    dst[k] = int(src[k])
+            return int(res[4]) if len(res) > 4 else 0
+        except Exception:   # (an exception must not cross the C frames)
+            return -1
+    cb = IDENT_FN(call)
+    return C.cast(cb, C.c_void_p), None, cb
 
 
 def python_sorter(fn):
@@ -345,16 +387,34 @@ class Smoother:
         out = C.c_void_p()
         return self._text(self.L.sxg_block_maf(self.g, self.b, block_id, C.byref(params), run, fre, ctx, C.byref(out)), out)
 
-    def smooth_maf_gfa(self, params, provider, merge_blocks=False, jaccard=1.0, preserve_unmerged=False, max_groups=50, header=None):
-        """The iteration with the in-order MAF consumer (block merging, flips): -> (GFA text, MAF text, flipped blocks)."""
+    def identity_thresholds(self, kmer_size=17, identity=None, max_depth=1000):
+        """A14 for every block (sxg_blockset_identity_thresholds): (thresholds as float32, sequences used as int32), one entry
+        per block; a threshold only counts where more than one sequence was used, and a block with at most one range or more
+        than max_depth ranges reports 0 used.  identity: an identity provider (gpu_identifier(engine): ONE call on the device
+        for all blocks); None = the host estimator, block by block over the host threads."""
+        import numpy as np
+        n = self.n_blocks
+        thr, used = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32)
+        ident = identity if identity is not None else (None, None)
+        if self.L.sxg_blockset_identity_thresholds(self.g, self.b, int(kmer_size), int(max_depth), ident[0], ident[1],
+                                                   thr.ctypes.data_as(C.POINTER(C.c_float)), used.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise SmoothError(self.L.sxg_smooth_last_error().decode())
+        return thr[:n], used[:n]
+
+    def smooth_maf_gfa(self, params, provider, merge_blocks=False, jaccard=1.0, preserve_unmerged=False, max_groups=50, header=None,
+                       identity=None):
+        """The iteration with the in-order MAF consumer (block merging, flips): -> (GFA text, MAF text, flipped blocks).
+        identity: as for smooth_gfa."""
         run, fre, ctx = provider
+        ident = identity if identity is not None else (None, None)
         mp = MergeParams()
         self.L.sxg_merge_default_params(C.byref(mp))
         mp.merge_blocks, mp.contiguous_path_jaccard, mp.preserve_unmerged_consensus = int(merge_blocks), jaccard, int(preserve_unmerged)
         mp.max_merged_groups_in_memory = max_groups
         mp.maf_header = header.encode() if header is not None else None
         gfa, maf, nf = C.c_void_p(), C.c_void_p(), C.c_int64()
-        rc = self.L.sxg_smooth_maf_gfa(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, C.byref(gfa), C.byref(maf), C.byref(nf))
+        rc = self.L.sxg_smooth_maf_gfa_adaptive(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, ident[0], ident[1], C.byref(gfa),
+                                                C.byref(maf), C.byref(nf))
         if rc:
             raise SmoothError(self.L.sxg_smooth_last_error().decode())
         try:
@@ -363,11 +423,14 @@ class Smoother:
             self.L.sxg_smooth_free(gfa)
             self.L.sxg_smooth_free(maf)
 
-    def smooth_gfa(self, params, provider):
-        """One smoothing iteration -> GFA text; None on a rank of a multi-GPU provider that does not lace."""
+    def smooth_gfa(self, params, provider, identity=None):
+        """One smoothing iteration -> GFA text; None on a rank of a multi-GPU provider that does not lace.
+        identity: an identity provider for adaptive_poa_params (gpu_identifier(engine): the estimates of all blocks in one
+        device call before the POA calls); None = the host estimator.  Without adaptive_poa_params it is never called."""
         run, fre, ctx = provider
+        ident = identity if identity is not None else (None, None)
         out = C.c_void_p()
-        rc = self.L.sxg_smooth_gfa(self.g, self.b, C.byref(params), run, fre, ctx, C.byref(out))
+        rc = self.L.sxg_smooth_gfa_adaptive(self.g, self.b, C.byref(params), run, fre, ctx, ident[0], ident[1], C.byref(out))
         if rc == 1:   # SXG_NOT_ROOT
             return None
         return self._text(rc, out)
