@@ -337,6 +337,8 @@ int sxg_poa_sharded_timing(sxg_poa_handle *h, double *pack_ms, double *exchange_
 /* Test entry: the same partition / packing / assembly with `nranks` simulated ranks on this one GPU. */
 int sxg_poa_batch_run_sharded_local(sxg_poa_handle *h, const sxg_poa_batch_in *in, int nranks, sxg_poa_batch_out *out);
 
+/* sxg_poa_stats after the call: dp_launches, kernel_ms and n_slots of its launches (one per geometry, gap model and alignment
+ * mode), dom_threads / dom_cols_per_lane / dom_row_mode / dom_kernel_ms of the launch with the most rows x letters. */
 int sxg_poa_align_batch(sxg_poa_handle *h, const sxg_poa_align_in *in, sxg_poa_align_out *out);
 void sxg_poa_align_free(sxg_poa_align_out *out);
 

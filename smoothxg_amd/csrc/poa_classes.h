@@ -72,12 +72,14 @@ constexpr ClassRow kClasses[] = {
     // part 1: the banded one-wave sweep (2-byte band cells: local alignment only), the 32-bit sweeps (int16 and int32 row words)
     {1, CLASS_BLOCK, RM3, 2, 64, cw(6) | cw(8) | cw(11), CLS_LOCAL},
     {1, CLASS_BLOCK, RM3, 4, 64, cw(6) | cw(8) | cw(11), CLS_BOTH},
+    // (no 8-column class of 8 or 16 waves: 8 x 8, 12 x 8 and 16 x 8 waves-by-columns tie with 4 x 16, 8 x 12 and 8 x 16, and the
+    //  wider strip wins -- variant_for_len never returns them for a 32-bit sweep, which has no forced geometry either)
     {1, CLASS_BLOCK, RM01, 4, 256, cw(8) | cw(12) | cw(16), CLS_BOTH},
-    {1, CLASS_BLOCK, RM01, 4, 512, cw(8) | cw(12) | cw(16), CLS_BOTH},
-    {1, CLASS_BLOCK, RM01, 4, 1024, cw(8) | cw(12), CLS_BOTH},
+    {1, CLASS_BLOCK, RM01, 4, 512, cw(12) | cw(16), CLS_BOTH},
+    {1, CLASS_BLOCK, RM01, 4, 1024, cw(12), CLS_BOTH},
     {1, CLASS_ALIGN, RM01, 4, 256, cw(8) | cw(12) | cw(16), CLS_BOTH},
-    {1, CLASS_ALIGN, RM01, 4, 512, cw(8) | cw(12) | cw(16), CLS_BOTH},
-    {1, CLASS_ALIGN, RM01, 4, 1024, cw(8) | cw(12), CLS_BOTH},
+    {1, CLASS_ALIGN, RM01, 4, 512, cw(12) | cw(16), CLS_BOTH},
+    {1, CLASS_ALIGN, RM01, 4, 1024, cw(12), CLS_BOTH},
     // parts 2, 3: packed sweep, block kernels, 2-byte delta plane cells, 4 / 8 and 16 waves
     // (the long classes, 16 waves of 10, 12, 13 columns, exist for local alignment only: a global score of such lengths does not fit int16)
     // (W = 9 .. 12 with the second width W - 1: sequences of 4.6-6.1 kbp and 9.2-12.3 kbp, whose blocks mix lengths on either side

@@ -893,8 +893,9 @@ static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt)
     for (int k = 0; k < 6; ++k) tot += (double)acc[k];
     size_t fr = 0, tt = 0;
     (void)hipMemGetInfo(&fr, &tt);
-    fprintf(stderr, "[sxg] variant T=%d W=%d cvx=%d rowmode=%d attempt=%d work=%zu slots=%lld per_cu=%d smem=%d slot_bytes=%zu free=%zu ms=%.2f\n",
-            V.T(), V.W, (int)P.cvx, V.RM, attempt, P.work.size(), (long long)P.n_slots, P.per_cu, P.smem, P.lay.total, fr, P.ms);
+    fprintf(stderr, "[sxg] variant T=%d W=%d cvx=%d rowmode=%d attempt=%d work=%zu slots=%lld per_cu=%d smem=%d slot_bytes=%zu free=%zu ms=%.2f tmax=%d cb=%d ds=%d w2=%d\n",
+            V.T(), V.W, (int)P.cvx, V.RM, attempt, P.work.size(), (long long)P.n_slots, P.per_cu, P.smem, P.lay.total, fr, P.ms,
+            V.TMAX, V.CB, (int)V.DS, V.W2);   // (the class that ran: tests read these)
     fprintf(stderr, "[sxg]   slot busy (of the longest slot): min %.1f%% mean %.1f%%\n", 100.0 * (double)smin / (double)std::max(smax, 1ull),
             100.0 * tot / (double)P.n_slots / (double)std::max(smax, 1ull));
     fprintf(stderr, "[sxg]   slot time: other %.1f%% prep_rows %.1f%% dp_fill %.1f%% traceback %.1f%% add_alignment %.1f%% output %.1f%%\n",
@@ -2274,7 +2275,11 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         HCK(hipMemset(d_status.p, 0, 4 * (size_t)n)); HCK(hipMemset(d_score.p, 0, 4 * (size_t)n)); HCK(hipMemset(d_np.p, 0, 4 * (size_t)n));
 
     }
-    // plans
+    // plans (the statistics of an align batch: launches, kernel time and the geometry of the plan with the most work)
+    h->stats = sxg_poa_stats{};
+    h->wstats = sxg_poa_width_stats{};
+    const bool dbg = getenv("SXG_POA_DEBUG") != nullptr;
+    double dom_work = -1;
     struct APlan { Variant variant; bool cvx, sw; std::vector<int32_t> work; int rows_cap = 0; };
     std::vector<APlan> plans;
     for (int p = 0; p < n; ++p) {
@@ -2329,9 +2334,27 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         A.park_in_lds = (V.RM == 2 || dp_park_in_lds(V.Lpad(), wb)) ? 1 : 0;
         A.pf_off = pf_off;
         A.num_cu = std::max(h->num_cu, 1);
+        HCK(hipEventRecord(h->ev0, h->stream));
         hipLaunchKernelGGL(kern, dim3((unsigned)n_slots), dim3(V.T()), (size_t)smem, h->stream, A);
         HCK(hipGetLastError());
+        HCK(hipEventRecord(h->ev1, h->stream));
         HCK(hipStreamSynchronize(h->stream));
+        float ms = 0;
+        HCK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        double work = 0;   // rows x letters of the plan's problems
+        for (int p : pl.work) work += (double)(in->row_off[p + 1] - in->row_off[p]) * (double)(in->seq_off[p + 1] - in->seq_off[p]);
+        h->stats.dp_launches += 1;
+        h->stats.kernel_ms += ms;
+        h->stats.n_slots += (int)n_slots;
+        if (work > dom_work) {
+            dom_work = work;
+            h->stats.dom_kernel_ms = ms;
+            h->stats.dom_threads = V.T(); h->stats.dom_cols_per_lane = V.W * (V.RM >= 2 ? 2 : 1); h->stats.dom_row_mode = V.RM;
+            h->wstats.dom_width = V.W;
+        }
+        if (dbg)
+            fprintf(stderr, "[sxg] variant T=%d W=%d cvx=%d rowmode=%d attempt=0 work=%zu slots=%lld per_cu=%d smem=%d slot_bytes=%zu free=0 ms=%.2f tmax=%d cb=%d ds=%d w2=%d\n",
+                    V.T(), V.W, (int)pl.cvx, V.RM, pl.work.size(), (long long)n_slots, per_cu, smem, lay2.total, ms, V.TMAX, V.CB, (int)V.DS, V.W2);
     }
     std::vector<int32_t> npairs(std::max(n, 1), 0), pr(outcap), pp(outcap);
     if (n) {

@@ -199,8 +199,9 @@ def test_invalid_arguments(engine):
 
 @pytest.mark.parametrize("mode", [0, 1])
 def test_long_sequences_every_kernel_class(engine, oracle, mode):
-    """Lengths that select the 256/512/1024-thread classes, all three strip widths and (in
-    global mode beyond ~7 kbp) the 32-bit row words."""
+    """Lengths of 1.5 - 11.5 kbp in one batch: packed classes of one, two, four and eight waves, local and global.  Both modes stay on
+    the packed sweep: a global block does up to m * L + m < 14 500.  The 32-bit row words and every other class run in
+    test_gpu_class_matrix.py."""
     rng = np.random.default_rng(17 + mode)
     blocks = [random_block(rng, 3, L, div=0.02) for L in (1500, 2500, 3500, 7000, 9000, 11500)]
     res = engine.run_blocks(blocks, gparams("convex_default", mode))
