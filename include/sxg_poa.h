@@ -262,6 +262,14 @@ typedef struct sxg_poa_width_stats {
     int32_t dom_width, dom_width2; /* strip widths of the dominant launch (dom_width2 = 0: one width only) */
 } sxg_poa_width_stats;
 
+/* Packed sweep, twin step (the classes of three waves and more with 2-byte cells sweep two consecutive rows with the same
+ * single predecessor in one step, and the row that joins them takes their maxima out of the registers; SXG_POA_TWIN=0 switches
+ * that off): the rows the last execute prepared that way, summed over its launches from the slots' counters. */
+typedef struct sxg_poa_twin_stats {
+    uint64_t twin_steps;  /* pairs of rows swept in one step */
+    uint64_t join_rows;   /* rows that took both rows of the pair in front of them from registers */
+} sxg_poa_twin_stats;
+
 int sxg_poa_abi_version(void);
 /* Measurement aids (no counterpart in the reference; SURVEY sections 5 and 8d).
  * _measure_copy: a streaming device-to-device copy of `bytes` bytes on this engine's device and stream, timed with HIP events over
@@ -518,6 +526,7 @@ int sxg_poa_path_sgd_order(sxg_poa_handle *h, const sxg_poa_sgd_in *in, int32_t 
 
 int sxg_poa_get_stats(sxg_poa_handle *h, sxg_poa_stats *out);
 int sxg_poa_get_width_stats(sxg_poa_handle *h, sxg_poa_width_stats *out);
+int sxg_poa_get_twin_stats(sxg_poa_handle *h, sxg_poa_twin_stats *out);
 /* Cap on device memory the handle may use for scratch arenas (bytes; 0 = default 3/4 of free). */
 int sxg_poa_set_memory_budget(sxg_poa_handle *h, uint64_t bytes);
 

@@ -30,6 +30,7 @@ struct ClassTraits {
     int tfix;         // the thread count the sweep is compiled for (the launch must run at exactly that), 0 = read at run time
     int min_waves;    // second launch bound: waves per SIMD the register allocator leaves room for
     int graph_batch;  // elements per thread and step of the graph phases (WgCtxT<>): 16, 8 or 4; a class of 8 run on one wave takes 16
+    int twin;         // packed sweep: sibling rows are swept in one step and joined from registers (ROW_TWIN / ROW_JOIN, poa_types.h)
 };
 constexpr ClassTraits class_traits(int TMAX, int W, int RM, int CB) {
     const bool p2 = RM == 2 && CB == 2;   // packed sweep, 2-byte delta plane cells
@@ -51,6 +52,8 @@ constexpr ClassTraits class_traits(int TMAX, int W, int RM, int CB) {
     t.min_waves = TMAX > 512 ? 4 : (RM == 2 ? 4 : (W <= 12 ? 4 : 3));
 #endif
     t.graph_batch = TMAX == 64 ? 16 : (TMAX <= 128 ? 8 : 4);
+    // the packed classes of three waves and more (2-byte cells, stored rows never read back from the plane)
+    t.twin = (p2 && t.rp == 0) ? 1 : 0;
     return t;
 }
 

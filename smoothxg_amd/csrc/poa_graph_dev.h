@@ -872,87 +872,112 @@ SXG_HD_PHASE void rows_remain(Ctx& c, const GraphView& G, int N, SXG_GP int32_t*
     c.sync();
 }
 
-// Rank-space CSR + per-row DP metadata of the current graph.  Returns a status code
-// (identical on every thread).
-// (The packed sweep's band hints written here are COLUMNS, xpos of the row's node: the same rows serve a sweep at either of a
-//  dual-width class's strip widths, and a repeat after a hint shift.)
+// Round 13, the twin step of the packed sweep (dp_fill_p16): two consecutive rows with the same single predecessor are swept in
+// one step from the same inputs, and the row that joins them takes their maxima out of the registers.
+//  * ROW_TWIN on row r: rows r and r + 1 have exactly one predecessor each, the same row.  Pairs are disjoint; a run of such
+//    rows is paired from its start (rows 1 + 2, 3 + 4, ...).  A row finds its place in the run by looking back at most
+//    TWIN_LOOKBACK rows: the rows of a run beyond that many are not paired (both rows of a pair lie below the bound or neither).
+//  * ROW_JOIN on row r + 2: row r carries ROW_TWIN and rows r and r + 1 are both among the predecessors of r + 2.
+//  * ROW_STORE of row x only for readers the registers do not serve.  Served: h == x + 1; h == x + 2 when x + 1 carries
+//    ROW_TWIN (x is the pair's predecessor); h == x + 2 when x carries ROW_TWIN and h carries ROW_JOIN.
+// On entry R.flags holds the plain rule's bits plus ROW_T_NEXT2 / ROW_T_FAR (readers at x + 2 / elsewhere), R.pred_off and
+// R.preds are written; every row decides for itself (two rounds: the pair bits, then the store bit from the neighbours' pair bits).
+// With the launch's knob off (SXG_POA_TWIN=0) prep_rows_twin sets neither helper bit and does not come here.
+constexpr int TWIN_LOOKBACK = 8;
+// Returns this thread's share of the count: twin steps | join rows << 32.
 template <class Ctx>
-SXG_HD_PHASE int prep_rows(Ctx& c, const GraphView& G_, const RowsView& R_, const RowCaps& caps, const int hinted = 0) {
-    const GraphView G = sxg_scalar_view(G_);
-    const RowsView R = sxg_scalar_view(R_);
+SXG_HD unsigned long long twin_flags(Ctx& c, const int N, const RowsView& R) {
     const int T = c.nthreads(), t = c.tid();
     c.sync();
-    const int N = *G.n_nodes;
-    if (N > caps.rows_cap) return ST_ROWS_OVERFLOW;
-    // (GB rows per thread and iteration, every stage of dependent loads issued for all of them before the next: the chains
-    // order -> in_head -> e_tail -> rank are four HBM round trips deep, and one wave per block has nothing else to hide them)
+    // the single predecessor (a row number, rank + 1) of row x, -1: none or several
+    auto one = [&](const int x) -> int {
+        if (x < 0 || x >= N) return -1;
+        const int o = R.pred_off[x];
+        return R.pred_off[x + 1] - o == 1 ? R.preds[o] : -1;
+    };
+    // the place of row x in its run of rows with the single predecessor p (saturates at TWIN_LOOKBACK): a pair opens at the even places
+    auto place = [&](const int x, const int p) -> int {
+        int pos = 0;
+        while (pos < TWIN_LOOKBACK && one(x - pos - 1) == p) ++pos;
+        return pos;
+    };
+    // (GB rows per thread and step, the loads every row needs -- its own and the next row's predecessor -- in two stages, as in
+    //  prep_rows; the look-back and the join test run for the few rows that get that far)
     constexpr int GB = Ctx::GB;
     for (int r0 = t; r0 < N; r0 += GB * T) {
-        int v[GB], cd[GB], xp[GB];
+        int o0[GB], o1[GB], o2[GB], p0[GB], p1[GB];
 #pragma unroll
-        for (int u = 0; u < GB; ++u) v[u] = r0 + u * T < N ? G.order[r0 + u * T] : 0;
+        for (int u = 0; u < GB; ++u) {
+            const int r = r0 + u * T;
+            o0[u] = r < N ? R.pred_off[r] : 0;
+            o1[u] = r < N ? R.pred_off[r + 1] : 0;
+            o2[u] = r + 1 < N ? R.pred_off[r + 2] : o1[u];
+        }
 #pragma unroll
-        for (int u = 0; u < GB; ++u) { cd[u] = G.code[v[u]]; xp[u] = hinted ? G.xpos[v[u]] : 0; }
+        for (int u = 0; u < GB; ++u) {
+            p0[u] = o1[u] - o0[u] == 1 ? R.preds[o0[u]] : -1;
+            p1[u] = o2[u] - o1[u] == 1 ? R.preds[o1[u]] : -1;
+        }
 #pragma unroll
         for (int u = 0; u < GB; ++u) {
             const int r = r0 + u * T;
             if (r >= N) continue;
-            R.row_node[r] = v[u];
-            R.code[r] = (uint8_t)cd[u];
-            if (hinted && hinted != 3) R.tbx[r] = xp[u];
-        }
-    }
-    if (hinted == 3) rows_remain(c, G, N, R.tbx);
-    const int E = array_excl_sum(c, N, [&](int r) { return G.in_deg[G.order[r]]; }, R.pred_off);
-    if (t == 0) R.pred_off[N] = E;
-    c.sync();
-    // preds in rank space; store / sink flags; last reader of every row (kept in R.slot)
-    constexpr int GBH = Ctx::GBH;   // (eleven values per row)
-    for (int r0 = t; r0 < N; r0 += GBH * T) {
-        int v[GBH], o[GBH], ei[GBH], eo[GBH], od[GBH], ti[GBH], ho[GBH], ni[GBH], no[GBH], ri[GBH], ro[GBH];
-#pragma unroll
-        for (int u = 0; u < GBH; ++u) {
-            const int r = r0 + u * T;
-            v[u] = r < N ? G.order[r] : -1;
-            o[u] = r < N ? R.pred_off[r] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < GBH; ++u) {
-            ei[u] = v[u] >= 0 ? G.in_head[v[u]] : -1;
-            eo[u] = v[u] >= 0 ? G.out_head[v[u]] : -1;
-            od[u] = v[u] >= 0 ? G.out_deg[v[u]] : 0;
-        }
-#pragma unroll
-        for (int u = 0; u < GBH; ++u) {   // the first edge of either list (most nodes have one of each)
-            ti[u] = ei[u] >= 0 ? G.e_tail[ei[u]] : -1;
-            ni[u] = ei[u] >= 0 ? G.e_next_in[ei[u]] : -1;
-            ho[u] = eo[u] >= 0 ? G.e_head[eo[u]] : -1;
-            no[u] = eo[u] >= 0 ? G.e_next_out[eo[u]] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < GBH; ++u) {
-            ri[u] = ti[u] >= 0 ? G.rank[ti[u]] : -1;
-            ro[u] = ho[u] >= 0 ? G.rank[ho[u]] : -1;
-        }
-#pragma unroll
-        for (int u = 0; u < GBH; ++u) {
-            const int r = r0 + u * T;
-            if (r >= N) continue;
-            int oo = o[u], regpred = 0;
-            if (ei[u] >= 0) { R.preds[oo++] = ri[u] + 1; regpred |= (int)(ri[u] + 1 == r); }
-            for (int e = ni[u]; e >= 0; e = G.e_next_in[e]) { const int pr = G.rank[G.e_tail[e]] + 1; R.preds[oo++] = pr; regpred |= (int)(pr == r); }
-            int store = 0, lu = r;
-            if (eo[u] >= 0) { if (ro[u] != r + 1) store = 1; if (ro[u] > lu) lu = ro[u]; }
-            for (int e = no[u]; e >= 0; e = G.e_next_out[e]) {
-                const int hr = G.rank[G.e_head[e]];
-                if (hr != r + 1) store = 1;
-                if (hr > lu) lu = hr;
+            int bits = 0;
+            if (p0[u] >= 0) {
+                if (p1[u] == p0[u]) {
+                    const int pos = place(r, p0[u]);
+                    if (pos < TWIN_LOOKBACK && !(pos & 1)) bits = ROW_TWIN;
+                }
+            } else if (r >= 2 && o1[u] - o0[u] >= 2) {
+                const int p2 = one(r - 2);
+                if (p2 >= 0 && one(r - 1) == p2) {
+                    const int pos = place(r - 2, p2);
+                    if (pos < TWIN_LOOKBACK && !(pos & 1)) {
+                        int seen = 0;   // (rows r - 2 and r - 1 are the row numbers r - 1 and r)
+                        for (int x = o0[u]; x < o1[u]; ++x) { const int q = R.preds[x]; seen |= q == r - 1 ? 1 : (q == r ? 2 : 0); }
+                        if (seen == 3) bits = ROW_JOIN;
+                    }
+                }
             }
-            R.flags[r] = (uint8_t)((store ? ROW_STORE : 0) | (od[u] == 0 ? ROW_SINK : 0) | (regpred ? ROW_REGPRED : 0));
-            R.slot[r] = lu;
+            if (bits) R.flags[r] = (uint8_t)(R.flags[r] | bits);
         }
     }
-    return finish_rows(c, N, R, caps, hinted);
+    c.sync();
+    unsigned long long cnt = 0;
+    for (int x = t; x < N; x += T) {
+        const int fl = R.flags[x];
+        cnt += (fl & ROW_TWIN ? 1ull : 0ull) + (fl & ROW_JOIN ? 1ull << 32 : 0ull);
+        if (!(fl & (ROW_T_NEXT2 | ROW_T_FAR))) continue;
+        int out = fl & ~(ROW_T_NEXT2 | ROW_T_FAR);
+        if (!(fl & ROW_T_FAR)) {   // its one reader that is not the next row is row x + 2
+            const bool served2 = (R.flags[x + 1] & ROW_TWIN) || ((fl & ROW_TWIN) && (R.flags[x + 2] & ROW_JOIN));
+            if (served2) out &= ~ROW_STORE;
+        }
+        R.flags[x] = (uint8_t)out;
+    }
+    return cnt;
+}
+
+// Rank-space CSR + per-row DP metadata of the current graph.  Returns a status code
+// (identical on every thread).
+// (The packed sweep's band hints written here are COLUMNS, xpos of the row's node: the same rows serve a sweep at either of a
+//  dual-width class's strip widths, and a repeat after a hint shift.)
+// TWIN (round 13; the packed classes with a twin step, class_traits().twin) and twin_on (the launch's knob): the rows also get
+// ROW_TWIN / ROW_JOIN, and ROW_STORE only for the readers the twin step's registers do not serve -- see twin_flags.  One body
+// (poa_prep_rows.inc.h), two out-of-line functions.
+template <class Ctx>
+SXG_HD_PHASE int prep_rows(Ctx& c, const GraphView& G_, const RowsView& R_, const RowCaps& caps, const int hinted = 0) {
+    constexpr bool TWIN = false;
+    constexpr int twin_on = 0;
+    constexpr unsigned long long* twin_count = nullptr;
+#include "poa_prep_rows.inc.h"
+}
+// the rows of a packed class with the twin step (twin_on = 0: the same flags as prep_rows)
+template <class Ctx>
+SXG_HD_PHASE int prep_rows_twin(Ctx& c, const GraphView& G_, const RowsView& R_, const RowCaps& caps, const int hinted, const int twin_on,
+                                unsigned long long* twin_count) {   // twin_count: += twin steps | join rows << 32 (this thread's share)
+    constexpr bool TWIN = true;
+#include "poa_prep_rows.inc.h"
 }
 
 // S8: heaviest bundle + branch completion.  One thread; scores in sc (int64), preds in pr.

@@ -210,6 +210,7 @@ struct BlockArgs {
     // later ones p16_drift_strips(drift seen so far, band_margin, W, band_floor, lay.band_strips); band_floor = 0: every
     // alignment keeps lay.band_strips (the fixed band)
     int band_floor, band_margin, band_full;
+    int twin;   // packed classes with the twin step: 0 = prep sets neither ROW_TWIN nor ROW_JOIN (SXG_POA_TWIN=0: the rows of round 12)
 };
 
 // Kernel classes <TMAX, W>: TMAX bounds blockDim.x (the actual T = 64 * strips is a run-time
@@ -292,7 +293,14 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                 const int band_mode = RM == 3 ? (int)A.params[A.per_block_params ? b : 0].banded : 0;   // 1 = B2, 2 = adaptive (B4)
                 // (workgroups of one and two waves take more elements per thread and step: see WgCtxT)
                 const int hinted_ = RM == 3 ? (band_mode == 2 ? 3 : 2) : (RM == 2 ? 1 : 0);
-                if (CT.graph_batch == 16 || (CT.graph_batch == 8 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; status = prep_rows(c16, V.G, V.R, caps, hinted_); }
+                if constexpr (RM == 2 && CT.twin != 0) {
+                    // (the classes with the twin step -- three waves and more -- run the graph phases four elements per thread)
+                    static_assert(CT.graph_batch == 4, "twin classes: the plain workgroup context");
+                    unsigned long long n2 = 0;   // twin steps | join rows << 32 among this thread's rows (sxg_poa_get_twin_stats)
+                    status = prep_rows_twin(ctx, V.G, V.R, caps, hinted_, A.twin, &n2);
+                    if (status == ST_OK && n2) atomicAdd(&prof[55], n2);
+                }
+                else if (CT.graph_batch == 16 || (CT.graph_batch == 8 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; status = prep_rows(c16, V.G, V.R, caps, hinted_); }
                 else if (CT.graph_batch == 8) { WgCtxT<8> c8{ctx.lds}; status = prep_rows(c8, V.G, V.R, caps, hinted_); }
                 else status = prep_rows(ctx, V.G, V.R, caps, hinted_);
                 if (status != ST_OK) break;
@@ -356,7 +364,8 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                             // (development: a sweep with parts switched off in front of the real one -- see dp_fill_p16's EXP)
                             if (att == 0) { res = dp_fill_p16<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS, SXG_EXP>(S, V.R, N, seq, len, V.B, smem); __syncthreads(); if (res.best == 0x7fffffff) break; }
 #endif
-                            res = dp_fill_p16<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
+                            if constexpr (CT.twin != 0) res = dp_fill_p16_twin<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
+                            else res = dp_fill_p16<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
                             __syncthreads();
                             PROF(2);
                             if (t == 0) { lds[TBM_FLAG] = 0; lds[TBM_RANGE] = 0; }

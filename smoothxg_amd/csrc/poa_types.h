@@ -27,6 +27,10 @@ constexpr int TB_FEXT = 0x08, TB_OEXT = 0x10, TB_EEXT = 0x20, TB_QEXT = 0x40;
 constexpr int ROW_STORE = 1;  // some successor is not rank+1 -> row goes to the row pool
 constexpr int ROW_SINK = 2;   // no out-edge (NW end candidates)
 constexpr int ROW_REGPRED = 4;  // the previous rank is one of the row's predecessors (its values are still in registers)
+// packed sweep with the twin step (round 13, class_traits().twin; poa_graph_dev.h::twin_flags):
+constexpr int ROW_TWIN = 8;   // rows r and r + 1 have the same single predecessor: dp_fill_p16 sweeps them in one step
+constexpr int ROW_JOIN = 16;  // rows r - 2 (ROW_TWIN) and r - 1 are both predecessors of row r: their maxima are in registers
+constexpr int ROW_T_NEXT2 = 32, ROW_T_FAR = 64;   // (inside prep_rows only: a reader at rank + 2 / a reader beyond)
 
 // status codes (per block); mirrored in include/sxg_poa.h
 enum : int {

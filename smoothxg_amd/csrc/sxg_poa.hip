@@ -329,6 +329,7 @@ struct sxg_poa_handle {
     std::vector<int32_t> bg_counts;
     sxg_poa_stats stats{};
     sxg_poa_width_stats wstats{};   // packed sweeps of the last execute per strip width (sxg_poa_get_width_stats)
+    sxg_poa_twin_stats tstats{};    // twin steps and join rows of the last execute (sxg_poa_get_twin_stats)
     // multi-GPU (sxg_poa_batch_run_sharded): communicator of this rank, result blob of the local shard, and -- on the
     // root -- the blobs of the other ranks, delivered by RCCL
     ncclComm_t comm = nullptr;
@@ -497,6 +498,18 @@ extern "C" int sxg_poa_get_width_stats(sxg_poa_handle* h, sxg_poa_width_stats* o
     if (!h || !out) return fail(SXG_E_INVALID, "NULL argument");
     *out = h->wstats;
     return SXG_OK;
+}
+
+extern "C" int sxg_poa_get_twin_stats(sxg_poa_handle* h, sxg_poa_twin_stats* out) {
+    if (!h || !out) return fail(SXG_E_INVALID, "NULL argument");
+    *out = h->tstats;
+    return SXG_OK;
+}
+
+// SXG_POA_TWIN=0: the classes with a twin step run the rows of round 12 (prep sets neither ROW_TWIN nor ROW_JOIN)
+static bool twin_enabled() {
+    const char* e = getenv("SXG_POA_TWIN");
+    return !(e && atoi(e) == 0);
 }
 
 static uint64_t arena_budget(sxg_poa_handle* h) {
@@ -790,6 +803,7 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     A.blk_cycles = h->d_blk_cycles.as<unsigned long long>();
     A.lds_bytes = getenv("SXG_POA_RESORT_NO_LDS") ? 0 : P.smem;   // (test knob: the S7' re-sort keeps its states in the slot's scratch, as it does for graphs beyond its LDS)
     band_adapt_args(A);
+    A.twin = twin_enabled() ? 1 : 0;
     // every slot's header (counters, phase times, clock readings) starts a launch at zero: one strided memset
     HIPCHK(hipMemset2DAsync(R.arena.as<uint8_t>() + P.lay.hdr, P.lay.total, 0, 512, (size_t)P.n_slots, R.stream));
     HIPCHK(hipStreamWaitEvent(R.stream, h->ev0, 0));
@@ -801,17 +815,18 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     return SXG_OK;
 }
 
-// Packed sweep: what the launch's sweeps ran at, from the slot headers (words 27 and 49..54 of the counters the kernel keeps
-// there -- poa_kernels.hip.h), gathered with one strided copy.
-static int width_stats_of(const LaunchPlan& P, const PlanRes& R, sxg_poa_width_stats& w) {
+// Packed sweep: what the launch's sweeps ran at, from the slot headers (words 27 and 49..55 of the counters the kernel keeps
+// there -- poa_kernels.hip.h), gathered with one strided copy.  Word 55: twin steps | join rows << 32 of the rows the slot prepared.
+static int width_stats_of(const LaunchPlan& P, const PlanRes& R, sxg_poa_width_stats& w, sxg_poa_twin_stats* tw = nullptr) {
     if (P.variant.RM != 2 || P.n_slots <= 0) return SXG_OK;
-    constexpr int K0 = 27, K1 = 55;
+    constexpr int K0 = 27, K1 = 56;
     std::vector<unsigned long long> v((size_t)P.n_slots * (K1 - K0));
     HIPCHK(hipMemcpy2D(v.data(), (K1 - K0) * 8, R.arena.as<uint8_t>() + P.lay.hdr + 64 + K0 * 8, P.lay.total, (K1 - K0) * 8, (size_t)P.n_slots, hipMemcpyDeviceToHost));
     for (int64_t sl = 0; sl < P.n_slots; ++sl) {
         const unsigned long long* c = v.data() + (size_t)sl * (K1 - K0);
         w.hint_shift_repeats += c[27 - K0];
         for (int k = 0; k < 2; ++k) { w.sweeps[k] += c[49 + k - K0]; w.swept_cols[k] += c[51 + k - K0]; w.swept_cells[k] += c[53 + k - K0]; }
+        if (tw) { tw->twin_steps += c[55 - K0] & 0xffffffffull; tw->join_rows += c[55 - K0] >> 32; }
     }
     return SXG_OK;
 }
@@ -838,9 +853,11 @@ static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt)
                 (double)wsum / (double)std::max(nsw, 1ull), P.lay.band_strips, (double)wsum / (double)std::max(nsw, 1ull) * V.W, rep);
         // (with a second width the band line's strips are a mix of both widths' and its columns an upper bound)
         sxg_poa_width_stats w{};
-        if (int rcw = width_stats_of(P, R, w)) return rcw;
+        sxg_poa_twin_stats tw{};
+        if (int rcw = width_stats_of(P, R, w, &tw)) return rcw;
         fprintf(stderr, "[sxg]   width: W=%d %llu sweeps %llu columns %.4g cells; W2=%d %llu sweeps %llu columns %.4g cells\n", V.W, (unsigned long long)w.sweeps[0],
                 (unsigned long long)w.swept_cols[0], (double)w.swept_cells[0], P.lay.W2, (unsigned long long)w.sweeps[1], (unsigned long long)w.swept_cols[1], (double)w.swept_cells[1]);
+        fprintf(stderr, "[sxg]   twin: %llu twin steps, %llu join rows\n", (unsigned long long)tw.twin_steps, (unsigned long long)tw.join_rows);
     }
     if (const char* path = getenv("SXG_POA_SLOT_CSV")) {  // per-slot placement and wall-clock span
         if (FILE* f = fopen(path, "a")) {
@@ -986,6 +1003,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
     const RoctxRange range_("sxg_poa_batch_execute");
     h->stats = sxg_poa_stats{};
     h->wstats = sxg_poa_width_stats{};
+    h->tstats = sxg_poa_twin_stats{};
     const bool dbg = getenv("SXG_POA_DEBUG") != nullptr;
     auto T0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
@@ -1174,7 +1192,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
             h->stats.dp_launches += 1;
             h->stats.n_slots += (int)plans[i].n_slots;
             h->stats.device_bytes += (uint64_t)plans[i].n_slots * plans[i].lay.total;
-            if (int rcw = width_stats_of(plans[i], *h->planres[i], h->wstats)) return rcw;
+            if (int rcw = width_stats_of(plans[i], *h->planres[i], h->wstats, &h->tstats)) return rcw;
             if (dbg) debug_plan(h, plans[i], *h->planres[i], attempt);
         }
         lap("launches");
@@ -2278,6 +2296,7 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
     // plans (the statistics of an align batch: launches, kernel time and the geometry of the plan with the most work)
     h->stats = sxg_poa_stats{};
     h->wstats = sxg_poa_width_stats{};
+    h->tstats = sxg_poa_twin_stats{};
     const bool dbg = getenv("SXG_POA_DEBUG") != nullptr;
     double dom_work = -1;
     struct APlan { Variant variant; bool cvx, sw; std::vector<int32_t> work; int rows_cap = 0; };

@@ -75,6 +75,11 @@ class WidthStats(C.Structure):
                 ("hint_shift_repeats", C.c_uint64), ("dom_width", C.c_int32), ("dom_width2", C.c_int32)]
 
 
+class TwinStats(C.Structure):
+    """sxg_poa_twin_stats: twin steps and join rows of the last execute (packed classes with the twin step)."""
+    _fields_ = [("twin_steps", C.c_uint64), ("join_rows", C.c_uint64)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [("n_blocks", C.c_int32), ("n_seqs", C.c_int64), ("n_bases", C.c_int64),
                 ("status", C.c_void_p), ("n_nodes", C.c_void_p), ("n_edges", C.c_void_p),
@@ -122,7 +127,7 @@ ST_TOO_LONG = 5
 EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
-           "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
+           "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_get_twin_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
            "sxg_poa_comm_attach", "sxg_poa_comm_destroy", "sxg_poa_batch_run_sharded", "sxg_poa_batch_run_sharded_local",
            "sxg_poa_batch_upload_sharded", "sxg_poa_batch_execute_sharded", "sxg_poa_batch_download_sharded", "sxg_poa_sharded_info",
            "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available"]
@@ -157,6 +162,7 @@ def load_library(build_if_missing=True):
     L.sxg_poa_align_free.argtypes = [C.POINTER(AlignOut)]
     L.sxg_poa_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sxg_poa_get_width_stats.argtypes = [vp, C.POINTER(WidthStats)]
+    L.sxg_poa_get_twin_stats.argtypes = [vp, C.POINTER(TwinStats)]
     L.sxg_poa_set_memory_budget.argtypes = [vp, C.c_uint64]
     L.sxg_poa_measure_copy.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
     L.sxg_poa_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
@@ -305,6 +311,9 @@ class PoaEngine:
         self.lib.sxg_poa_get_width_stats(self.h, C.byref(w))
         st.update(width_sweeps=tuple(w.sweeps), width_swept_cols=tuple(w.swept_cols), width_swept_cells=tuple(w.swept_cells),
                   hint_shift_repeats=w.hint_shift_repeats, dom_width=w.dom_width, dom_width2=w.dom_width2)
+        tw = TwinStats()
+        self.lib.sxg_poa_get_twin_stats(self.h, C.byref(tw))
+        st.update(twin_steps=tw.twin_steps, join_rows=tw.join_rows)
         return st
 
     def device_view(self):
