@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-/* 5 (addition, no number change): sxg_poa_path_sgd_order and struct sxg_poa_sgd_in -- the path-guided SGD node order of prep
+/* 5 (addition, no number change, no struct change): want_msa = SXG_MSA_TRIMMED -- the rows of the MAF built on the device -- and
+ *    sxg_poa_get_msa_stats.
+ * 5 (addition, no number change): sxg_poa_path_sgd_order and struct sxg_poa_sgd_in -- the path-guided SGD node order of prep
  *    (src/prep.cpp:11-163) on the device, decree Y.
  * 5 (addition, no number change): sxg_poa_kmer_jaccard_batch, sxg_poa_split_mash_batch and struct sxg_poa_split_mash -- the
  *    mash-based branch of the identity split (src/breaks.cpp:388-471) on the device, decrees M1-M5.
@@ -119,6 +121,26 @@ typedef struct sxg_poa_params {
                        sxg_poa_align_batch ignores it.                                                            */
 } sxg_poa_params;
 
+/* sxg_poa_batch_in::want_msa.
+ * SXG_MSA_FULL: rows = the block's sequences (+ the consensus row when want_consensus), columns = every aligned group in rank order
+ *   (decree S8); formatted on the host from the per-base paths.  Any other non-zero value but SXG_MSA_TRIMMED means this.
+ * SXG_MSA_TRIMMED (an addition to ABI 5): the rows the MAF is written from (src/smooth.cpp:791-847; the `text` fields of
+ *   maf_rows_from_msa, before rows are repeated for duplicates), built on the device: in every row -- the consensus row, which
+ *   comes last, included -- the first and the last bg_trim[b] letters are blanked (bg_trim NULL = 0; a row with fewer than
+ *   2 * trim letters is all gaps); the columns in front of the first column that still holds a letter in any row are removed, and
+ *   those behind the last such column; interior columns stay, all-gap ones too.  msa_cols[b] is the width that remains (0 if
+ *   nothing remains), msa_off / msa as for the full MSA; a block whose status is not SXG_ST_OK, or without sequences, owns no
+ *   bytes.  want_block_graph is NOT downgraded: with 2 or 3 seq_path_nodes stays NULL, with 3 the raw graphs too -- nothing per
+ *   base crosses PCIe but the rows.  Works through sxg_poa_batch_run and upload / execute / download, for full-matrix and banded
+ *   blocks and per-block params.  The sharded entry points (sxg_poa_batch_run_sharded, _upload_sharded and the test entry
+ *   _run_sharded_local) refuse it with SXG_E_INVALID before any work, identically on every rank: device MSAs are not
+ *   reassembled across ranks.
+ *   sxg_poa_get_msa_stats: HIP-event milliseconds of the two kernels of the last execute (columns; rows) and the bytes of rows
+ *   it wrote (any pointer may be NULL).  The columns and the scan scratch take 8 bytes per POA node of the batch, allocated
+ *   with the handle's other result buffers (outside sxg_poa_set_memory_budget, which caps the block arenas). */
+#define SXG_MSA_FULL 1
+#define SXG_MSA_TRIMMED 2
+
 typedef struct sxg_poa_handle sxg_poa_handle;
 
 /* A batch of blocks.  Block b owns sequences blk_off[b] .. blk_off[b+1]-1, in the order
@@ -134,7 +156,7 @@ typedef struct sxg_poa_batch_in {
     const sxg_poa_params *params; /* [n_blocks] if per_block_params else [1] */
     int32_t per_block_params;
     int32_t want_consensus; /* GenerateConsensus(), src/smooth.cpp:773 */
-    int32_t want_msa;       /* GenerateMultipleSequenceAlignment(), src/smooth.cpp:785 */
+    int32_t want_msa;       /* GenerateMultipleSequenceAlignment(), src/smooth.cpp:785: 0, SXG_MSA_FULL or SXG_MSA_TRIMMED (below) */
     /* ABI 4.  The NORMALISED BLOCK GRAPH of every block, computed on the device right after the block's chain of
      * alignments: what smooth_spoa returns to its caller (src/smooth.cpp:931-1010) -- build_odgi_SPOA (:2576-2654: one
      * node per POA node, a path per sequence with bg_trim[b] = poa_padding steps trimmed at both ends, consensus path,
@@ -145,7 +167,8 @@ typedef struct sxg_poa_batch_in {
      *   2 = ... and seq_path_nodes (one node id per base: two thirds of the download) is left out (NULL);
      *   3 = ... and the per-node / per-edge arrays of the raw POA graphs and cons_nodes as well (NULL; status, n_nodes,
      *       n_edges, the offsets, score and cells stay): for a caller that only laces block graphs (sxg_smooth_gfa).
-     *   A request for the MSA (want_msa) turns 2 and 3 into 1: the MSA is formatted from the per-base paths. */
+     *   A request for the full MSA (want_msa = SXG_MSA_FULL) turns 2 and 3 into 1: that MSA is formatted from the per-base
+     *   paths.  The trimmed MSA (SXG_MSA_TRIMMED) is built on the device and leaves the value as it is. */
     int32_t want_block_graph;
     int32_t bg_consensus_visited_only; /* 1 = the consensus path keeps only nodes some sequence path visits (build_odgi_abPOA,
                                           src/smooth.cpp:2542-2548); 0 = every consensus node (build_odgi_SPOA, :2624-2627) */
@@ -527,6 +550,9 @@ int sxg_poa_path_sgd_order(sxg_poa_handle *h, const sxg_poa_sgd_in *in, int32_t 
 int sxg_poa_get_stats(sxg_poa_handle *h, sxg_poa_stats *out);
 int sxg_poa_get_width_stats(sxg_poa_handle *h, sxg_poa_width_stats *out);
 int sxg_poa_get_twin_stats(sxg_poa_handle *h, sxg_poa_twin_stats *out);
+int sxg_poa_get_msa_stats(sxg_poa_handle *h, double *cols_ms, double *rows_ms, uint64_t *msa_bytes);
+/* The rows kernel's geometry: kept letters of a row one work item places, bytes of a row it builds on chip at once (tests). */
+void sxg_poa_msa_geometry(int32_t *chunk_letters, int32_t *tile_bytes);
 /* Cap on device memory the handle may use for scratch arenas (bytes; 0 = default 3/4 of free). */
 int sxg_poa_set_memory_budget(sxg_poa_handle *h, uint64_t bytes);
 

@@ -262,6 +262,20 @@ int sxg_smooth_maf_gfa_adaptive(const sxg_graph *g, const sxg_blockset *b, const
                                 sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, sxg_identity_fn ident, void *ident_ctx,
                                 char **out_gfa, char **out_maf, int64_t *n_flipped);
 
+/* sxg_smooth_maf_gfa_adaptive (ident may be NULL) over MAF rows built by the provider (an addition to ABI 2).  With
+ * mp->merge_blocks == 0 the iteration asks the provider for want_msa = SXG_MSA_TRIMMED, want_block_graph = 3 and bg_trim
+ * (include/sxg_poa.h), so the provider MUST honour SXG_MSA_TRIMMED; it builds the MAF rows straight from the trimmed rows --
+ * names, starts, sizes and strands from the collected ranges --, takes every block's grooming orientation from the collected
+ * ranges (the lowest-ranked input path's range: collected in reverse or not), runs the same in-order consumer and laces the
+ * compact block graphs as sxg_smooth_gfa does (chunk pipeline, validation); a provider that returns no block graphs but raw
+ * results with per-base paths works as it does there.  Same GFA, same MAF, no flips.  Every sequence row must hold its padded
+ * length minus twice the padding in letters and every row must be msa_cols wide: otherwise -- a provider that answered with
+ * the full MSA -- the call fails with SXG_E_INVALID.  With mp->merge_blocks != 0, or SXG_SMOOTH_LEGACY=1, it is
+ * sxg_smooth_maf_gfa_adaptive call for call (merging flips block graphs and strings consensus paths together). */
+int sxg_smooth_maf_gfa_device_rows(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p, const sxg_merge_params *mp,
+                                   sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, sxg_identity_fn ident, void *ident_ctx,
+                                   char **out_gfa, char **out_maf, int64_t *n_flipped);
+
 /* prep (src/prep.cpp:11-163, called from src/main.cpp:423-433 before every iteration unless -n): the graph is sorted by
  * path-guided SGD and chopped to nodes of at most max_node_length bases, so that block discovery -- a sweep over the nodes in
  * rank order -- meets the nodes in the order the paths walk them (an addition to ABI 2, no existing struct changed).  odgi is

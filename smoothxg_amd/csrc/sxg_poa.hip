@@ -28,6 +28,7 @@
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
 #include "poa_identity.hip.h"      // the identity estimate of -a on those sets: all pairs of a block, the percentile's pair (kern_split.hip)
 #include "poa_sgd.hip.h"           // the path-guided SGD node order of prep: argument struct and launchers (kernels in kern_sgd.hip)
+#include "poa_msa.hip.h"           // the trimmed MSA (want_msa == SXG_MSA_TRIMMED): argument structs and launchers (kernels in kern_msa.hip)
 
 
 // ---------------------------------------------------------------------------------------
@@ -327,6 +328,13 @@ struct sxg_poa_handle {
         d_bg_work, d_bg_queue, d_bg_arena;
     std::vector<int64_t> bg_node_o, bg_edge_o;
     std::vector<int32_t> bg_counts;
+    // trimmed MSA (want_msa == SXG_MSA_TRIMMED): columns of the nodes, kept columns and offsets of the blocks, the rows
+    bool msa_done = false;
+    DevBuf d_msa_no, d_msa_tmp, d_msa_col, d_msa_be, d_msa_off, d_msa_items, d_msa_work, d_msa_queue, d_msa;
+    std::vector<int64_t> msa_off_h;
+    std::vector<int32_t> d_trim_h;   // host copy of d_trim
+    std::vector<int32_t> msa_cols_h;
+    double msa_cols_ms = 0, msa_rows_ms = 0;
     sxg_poa_stats stats{};
     sxg_poa_width_stats wstats{};   // packed sweeps of the last execute per strip width (sxg_poa_get_width_stats)
     sxg_poa_twin_stats tstats{};    // twin steps and join rows of the last execute (sxg_poa_get_twin_stats)
@@ -457,7 +465,8 @@ static void release_all(sxg_poa_handle* h) {
                       &h->d_edge_head, &h->d_edge_w, &h->d_paths, &h->d_score, &h->d_cells, &h->d_cons, &h->d_work,
                       &h->d_queue, &h->d_arena, &h->d_blk_cycles, &h->d_tmp_a, &h->d_tmp_b, &h->d_tmp_c, &h->d_tmp_d, &h->d_board, &h->d_trim, &h->d_bg_no, &h->d_bg_eo,
                       &h->d_bg_len, &h->d_bg_od, &h->d_bg_id, &h->d_bg_seq, &h->d_bg_eto, &h->d_bg_steps, &h->d_bg_nsteps, &h->d_bg_cons,
-                      &h->d_bg_counts, &h->d_bg_work, &h->d_bg_queue, &h->d_bg_arena};
+                      &h->d_bg_counts, &h->d_bg_work, &h->d_bg_queue, &h->d_bg_arena,
+                      &h->d_msa_no, &h->d_msa_tmp, &h->d_msa_col, &h->d_msa_be, &h->d_msa_off, &h->d_msa_items, &h->d_msa_work, &h->d_msa_queue, &h->d_msa};
     for (DevBuf* b : bufs) b->release();
 }
 
@@ -550,9 +559,10 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
     h->n_blocks = nb; h->n_seqs = ns; h->n_bases = nbases;
     h->want_consensus = in->want_consensus; h->want_msa = in->want_msa;
     h->want_block_graph = in->want_block_graph < 0 || in->want_block_graph > 3 ? 0 : in->want_block_graph;
-    if (h->want_block_graph >= 2 && in->want_msa) h->want_block_graph = 1;   // (the MSA is formatted from the per-base paths)
+    // (the full MSA is formatted on the host from the per-base paths; the trimmed one is built on the device)
+    if (h->want_block_graph >= 2 && in->want_msa && in->want_msa != SXG_MSA_TRIMMED) h->want_block_graph = 1;
     h->bg_cons_visited_only = in->bg_consensus_visited_only ? 1 : 0;
-    h->bg_done = false;
+    h->bg_done = false; h->msa_done = false;
     h->per_block_params = in->per_block_params;
     h->h_blk_off.assign(in->blk_off, in->blk_off + nb + 1);
     h->h_seq_off.assign(in->seq_off, in->seq_off + ns + 1);
@@ -610,7 +620,7 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
         if ((rc = h->d_weights.ensure(4 * (size_t)std::max<int64_t>(ns, 1)))) return rc;
         if (ns) HIPCHK(hipMemcpyAsync(h->d_weights.p, in->weights, 4 * (size_t)ns, hipMemcpyHostToDevice, h->stream));
     }
-    if (h->want_block_graph) {
+    if (h->want_block_graph || h->want_msa == SXG_MSA_TRIMMED) {
         std::vector<int32_t> trim((size_t)std::max(nb, 1), 0);
         for (int b = 0; b < nb; ++b) {
             trim[b] = in->bg_trim ? in->bg_trim[b] : 0;
@@ -618,6 +628,7 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
         }
         if ((rc = h->d_trim.ensure(4 * trim.size()))) return rc;
         HIPCHK(hipMemcpy(h->d_trim.p, trim.data(), 4 * trim.size(), hipMemcpyHostToDevice));
+        h->d_trim_h.swap(trim);
     }
     const size_t NB = (size_t)std::max<int64_t>(nbases, 1), NS = (size_t)std::max<int64_t>(ns, 1), NBL = (size_t)std::max(nb, 1);
     if ((rc = h->d_status.ensure(4 * NBL)) || (rc = h->d_nn.ensure(4 * NBL)) || (rc = h->d_ne.ensure(4 * NBL)) ||
@@ -996,6 +1007,107 @@ static int run_block_graphs(sxg_poa_handle* h, std::vector<int32_t>& status) {
     return SXG_OK;
 }
 
+// The trimmed MSA of every block on the device (poa_msa.hip.h), after the batch's alignments: the columns kernel leaves every
+// node's column and every block's kept columns [b0, e0); the host turns the nb pairs into widths, offsets and the flat list of
+// (block, row, chunk) items; the rows kernel writes the rows, which stay in HBM until the download.
+static int run_msa_rows(sxg_poa_handle* h, const std::vector<int32_t>& status) {
+    const int nb = h->n_blocks;
+    h->msa_done = false; h->msa_cols_ms = 0; h->msa_rows_ms = 0;
+    h->msa_off_h.assign((size_t)nb + 1, 0); h->msa_cols_h.assign((size_t)std::max(nb, 1), 0);
+    std::vector<int32_t> nc(std::max(nb, 1), 0), nn(std::max(nb, 1), 0), work;
+    if (nb && h->want_consensus) HIPCHK(hipMemcpy(nc.data(), h->d_nc.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    if (nb) HIPCHK(hipMemcpy(nn.data(), h->d_nn.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    std::vector<int64_t> node_o((size_t)nb + 1, 0);   // columns and scan scratch in a compact layout: the nodes the blocks really have
+    for (int b = 0; b < nb; ++b) {
+        const bool live = status[b] == ST_OK && h->meta[b].nseq > 0;
+        if (live && (nn[b] < 0 || nn[b] > h->meta[b].sumlen)) return fail(SXG_E_NODEVICE, "node count of block " + std::to_string(b) + " out of range");
+        node_o[(size_t)b + 1] = node_o[(size_t)b] + (live ? nn[b] : 0);
+        if (live) work.push_back(b);
+    }
+    std::stable_sort(work.begin(), work.end(), [&](int a, int b) { return h->meta[a].sumlen > h->meta[b].sumlen; });
+    const size_t NN = (size_t)std::max<int64_t>(node_o[(size_t)nb], 1), NBL = (size_t)std::max(nb, 1);
+    int rc;
+    if ((rc = h->d_msa_tmp.ensure(4 * NN)) || (rc = h->d_msa_col.ensure(4 * NN)) || (rc = h->d_msa_be.ensure(8 * NBL)) || (rc = h->d_msa_no.ensure(8 * (NBL + 1))) ||
+        (rc = h->d_msa_off.ensure(8 * (NBL + 1))) || (rc = h->d_msa_work.ensure(4 * std::max<size_t>(work.size(), 1))) ||
+        (rc = h->d_msa_queue.ensure(256)))
+        return rc;
+    if (work.empty()) { h->msa_done = true; return SXG_OK; }
+    HIPCHK(hipMemsetAsync(h->d_msa_be.p, 0, 8 * NBL, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_msa_queue.p, 0, 256, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_msa_work.p, work.data(), 4 * work.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_msa_no.p, node_o.data(), 8 * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream));
+    MsaColsArgs C;
+    C.blk_off = h->d_blk_off.as<int32_t>(); C.seq_off = h->d_seq_off.as<int64_t>(); C.paths = h->d_paths.as<int32_t>();
+    C.cons = h->want_consensus ? h->d_cons.as<int32_t>() : nullptr;
+    C.node_rank = h->d_node_rank.as<int32_t>(); C.node_group = h->d_node_group.as<int32_t>();
+    C.nn = h->d_nn.as<int32_t>(); C.nc = h->d_nc.as<int32_t>(); C.trim = h->d_trim.as<int32_t>();
+    C.work = h->d_msa_work.as<int32_t>(); C.n_work = (int32_t)work.size(); C.queue = h->d_msa_queue.as<int32_t>();
+    C.node_o = h->d_msa_no.as<int64_t>(); C.tmp = h->d_msa_tmp.as<int32_t>(); C.col = h->d_msa_col.as<int32_t>(); C.be = h->d_msa_be.as<int32_t>();
+    const int slots_c = (int)std::min<int64_t>((int64_t)work.size(), (int64_t)h->num_cu * 8);
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    sxg_msa_launch_cols(C, slots_c, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    std::vector<int32_t> be(2 * NBL, 0);
+    HIPCHK(hipMemcpyAsync(be.data(), h->d_msa_be.p, 8 * (size_t)nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1)); h->msa_cols_ms = ms; }
+    std::vector<char> live((size_t)NBL, 0);
+    for (int b : work) live[(size_t)b] = 1;
+    std::vector<MsaItem> items;
+    for (int b = 0; b < nb; ++b) {
+        const int64_t cols = live[(size_t)b] ? (int64_t)be[2 * (size_t)b + 1] - be[2 * (size_t)b] : 0;
+        if (cols < 0 || cols > 0x7fffffff) return fail(SXG_E_NODEVICE, "MSA columns kernel returned an impossible width for block " + std::to_string(b));
+        const int rows = h->meta[b].nseq + (h->want_consensus ? 1 : 0);
+        h->msa_cols_h[(size_t)b] = (int32_t)cols;
+        h->msa_off_h[(size_t)b + 1] = h->msa_off_h[(size_t)b] + (live[(size_t)b] ? (int64_t)rows * cols : 0);
+        if (!cols) continue;
+        const int64_t trim = h->d_trim_h.empty() ? 0 : h->d_trim_h[(size_t)b];
+        for (int row = 0; row < rows; ++row) {
+            const int s = h->h_blk_off[b] + row;
+            const int64_t len = row < h->meta[b].nseq ? h->h_seq_off[(size_t)s + 1] - h->h_seq_off[(size_t)s] : nc[(size_t)b];
+            int64_t k0, k1;
+            sxg_msa_kept(len, trim, &k0, &k1);
+            const int64_t n_chunks = sxg_msa_chunks(k0, k1, SXG_MSA_CHUNK);
+            for (int64_t c = 0; c < n_chunks; ++c) items.push_back(MsaItem{b, row, (int32_t)c, 0});
+        }
+    }
+    const int64_t total = h->msa_off_h[(size_t)nb];
+    if ((rc = h->d_msa.ensure((size_t)std::max<int64_t>(total, 16) + 16))) return rc;
+    if (!items.empty()) {
+        if ((rc = h->d_msa_items.ensure(sizeof(MsaItem) * items.size()))) return rc;
+        HIPCHK(hipMemcpyAsync(h->d_msa_off.p, h->msa_off_h.data(), 8 * ((size_t)nb + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->d_msa_items.p, items.data(), sizeof(MsaItem) * items.size(), hipMemcpyHostToDevice, h->stream));
+        MsaRowsArgs R;
+        R.blk_off = C.blk_off; R.seq_off = C.seq_off; R.paths = C.paths; R.cons = C.cons; R.node_code = h->d_node_code.as<uint8_t>();
+        R.nn = C.nn; R.nc = C.nc; R.trim = C.trim; R.col = C.col; R.node_o = C.node_o; R.be = C.be; R.msa_off = h->d_msa_off.as<int64_t>();
+        R.items = h->d_msa_items.as<MsaItem>(); R.n_items = (int64_t)items.size();
+        R.msa = h->d_msa.as<char>(); R.msa_bytes = total;
+        const int slots_r = (int)std::min<int64_t>((int64_t)items.size(), (int64_t)h->num_cu * 8);
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        sxg_msa_launch_rows(R, slots_r, h->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1)); h->msa_rows_ms = ms; }
+    }
+    h->msa_done = true;
+    return SXG_OK;
+}
+
+extern "C" void sxg_poa_msa_geometry(int32_t* chunk_letters, int32_t* tile_bytes) {
+    if (chunk_letters) *chunk_letters = SXG_MSA_CHUNK;
+    if (tile_bytes) *tile_bytes = SXG_MSA_TILE;
+}
+
+extern "C" int sxg_poa_get_msa_stats(sxg_poa_handle* h, double* cols_ms, double* rows_ms, uint64_t* msa_bytes) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    if (cols_ms) *cols_ms = h->msa_cols_ms;
+    if (rows_ms) *rows_ms = h->msa_rows_ms;
+    if (msa_bytes) *msa_bytes = h->msa_done && !h->msa_off_h.empty() ? (uint64_t)h->msa_off_h.back() : 0;
+    return SXG_OK;
+}
+
 extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
     if (!h) return fail(SXG_E_INVALID, "handle is NULL");
     if (!h->have_batch) return fail(SXG_E_INVALID, "no batch uploaded");
@@ -1275,6 +1387,11 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         if (rc) return rc;
         lap("block graphs");
     }
+    if (h->want_msa == SXG_MSA_TRIMMED) {
+        int rc = run_msa_rows(h, status);
+        if (rc) return rc;
+        lap("MSA rows");
+    }
     for (int b = 0; b < nb; ++b)
         if (status[b] != ST_OK) return fail(SXG_E_BLOCK, "block " + std::to_string(b) + " failed with status " + std::to_string(status[b]));
     return SXG_OK;
@@ -1320,6 +1437,7 @@ struct OutOwner {
     std::vector<int64_t> bg_node_off, bg_seq_off, bg_edge_off, bg_step_off, bg_cons_off;
     hvec<int32_t> bg_node_len, bg_node_outdeg, bg_edge_to, bg_steps, bg_cons_steps;
     hvec<uint8_t> bg_node_indeg, bg_seq;
+    hvec<uint8_t> msa_rows;   // the trimmed MSA, copied as the device wrote it
 };
 
 template <class Tv>
@@ -1474,7 +1592,18 @@ extern "C" int sxg_poa_batch_download(sxg_poa_handle* h, sxg_poa_batch_out* out)
     }
     out->seq_path_nodes = o->seq_path_nodes; out->score = o->score.data(); out->cells = o->cells.data();
     if (h->want_consensus) { out->cons_off = o->cons_off.data(); if (with_graphs) out->cons_nodes = o->cons_nodes.data(); }
-    if (h->want_msa && o->seq_path_nodes) {
+    if (h->want_msa == SXG_MSA_TRIMMED) {
+        if (!h->msa_done) { sxg_poa_batch_free(out); return fail(SXG_E_INVALID, "the trimmed MSA of this batch was not built"); }
+        o->msa_off = h->msa_off_h; o->msa_cols = h->msa_cols_h;
+        const int64_t total = o->msa_off[nb];
+        o->msa_rows.resize((size_t)std::max<int64_t>(total, 1));
+        if (total) {
+            const hipError_t e = hipMemcpy(o->msa_rows.data(), h->d_msa.p, (size_t)total, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) { sxg_poa_batch_free(out); return fail(SXG_E_NODEVICE, std::string("download of the MSA rows: ") + hipGetErrorString(e)); }
+        }
+        out->msa_off = o->msa_off.data(); out->msa_cols = o->msa_cols.data(); out->msa = (char*)o->msa_rows.data();
+        laps.lap("download: MSA rows");
+    } else if (h->want_msa && o->seq_path_nodes) {
         // S8: MSA column = aligned group in rank order; pure formatting of device results
         static const char dec[5] = {'A', 'C', 'G', 'T', 'N'};
         o->msa_off.assign(nb + 1, 0); o->msa_cols.assign(std::max(nb, 1), 0);
@@ -2037,6 +2166,7 @@ static int comm_wait(sxg_poa_handle* h, const char* what) {
 }
 
 static int check_batch(const sxg_poa_batch_in* in) {
+    if (in->want_msa == SXG_MSA_TRIMMED) return fail(SXG_E_INVALID, "the trimmed MSA (want_msa = SXG_MSA_TRIMMED) is not reassembled across ranks: use sxg_poa_batch_run");
     if (in->n_blocks < 0 || (in->n_blocks > 0 && (!in->blk_off || !in->seq_off || !in->params || !in->bases))) return fail(SXG_E_INVALID, "batch_in has NULL arrays");
     return SXG_OK;
 }
@@ -2182,6 +2312,7 @@ extern "C" int sxg_poa_sharded_info(sxg_poa_handle* h, int32_t* ranks_seen, uint
 extern "C" int sxg_poa_batch_run_sharded(sxg_poa_handle* h, const sxg_poa_batch_in* in, sxg_poa_batch_out* out) {
     if (!h || !in || !out) return fail(SXG_E_INVALID, "NULL argument");
     memset(out, 0, sizeof(*out));
+    if (int crc = check_batch(in)) return crc;   // (the same answer on every rank, before the collective)
     // (an upload that fails on one rank only -- a host or device allocation -- must still reach the collective: the
     //  execute stage then reports "no batch" as this rank's error and all ranks fail together)
     const int urc = sxg_poa_batch_upload_sharded(h, in);

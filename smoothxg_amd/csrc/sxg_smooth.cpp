@@ -854,14 +854,46 @@ int identity_table(const sxg_graph& g, const sxg_blockset& b, int k, uint64_t ma
 // MSA -> MAF rows: src/smooth.cpp:782-905
 struct maf_row_t { std::string src; uint64_t start, size; bool rev; uint64_t src_size; std::string text; };
 
+// :850-905 rows from the TRIMMED texts (one per dedup'd sequence, the consensus row last): a row per duplicate, names, starts,
+// sizes and strands from the collected ranges
+std::vector<maf_row_t> maf_rows_from_texts(const sxg_graph& g, const std::vector<path_range_t>& ranges, const collected_t& c,
+                                           const std::vector<std::string>& texts, const std::string& consensus_name, size_t consensus_len) {
+    std::vector<maf_row_t> rows;
+    const bool add_consensus = !consensus_name.empty();
+    const uint64_t pad = (uint64_t)c.poa_padding;
+    const size_t num_seqs = texts.size();
+    for (size_t rank = 0; rank < num_seqs; ++rank) {
+        const bool is_cons = add_consensus && rank == num_seqs - 1;
+        const size_t ndup = is_cons ? 1 : c.dup_rank_in_path_ranges[rank].size();  // :772-779 placeholder entry
+        for (size_t x = 0; x < ndup; ++x) {
+            maf_row_t row;
+            if (!is_cons) {  // :861-880
+                const path_range_t& pr = ranges[c.dup_rank_in_path_ranges[rank][x]];
+                row.src = g.pname[pr.path];
+                row.rev = c.dup_is_revs[rank][x];
+                row.src_size = g.pos[pr.path].back();
+                const uint64_t last = pr.end - 1;
+                row.start = row.rev ? row.src_size - g.pos[pr.path][last] - g.seq[nid(g.steps[pr.path][last])].size() : g.pos[pr.path][pr.begin];
+                row.size = c.seqs[rank].size() >= 2 * pad ? c.seqs[rank].size() - 2 * pad : 0;
+            } else {         // :881-889 (a consensus shorter than twice the padding keeps no letter: size 0, not a wrapped difference)
+                row.src = consensus_name; row.rev = false; row.src_size = consensus_len >= 2 * pad ? consensus_len - 2 * pad : 0; row.start = 0; row.size = row.src_size;
+            }
+            row.text = texts[rank];
+            rows.push_back(row);
+        }
+    }
+    return rows;
+}
+
 std::vector<maf_row_t> maf_rows_from_msa(const sxg_graph& g, const std::vector<path_range_t>& ranges, const collected_t& c,
                                          std::vector<std::string> msa, const std::string& consensus_name, size_t consensus_len) {
-    std::vector<maf_row_t> rows;
-    if (msa.empty()) return rows;
-    const bool add_consensus = !consensus_name.empty();
+    if (msa.empty()) return std::vector<maf_row_t>();
     const size_t msa_l = msa[0].size();
     const uint64_t pad = (uint64_t)c.poa_padding;
     for (auto& r : msa) {  // :791-812 blank the padding
+        // (a row with fewer than 2 * pad letters -- the consensus of a local alignment can be that short -- makes the reference
+        //  walk off the row; here it becomes all gaps, the rule of SXG_MSA_TRIMMED)
+        if ((uint64_t)(r.size() - (size_t)std::count(r.begin(), r.end(), '-')) < 2 * pad) { std::fill(r.begin(), r.end(), '-'); continue; }
         size_t j = 0;
         for (uint64_t left = pad; left > 0; ++j)
             if (r[j] != '-') { r[j] = '-'; --left; }
@@ -877,28 +909,8 @@ std::vector<maf_row_t> maf_rows_from_msa(const sxg_graph& g, const std::vector<p
     int64_t e0 = (int64_t)msa_l - 1;     // :832-847
     while (e0 >= 0 && !col_has_letter((size_t)e0)) --e0;
     e0 += 1;
-    const size_t num_seqs = msa.size();
-    for (size_t rank = 0; rank < num_seqs; ++rank) {
-        const bool is_cons = add_consensus && rank == num_seqs - 1;
-        const size_t ndup = is_cons ? 1 : c.dup_rank_in_path_ranges[rank].size();  // :772-779 placeholder entry
-        for (size_t x = 0; x < ndup; ++x) {
-            maf_row_t row;
-            if (!is_cons) {  // :861-880
-                const path_range_t& pr = ranges[c.dup_rank_in_path_ranges[rank][x]];
-                row.src = g.pname[pr.path];
-                row.rev = c.dup_is_revs[rank][x];
-                row.src_size = g.pos[pr.path].back();
-                const uint64_t last = pr.end - 1;
-                row.start = row.rev ? row.src_size - g.pos[pr.path][last] - g.seq[nid(g.steps[pr.path][last])].size() : g.pos[pr.path][pr.begin];
-                row.size = c.seqs[rank].size() - 2 * pad;
-            } else {         // :881-889
-                row.src = consensus_name; row.rev = false; row.src_size = consensus_len - 2 * pad; row.start = 0; row.size = row.src_size;
-            }
-            row.text = (int64_t)b0 < e0 ? msa[rank].substr(b0, (size_t)e0 - b0) : std::string();
-            rows.push_back(row);
-        }
-    }
-    return rows;
+    for (auto& r : msa) r = (int64_t)b0 < e0 ? r.substr(b0, (size_t)e0 - b0) : std::string();
+    return maf_rows_from_texts(g, ranges, c, msa, consensus_name, consensus_len);
 }
 std::string maf_rows_text(const std::vector<maf_row_t>& rows) {
     std::string o;
@@ -1186,6 +1198,29 @@ bool groom_flip(const std::unordered_map<std::string, size_t>& rank_of, const og
         auto it = rank_of.find(p.first.substr(0, p.first.find_last_of('_')));
         if (it == rank_of.end()) continue;
         if (it->second < best) { best = it->second; fl = rev(p.second.front()); }
+    }
+    return fl;
+}
+
+// groom_flip without a block graph: a block path exists per range, in the order of the ranges, and is empty when the padded
+// sequence holds nothing but padding; unchop and the topological numbering leave every node forward, so the first step of a
+// block path is reversed exactly when its range was collected in reverse.
+bool groom_flip_from_ranges(const std::unordered_map<std::string, size_t>& rank_of, const sxg_graph& g, const std::vector<path_range_t>& ranges,
+                            const collected_t& c) {
+    std::vector<int64_t> useq(ranges.size(), -1);
+    std::vector<char> is_rev(ranges.size(), 0);
+    for (size_t i = 0; i < c.dup_rank_in_path_ranges.size(); ++i)
+        for (size_t j = 0; j < c.dup_rank_in_path_ranges[i].size(); ++j) {
+            useq[(size_t)c.dup_rank_in_path_ranges[i][j]] = (int64_t)i;
+            is_rev[(size_t)c.dup_rank_in_path_ranges[i][j]] = c.dup_is_revs[i][j] ? 1 : 0;
+        }
+    size_t best = (size_t)-1;
+    bool fl = false;
+    for (size_t i = 0; i < ranges.size(); ++i) {
+        if (useq[i] < 0 || (int64_t)c.seqs[(size_t)useq[i]].size() <= 2 * (int64_t)c.poa_padding) continue;
+        auto it = rank_of.find(g.pname[ranges[i].path]);
+        if (it == rank_of.end()) continue;
+        if (it->second < best) { best = it->second; fl = is_rev[i] != 0; }
     }
     return fl;
 }
@@ -2267,7 +2302,7 @@ static void reap(std::function<void()> fn) { g_reaper.run(std::move(fn)); }
 
 static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp,
                             sxg_poa_run_fn run, sxg_poa_free_fn fre, void* ctx, sxg_identity_fn ident, void* ident_ctx, char** out_gfa,
-                            char** out_maf, int64_t* n_flipped) {
+                            char** out_maf, int64_t* n_flipped, const bool device_rows = false) {
     if (!g || !b || !p || !run || !out_gfa) return fail(SXG_E_INVALID, "NULL argument");
     if (int prc = check_params(p)) return prc;
     if (out_maf) *out_maf = nullptr;
@@ -2292,7 +2327,12 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
     // Without the MAF consumer (no flips, no merged consensus paths) the iteration works on compact block graphs -- asked of
     // the provider (the GPU engine builds them on the device), built here from raw results otherwise -- and laces them
     // without materialising the laced graph (lace_fast).  SXG_SMOOTH_LEGACY=1 keeps the ograph_t path for A/B runs and tests.
-    const bool fast = !mp && !getenv("SXG_SMOOTH_LEGACY");
+    // The MAF consumer without block merging decides no flip and strings no consensus paths together: asked for device rows
+    // (sxg_smooth_maf_gfa_device_rows) it takes the same compact path -- the provider returns the TRIMMED rows of every block
+    // (SXG_MSA_TRIMMED) next to the block graphs, the grooming orientation comes from the collected ranges.
+    const bool rows_fast = device_rows && mp && mp->merge_blocks == 0 && !getenv("SXG_SMOOTH_LEGACY");
+    const bool fast = (!mp || rows_fast) && !getenv("SXG_SMOOTH_LEGACY");
+    std::atomic<int64_t> rows_bad{-1};   // first block whose rows broke the contract of SXG_MSA_TRIMMED
     std::vector<collected_t> col((size_t)nb);
     std::vector<ograph_t> graphs(fast ? 0 : (size_t)nb);
     std::vector<cblock_t> cblocks(fast ? (size_t)nb : 0);
@@ -2387,7 +2427,7 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
         C.in.bases = B.bases.empty() ? &C.dummy : B.bases.data(); C.in.weights = B.weights.data(); C.in.params = C.pps.data();
         C.in.per_block_params = p->adaptive_poa_params && n > 0 ? 1 : 0;
         C.in.want_consensus = p->add_consensus;
-        C.in.want_msa = mp ? 1 : 0;   // the MAF rows (and with them the merge / flip decisions) need the blocks' MSAs
+        C.in.want_msa = rows_fast ? SXG_MSA_TRIMMED : mp ? SXG_MSA_FULL : 0;   // the MAF rows (and with them the merge / flip decisions) need the blocks' MSAs
         if (fast) {   // A9 + A10 asked of the provider: trim = the block's padding, consensus filter of the abPOA path
             C.trims.resize((size_t)std::max<int64_t>(n, 1), 0);
             for (int64_t k = 0; k < n; ++k) C.trims[(size_t)k] = col[(size_t)(k0 + k)].poa_padding;
@@ -2430,6 +2470,23 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
                 // on the next chunk: the block's share of the validation (src/main.cpp:770-810) is done here, off the serial
                 // tail behind the last chunk.  (One chunk: nothing to overlap with, lace_fast does it.)
                 if (nc > 1) Bk.validated = block_spells_its_ranges(g, b->blocks[(size_t)k], Bk) ? 1 : -1;
+                if (rows_fast) {   // the block's MAF rows straight from the provider's trimmed rows, after the contract is checked
+                    const size_t nrow = c.seqs.size() + (p->add_consensus ? 1 : 0);
+                    const int64_t cols = out.msa_cols[slot];
+                    bool ok = cols >= 0 && out.msa_off[slot + 1] - out.msa_off[slot] == (int64_t)nrow * cols;
+                    std::vector<std::string> texts;
+                    for (size_t r = 0; ok && r < nrow; ++r) {
+                        texts.emplace_back(cols ? out.msa + out.msa_off[slot] + (int64_t)r * cols : "", (size_t)cols);
+                        if (r >= c.seqs.size()) continue;
+                        int64_t letters = 0;
+                        for (char ch : texts.back()) letters += ch != '-';
+                        ok = letters == std::max<int64_t>(0, (int64_t)c.seqs[r].size() - 2 * (int64_t)c.poa_padding);
+                    }
+                    if (!ok) { int64_t none = -1; rows_bad.compare_exchange_strong(none, k); continue; }
+                    const size_t cons_len = out.cons_off ? (size_t)(out.cons_off[slot + 1] - out.cons_off[slot]) : 0;
+                    block_mafs[(size_t)k] = maf_block_map(maf_rows_from_texts(*g, b->blocks[(size_t)k], c, texts, cons_name(*p, k), cons_len));
+                    groom[(size_t)k] = groom_flip_from_ranges(rank_of, *g, b->blocks[(size_t)k], c) ? 1 : 0;
+                }
                 continue;   // (the padded sequences go with everything else when the iteration is over)
             }
             graphs[(size_t)k] = block_graph_from_out(col[(size_t)k], C.B, out, slot, cons_name(*p, k), p->use_abpoa != 0);
@@ -2469,7 +2526,14 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
             else if (fast && C.k1 > C.k0 && !C.out.bg_node_off && (!C.out.seq_path_nodes || !C.out.node_off || !C.out.node_code)) {
                 if (fail_rc == SXG_OK) { fail_rc = SXG_E_INVALID; fail_msg = "POA provider returned neither block graphs nor per-base paths"; }
             }
-            else if (fail_rc == SXG_OK && !not_root) finish(C);
+            else if (fail_rc == SXG_OK && !not_root) {
+                finish(C);
+                if (rows_bad.load() >= 0) {
+                    fail_rc = SXG_E_INVALID;
+                    fail_msg = "POA provider broke the contract of SXG_MSA_TRIMMED for block " + std::to_string(rows_bad.load()) +
+                               ": every sequence row holds its length minus twice the padding in letters, every row is msa_cols wide";
+                }
+            }
             if (fre && !C.keep_out) fre(&C.out);
             batch_t().bases.swap(C.B.bases);
         }
@@ -2483,6 +2547,16 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
         T0 = std::chrono::steady_clock::now();
     }
     if (fast) {
+        if (rows_fast) {   // the in-order MAF consumer (no merging: every block its own group, groomed)
+            merge_state_t mstate;
+            std::vector<char> flips;
+            const std::string maf = merge_maf_blocks(block_mafs, groom, false, mp->contiguous_path_jaccard, p->add_consensus != 0,
+                                                     p->consensus_base_name ? p->consensus_base_name : "Consensus_",
+                                                     mp->max_merged_groups_in_memory ? (size_t)mp->max_merged_groups_in_memory : 50,
+                                                     mp->preserve_unmerged_consensus != 0, mp->maf_header, flips, mstate);
+            if (out_maf) *out_maf = dup_out(maf);   // (without merging no block is flipped: *n_flipped stays 0)
+            lap("MAF rows");
+        }
         const int rc = lace_fast(g, b, p, cblocks, out_gfa, lap);
         // The providers' results go back to the provider HERE, on the caller's thread, before the call returns: the free
         // callback and its context need only live for the call (sxg_poa_free_fn, include/sxg_smooth.h), and a pinned
@@ -3088,6 +3162,12 @@ int sxg_smooth_maf_gfa_adaptive(const sxg_graph* g, const sxg_blockset* b, const
                                 int64_t* n_flipped) {
     if (!mp || !out_maf) return fail(SXG_E_INVALID, "NULL argument");
     return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, ident, ident_ctx, out_gfa, out_maf, n_flipped); });
+}
+int sxg_smooth_maf_gfa_device_rows(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
+                                   sxg_poa_free_fn fre, void* ctx, sxg_identity_fn ident, void* ident_ctx, char** out_gfa, char** out_maf,
+                                   int64_t* n_flipped) {
+    if (!mp || !out_maf) return fail(SXG_E_INVALID, "NULL argument");
+    return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, ident, ident_ctx, out_gfa, out_maf, n_flipped, true); });
 }
 int sxg_smooth_maf_gfa(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
                        sxg_poa_free_fn fre, void* ctx, char** out_gfa, char** out_maf, int64_t* n_flipped) {

@@ -123,6 +123,7 @@ MASH_SORT_TILE = 1024   # SXG_POA_MASH_SORT_TILE: k-mers a workgroup sorts on ch
 SPLIT_PANEL = 512   # SXG_POA_SPLIT_PANEL: columns of the second sequence a wavefront sweeps at once
 MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
 ST_TOO_LONG = 5
+MSA_FULL, MSA_TRIMMED = 1, 2   # SXG_MSA_FULL / SXG_MSA_TRIMMED: values of want_msa (True = the full MSA)
 
 EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
@@ -130,7 +131,7 @@ EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_km
            "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_get_twin_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
            "sxg_poa_comm_attach", "sxg_poa_comm_destroy", "sxg_poa_batch_run_sharded", "sxg_poa_batch_run_sharded_local",
            "sxg_poa_batch_upload_sharded", "sxg_poa_batch_execute_sharded", "sxg_poa_batch_download_sharded", "sxg_poa_sharded_info",
-           "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available"]
+           "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available", "sxg_poa_get_msa_stats", "sxg_poa_msa_geometry"]
 COMM_ID_BYTES = 128
 NOT_ROOT = 1
 
@@ -164,6 +165,9 @@ def load_library(build_if_missing=True):
     L.sxg_poa_get_width_stats.argtypes = [vp, C.POINTER(WidthStats)]
     L.sxg_poa_get_twin_stats.argtypes = [vp, C.POINTER(TwinStats)]
     L.sxg_poa_set_memory_budget.argtypes = [vp, C.c_uint64]
+    L.sxg_poa_get_msa_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.sxg_poa_msa_geometry.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.sxg_poa_msa_geometry.restype = None
     L.sxg_poa_measure_copy.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(C.c_double)]
     L.sxg_poa_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
     L.sxg_poa_comm_init.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int]
@@ -288,13 +292,14 @@ class PoaEngine:
 
     def upload(self, bases, seq_off, blk_off, weights, params, want_consensus=False, want_msa=False, block_graph=0,
                bg_trim=None, bg_cons_visited_only=False):
-        """block_graph: 1 = also the normalised block graphs (BlockResult.bg), 2 = ... without the per-base paths,
+        """want_msa: False, True / MSA_FULL, or MSA_TRIMMED (the rows of the MAF, built on the device; BlockResult.msa).
+        block_graph: 1 = also the normalised block graphs (BlockResult.bg), 2 = ... without the per-base paths,
         3 = ... and without the raw POA graphs (node_* / edge_* / consensus of the results are None)."""
         bi = self._mk_in(bases, seq_off, blk_off, weights, params, want_consensus, want_msa, block_graph, bg_trim,
                          bg_cons_visited_only)
         if self.lib.sxg_poa_batch_upload(self.h, C.byref(bi)):
             raise self._err("sxg_poa_batch_upload")
-        self._shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy())
+        self._shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy(), int(want_msa))
 
     def execute(self, check=True):
         rc = self.lib.sxg_poa_batch_execute(self.h)
@@ -316,6 +321,18 @@ class PoaEngine:
         st.update(twin_steps=tw.twin_steps, join_rows=tw.join_rows)
         return st
 
+    def msa_geometry(self):
+        """sxg_poa_msa_geometry: (kept letters of a row per work item of the rows kernel, bytes of its on-chip window)."""
+        a, b = C.c_int32(), C.c_int32()
+        self.lib.sxg_poa_msa_geometry(C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def msa_stats(self):
+        """sxg_poa_get_msa_stats: (columns kernel ms, rows kernel ms, bytes of rows) of the last execute with want_msa=MSA_TRIMMED."""
+        a, b, n = C.c_double(), C.c_double(), C.c_uint64()
+        self.lib.sxg_poa_get_msa_stats(self.h, C.byref(a), C.byref(b), C.byref(n))
+        return a.value, b.value, n.value
+
     def device_view(self):
         """Raw HBM pointers of the executed batch's results (see sxg_poa_device_view)."""
         v = DeviceView()
@@ -332,8 +349,11 @@ class PoaEngine:
         finally:
             self.lib.sxg_poa_batch_free(C.byref(out))
 
-    def _unpack(self, out):
-        blk_off, seq_off = self._shape
+    def _unpack(self, out, shape=None):
+        # shape: offsets and want_msa of the batch these results belong to (default: the batch upload() made resident)
+        shape = shape if shape is not None else self._shape
+        blk_off, seq_off = shape[:2]
+        msa_mode = shape[2] if len(shape) > 2 else 0
         nb = out.n_blocks
         ns = int(out.n_seqs)
         status = _arr(out.status, nb, np.int32)
@@ -399,7 +419,9 @@ class PoaEngine:
             r.device_cycles = int(cycles[b]) if cycles is not None else None   # (sxg_poa_batch_out::block_cycles)
             r.consensus = cons[cons_off[b]:cons_off[b + 1]] if cons is not None else None
             r.msa = None
-            if msa_raw is not None and r.status == 0:
+            if msa_mode == MSA_TRIMMED and msa_cols is not None and r.status == 0 and s1 > s0 and int(msa_cols[b]) == 0:
+                r.msa = [""] * ((s1 - s0) + (1 if cons_off is not None else 0))   # (nothing remains after the trim: rows x "")
+            elif msa_raw is not None and r.status == 0:
                 ncol = int(msa_cols[b])
                 raw = msa_raw[int(msa_off[b]):int(msa_off[b + 1])]
                 r.msa = [raw[i * ncol:(i + 1) * ncol].decode() for i in range(len(raw) // ncol)] if ncol else []
@@ -431,7 +453,7 @@ class PoaEngine:
         """sxg_poa_batch_run_sharded: every rank passes the SAME batch; rank 0 gets all results (list), the others None.
         simulate_ranks > 0: the test entry that plays that many ranks on this one GPU."""
         bi = self._mk_in(bases, seq_off, blk_off, weights, params, want_consensus, want_msa, block_graph, bg_trim, bg_cons_visited_only)
-        self._shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy())
+        shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy(), int(want_msa))   # (of THIS call: a refused call leaves the resident batch and its shape alone)
         out = BatchOut()
         if simulate_ranks:
             rc = self.lib.sxg_poa_batch_run_sharded_local(self.h, C.byref(bi), simulate_ranks, C.byref(out))
@@ -442,17 +464,18 @@ class PoaEngine:
         try:
             if rc and (check or rc != -4):
                 raise self._err("sxg_poa_batch_run_sharded")
-            return self._unpack(out)
+            return self._unpack(out, shape)
         finally:
             self.lib.sxg_poa_batch_free(C.byref(out))
 
     # -- the sharded run in stages (inputs stay resident between executes) ------------------
     def upload_sharded(self, bases, seq_off, blk_off, weights, params, want_consensus=False, want_msa=False):
         """Every rank, SAME batch: deal the blocks by cost over the communicator's ranks, upload this rank's share."""
-        self._sh_in = self._mk_in(bases, seq_off, blk_off, weights, params, want_consensus, want_msa)
-        self._shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy())
-        if self.lib.sxg_poa_batch_upload_sharded(self.h, C.byref(self._sh_in)):
+        sh_in = self._mk_in(bases, seq_off, blk_off, weights, params, want_consensus, want_msa)
+        if self.lib.sxg_poa_batch_upload_sharded(self.h, C.byref(sh_in)):
             raise self._err("sxg_poa_batch_upload_sharded")
+        self._sh_in = sh_in
+        self._sh_shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy(), int(want_msa))
 
     def execute_sharded(self):
         """Collective: align the uploaded share, pack it, bring every rank's blob to rank 0 (RCCL)."""
@@ -468,7 +491,7 @@ class PoaEngine:
         try:
             if rc and (check or rc != -4):
                 raise self._err("sxg_poa_batch_download_sharded")
-            return self._unpack(out)
+            return self._unpack(out, self._sh_shape)
         finally:
             self.lib.sxg_poa_batch_free(C.byref(out))
 

@@ -37,7 +37,7 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
            "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa",
            "sxg_prep_default_params", "sxg_graph_prep", "sxg_blockset_identity_thresholds", "sxg_smooth_gfa_adaptive",
-           "sxg_smooth_maf_gfa_adaptive"]
+           "sxg_smooth_maf_gfa_adaptive", "sxg_smooth_maf_gfa_device_rows"]
 
 
 class PrepParams(C.Structure):
@@ -98,6 +98,7 @@ def load_library():
     L.sxg_smooth_gfa_adaptive.argtypes = [vp, vp, C.POINTER(SmoothParams), vp, vp, vp, vp, vp, C.POINTER(vp)]
     L.sxg_smooth_maf_gfa_adaptive.argtypes = [vp, vp, C.POINTER(SmoothParams), C.POINTER(MergeParams), vp, vp, vp, vp, vp, C.POINTER(vp),
                                               C.POINTER(vp), C.POINTER(C.c_int64)]
+    L.sxg_smooth_maf_gfa_device_rows.argtypes = L.sxg_smooth_maf_gfa_adaptive.argtypes
     L.sxg_blockset_identity_thresholds.argtypes = [vp, vp, C.c_int32, C.c_uint64, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     L.sxg_block_maf_rows.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
     L.sxg_block_maf.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
@@ -402,9 +403,11 @@ class Smoother:
         return thr[:n], used[:n]
 
     def smooth_maf_gfa(self, params, provider, merge_blocks=False, jaccard=1.0, preserve_unmerged=False, max_groups=50, header=None,
-                       identity=None):
+                       identity=None, device_rows=False):
         """The iteration with the in-order MAF consumer (block merging, flips): -> (GFA text, MAF text, flipped blocks).
-        identity: as for smooth_gfa."""
+        identity: as for smooth_gfa.  device_rows=True: sxg_smooth_maf_gfa_device_rows -- without merge_blocks the provider
+        builds the trimmed MSA rows (SXG_MSA_TRIMMED: the GPU engine does, on the device) and the iteration laces compact
+        block graphs; same outputs."""
         run, fre, ctx = provider
         ident = identity if identity is not None else (None, None)
         mp = MergeParams()
@@ -413,8 +416,8 @@ class Smoother:
         mp.max_merged_groups_in_memory = max_groups
         mp.maf_header = header.encode() if header is not None else None
         gfa, maf, nf = C.c_void_p(), C.c_void_p(), C.c_int64()
-        rc = self.L.sxg_smooth_maf_gfa_adaptive(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, ident[0], ident[1], C.byref(gfa),
-                                                C.byref(maf), C.byref(nf))
+        call = self.L.sxg_smooth_maf_gfa_device_rows if device_rows else self.L.sxg_smooth_maf_gfa_adaptive
+        rc = call(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, ident[0], ident[1], C.byref(gfa), C.byref(maf), C.byref(nf))
         if rc:
             raise SmoothError(self.L.sxg_smooth_last_error().decode())
         try:
