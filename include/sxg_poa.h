@@ -302,6 +302,9 @@ int sxg_poa_abi_version(void);
 int sxg_poa_measure_copy(sxg_poa_handle *h, uint64_t bytes, int reps, double *gbps);
 int sxg_poa_roctx_available(void);
 int sxg_poa_device_count(void);
+/* compute units of the engine's device: what the launch plan deals workgroups over (a round whose packed launches ask for at
+ * least one workgroup per unit runs neighbouring strip widths as one launch); -1: no handle */
+int sxg_poa_compute_units(sxg_poa_handle *h);
 const char *sxg_poa_last_error(void);
 
 int sxg_poa_create(int device, sxg_poa_handle **out);

@@ -43,20 +43,17 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "poa_dp16.hip.h"
+#include "poa_cost.h"   // BAND_WB, BAND_WF, BAND_WMAX, band_half_width: the host prices a banded block with them
 
 namespace sxg {
 
-constexpr int BAND_WB = 311;        // abpt->wb, src/smooth.cpp:269
-constexpr double BAND_WF = 0.03;    // abpt->wf, src/smooth.cpp:271
 constexpr int BAND_W_MAX = 11;      // widest strip (decree B2; poa_band_strip_width of the oracle)
 constexpr int BAND_WIN = 128;       // strips of the window (two per lane)
-constexpr int BAND_WMAX = 693;      // decree B1: cap of the half-width -- a band never exceeds the window (2 * 693 / 11 + 2 = 128 strips)
 // decree B2: strip width of a block whose longest sequence has maxlen letters
 __host__ __device__ inline int band_strip_width(int maxlen) {
     const int w0 = BAND_WB + (int)(BAND_WF * maxlen), w = w0 < BAND_WMAX ? w0 : BAND_WMAX;
     return 2 * w <= 756 ? 6 : (2 * w <= 1008 ? 8 : 11);
 }
-__host__ __device__ inline int band_half_width(int L) { const int w = BAND_WB + (int)(BAND_WF * L); return w < BAND_WMAX ? w : BAND_WMAX; }
 // strips the plane keeps per row: the widest band of a block whose longest sequence has maxlen letters
 __host__ __device__ inline int band_plane_strips(int maxlen, int W) { return plane_round4(2 * band_half_width(maxlen) / W + 2); }
 __host__ __device__ constexpr int band_lds_bytes(int W) { return LDS_CTL_BYTES + LDS_META_BYTES / 2 + 64 * W * 8; }

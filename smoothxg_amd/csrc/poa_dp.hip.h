@@ -183,7 +183,7 @@ struct DpBuffers {
     int band_mode;     // banded sweep: params.banded -- 1 = band around the backbone coordinate (B2), 2 = adaptive band (B4)
     int prio_rank;     // launch rank of this workgroup among its CU's co-residents (see sxg_rotate_prio)
     uint32_t* prio_board;          // this CU's progress board (PRIO_BOARD_SLOTS words) or nullptr
-    unsigned long long prio_rem0;  // estimated cells this workgroup still has to do, at row 0 of this sweep
+    unsigned long long prio_rem0;  // estimated work this workgroup still has to do, at row 0 of this sweep: rows x swept columns (poa_cost.h)
     unsigned long long* row_prof;  // SXG_ROW_PROF builds: 12 per-slot accumulators of row segments
 };
 constexpr int PRIO_BOARD_SLOTS = 16;   // co-resident workgroups per CU the board can tell apart
@@ -383,7 +383,7 @@ __device__ __forceinline__ void dp_fill(const Scoring& S, const RowsView& R, con
     const int kL = L - j0;                          // strip-local index of the end column L
 
     for (int i = 1; i <= N; ++i) {
-        if (B.prio_board) { if ((i & 127) == 1) sxg_balance_prio(B, (unsigned long long)i * (unsigned long long)L); }
+        if (B.prio_board) { if ((i & 127) == 1) sxg_balance_prio(B, (unsigned long long)i * (unsigned long long)Lpad); }   // rows done x swept columns (poa_cost.h)
         else if ((i & 63) == 1) sxg_rotate_prio(B.prio_rank);
         const int r = i - 1;
         if ((r & (META_CHUNK - 1)) == 0) {

@@ -250,7 +250,7 @@
     //  for the next row's descriptor, asked for a few instructions earlier: an exposed scalar-load latency in every row)
     if constexpr (TWIN) { const int d1_ = dnext[1]; asm volatile("" :: "s"(d1_)); }   /* (a use: the compiler waits for the load here) */
     for (int i = 1; i <= N; ++i) {
-        if (has_board) { if ((i & 127) == 1) sxg_balance_prio(B, (unsigned long long)i * (unsigned long long)L); }
+        if (has_board) { if ((i & 127) == 1) sxg_balance_prio(B, (unsigned long long)i * (unsigned long long)(2 * TW)); }   /* rows done x swept columns (poa_cost.h) */
         else if ((i & 63) == 1) sxg_rotate_prio(prio_rank);
         // (not const: behind a twin step the iteration goes on with the row that follows the pair)
         i32x8 dsc = dnext;
@@ -348,7 +348,7 @@
                 //  would have the step's whole state live across it.  At most one of the two is due.)
                 if (has_board) {
                     const int due = ((i + 1) & 127) == 1 ? i + 1 : ((((i + 2) & 127) == 1 && i + 2 <= N) ? i + 2 : 0);
-                    if (due) sxg_balance_prio(B, (unsigned long long)due * (unsigned long long)L);
+                    if (due) sxg_balance_prio(B, (unsigned long long)due * (unsigned long long)(2 * TW));
                 } else if (((i + 1) & 63) == 1 || (((i + 2) & 63) == 1 && i + 2 <= N)) sxg_rotate_prio(prio_rank);
                 if (p0 != i - 1) {
                     int hl;

@@ -203,7 +203,8 @@ struct BlockArgs {
     int num_cu;  // compute units of the device (co-residency of workgroups, sxg_rotate_prio)
     uint32_t* prio_board;              // [PRIO_BOARD_CUS][PRIO_BOARD_SLOTS] progress board, shared by the launches of a round
     int prio_base;                     // first board rank of this launch (the launches before it took the ranks below)
-    const unsigned long long* est;     // [n_work] estimated cells of work item wi (host cost model)
+    const unsigned long long* est;     // [n_work] estimated cost of work item wi, rows x swept columns (host cost model: poa_cost.h)
+    const unsigned long long* est_done; // [n_seqs] the part of its block's cost that lies before sequence s (the same model's prefix sums)
     int lds_bytes;                     // dynamic LDS of the launch (S7': the re-sort keeps its per-node states behind the control words)
     unsigned long long* blk_cycles;    // [n_blocks] shader-clock cycles the slot spent on block b (sxg_poa_batch_out::block_cycles)
     // packed sweep, adaptive band: the first `band_full` alignments of a block keep lay.band_strips strips per plane row, the
@@ -255,7 +256,6 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
         if (wi >= A.n_work) break;
         const int b = A.work[wi];
         const unsigned long long est_total = A.est ? A.est[wi] : 0ull;
-        unsigned long long done_cells = 0;
         const int s0 = A.blk_off[b], s1 = A.blk_off[b + 1];
         const int64_t base0 = A.seq_off[s0];
         const Scoring S = normalise(A.params[A.per_block_params ? b : 0]);
@@ -306,7 +306,11 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                 if (status != ST_OK) break;
                 PROF(1);
                 DpResult res;
-                V.B.prio_rem0 = est_total > done_cells ? est_total - done_cells : 0ull;
+                // what the block has left at row 0 of this sweep, in rows x swept columns: the host's estimate less its terms of the
+                // alignments that are done (a finished alignment advances it by ITS rows_k * cols_k of the model, so that it ends at
+                // 0; the sweep reports rows done x the columns it sweeps -- dp_fill_p16: T * 2 * Wk).  A repeat starts here again.
+                const unsigned long long done_cost = A.est_done ? A.est_done[s] : 0ull;
+                V.B.prio_rem0 = est_total > done_cost ? est_total - done_cost : 0ull;
                 if constexpr (RM == 3) {
                     // banded sweep (decrees B1-B3): one wave, the band slides with the rows; out-of-band cells do not
                     // exist, so the traceback cannot leave the kept cells
@@ -415,7 +419,6 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                 score = res.bi >= 0 ? res.best : 0;
             }
             if (t == 0) { A.score[s] = score; if (RM != 3 || N == 0 || len == 0) A.cells[s] = RM == 3 ? 0ull : (unsigned long long)N * (unsigned long long)len; }
-            done_cells += (unsigned long long)N * (unsigned long long)len;
             // (spoa's order: the re-sort below rebuilds order and ranks; AddAlignment leaves its own bookkeeping of them out)
             const bool spoa_order = (A.params[A.per_block_params ? b : 0].mode & SXG_ORDER_SPOA) != 0;
             if (CT.graph_batch == 16 || (CT.graph_batch == 8 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; add_alignment(c16, V.G, seq, len, A.weights ? A.weights[s] : 1u, A.paths + so, !spoa_order); }

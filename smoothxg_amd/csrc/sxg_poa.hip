@@ -23,6 +23,7 @@
 #include <rccl/rccl.h>   // (types and prototypes only: the library is opened on first use, see rccl_api)
 #include <dlfcn.h>
 #include "poa_kernels.hip.h"       // slot layout, launch arguments, the persistent kernels (device side)
+#include "poa_cost.h"              // a block's cost in its launch (rows x swept columns), the deal over CUs
 #include "poa_kern_tables.hip.h"   // kernel classes by geometry; instantiated in the kern_*.hip translation units
 #include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
@@ -319,6 +320,10 @@ struct sxg_poa_handle {
         d_paths, d_score, d_cells, d_cons, d_work, d_queue, d_arena, d_blk_cycles;
     DevBuf d_tmp_a, d_tmp_b, d_tmp_c, d_tmp_d;
     DevBuf d_board;   // the per-CU progress board (sxg_balance_prio) the launches of a round share
+    // a round's cost model, rows x swept columns (poa_cost.h): per block in the launch it runs in, and per sequence the part of its
+    // block's cost that lies before it (BlockArgs::est_done -- one array for all launches of the round: a block is in one of them)
+    std::vector<uint64_t> blk_cost, seq_done;
+    DevBuf d_est_done;
     // block graphs (want_block_graph): inputs, outputs in per-block layouts, the per-block counts of the last execute
     int want_block_graph = 0, bg_cons_visited_only = 0;
     std::shared_ptr<PinPool> pins;   // pinned host buffers lent to results (created with the handle)
@@ -428,6 +433,7 @@ extern "C" const char* sxg_poa_last_error(void) {
     { std::lock_guard<std::mutex> lk(g_err_mu); g_err_ret = g_err_any; }
     return g_err_ret.c_str();
 }
+extern "C" int sxg_poa_compute_units(sxg_poa_handle* h) { return h ? h->num_cu : -1; }
 extern "C" int sxg_poa_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -463,7 +469,7 @@ static void release_all(sxg_poa_handle* h) {
     DevBuf* bufs[] = {&h->d_blk_off, &h->d_seq_off, &h->d_bases, &h->d_weights, &h->d_params, &h->d_status, &h->d_nn,
                       &h->d_ne, &h->d_nc, &h->d_node_code, &h->d_node_rank, &h->d_node_group, &h->d_edge_tail,
                       &h->d_edge_head, &h->d_edge_w, &h->d_paths, &h->d_score, &h->d_cells, &h->d_cons, &h->d_work,
-                      &h->d_queue, &h->d_arena, &h->d_blk_cycles, &h->d_tmp_a, &h->d_tmp_b, &h->d_tmp_c, &h->d_tmp_d, &h->d_board, &h->d_trim, &h->d_bg_no, &h->d_bg_eo,
+                      &h->d_queue, &h->d_arena, &h->d_blk_cycles, &h->d_tmp_a, &h->d_tmp_b, &h->d_tmp_c, &h->d_tmp_d, &h->d_board, &h->d_est_done, &h->d_trim, &h->d_bg_no, &h->d_bg_eo,
                       &h->d_bg_len, &h->d_bg_od, &h->d_bg_id, &h->d_bg_seq, &h->d_bg_eto, &h->d_bg_steps, &h->d_bg_nsteps, &h->d_bg_cons,
                       &h->d_bg_counts, &h->d_bg_work, &h->d_bg_queue, &h->d_bg_arena,
                       &h->d_msa_no, &h->d_msa_tmp, &h->d_msa_col, &h->d_msa_be, &h->d_msa_off, &h->d_msa_items, &h->d_msa_work, &h->d_msa_queue, &h->d_msa};
@@ -762,31 +768,12 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     int rc;
     if (!P.kern) return fail(SXG_E_INVALID, P.why);
     if ((rc = R.arena.ensure((size_t)P.n_slots * P.lay.total))) return rc;
-    // Workgroup k runs on CU k mod #CU (measured, profiles/tools/slot_report.py): when the slots do not
-    // divide evenly, the CUs with one workgroup less run theirs faster -- they get the costliest blocks, so
-    // that those are not what the launch ends on.  P.work arrives sorted by cost, largest first.
-    {
-        const int64_t ns = P.n_slots, ncu = std::max(h->num_cu, 1);
-        const int64_t rem = ns % ncu, full = ns / ncu;
-        if (rem > 0 && full >= 1 && (int64_t)P.work.size() >= ns) {
-            std::vector<int32_t> first((size_t)ns, -1);
-            size_t next = 0;
-            for (int64_t p = 0; p < ns; ++p)          // light CUs first
-                if (p % ncu >= rem && p / ncu < full) first[(size_t)p] = P.work[next++];
-            // the crowded CUs are dealt the rest in snake order (round 0 left to right, round 1 right to
-            // left, ...), which evens out the sum of costs per CU
-            for (int64_t round = 0; round <= full; ++round)
-                for (int64_t c = 0; c < rem; ++c) {
-                    const int64_t cu = (round & 1) ? rem - 1 - c : c, p = round * ncu + cu;
-                    if (p < ns && first[(size_t)p] < 0) first[(size_t)p] = P.work[next++];
-                }
-            std::copy(first.begin(), first.end(), P.work.begin());
-        }
-    }
+    // light CUs first, then snake: deal_over_cus (poa_cost.h).  P.work arrives sorted by the blocks' cost IN THIS LAUNCH, largest first.
+    deal_over_cus(P.work, P.n_slots, std::max(h->num_cu, 1));
     if ((rc = R.work.ensure(4 * P.work.size())) || (rc = R.queue.ensure(256)) || (rc = R.est.ensure(8 * P.work.size()))) return rc;
     HIPCHK(hipMemcpyAsync(R.work.p, P.work.data(), 4 * P.work.size(), hipMemcpyHostToDevice, R.stream));
     P.est.resize(P.work.size());
-    for (size_t k = 0; k < P.work.size(); ++k) P.est[k] = (unsigned long long)std::max(h->meta[P.work[k]].cost, 1.0);
+    for (size_t k = 0; k < P.work.size(); ++k) P.est[k] = (unsigned long long)std::max<uint64_t>(h->blk_cost[(size_t)P.work[k]], 1);
     HIPCHK(hipMemcpyAsync(R.est.p, P.est.data(), 8 * P.est.size(), hipMemcpyHostToDevice, R.stream));
     HIPCHK(hipMemsetAsync(R.queue.p, 0, 256, R.stream));
     BlockArgs A;
@@ -811,6 +798,7 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     A.prio_board = getenv("SXG_POA_NO_BALANCE") ? nullptr : h->d_board.as<uint32_t>();
     A.prio_base = prio_base;
     A.est = R.est.as<unsigned long long>();
+    A.est_done = h->d_est_done.as<unsigned long long>();   // (uploaded on h->stream in front of ev0, which this launch waits for)
     A.blk_cycles = h->d_blk_cycles.as<unsigned long long>();
     A.lds_bytes = getenv("SXG_POA_RESORT_NO_LDS") ? 0 : P.smem;   // (test knob: the S7' re-sort keeps its states in the slot's scratch, as it does for graphs beyond its LDS)
     band_adapt_args(A);
@@ -1168,13 +1156,26 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         // config 2 (three launches of 1-2 waves per block) still lose 15 % apart.  So: wide geometries merge only within 8 %,
         // the others within 25 % as before.
         const double merge_env = getenv("SXG_POA_MERGE") ? atof(getenv("SXG_POA_MERGE")) : 0.0;
-        const bool merge_w2 = getenv("SXG_POA_MERGE_WIDTH2") && atoi(getenv("SXG_POA_MERGE_WIDTH2")) != 0 && width2_enabled();
+        // Round 14: neighbouring widths -- a geometry whose strip width IS the second width of a wider one's class at the same wave
+        // count (the headline's W = 10 beside its W = 11) -- run as ONE launch wherever there is something to deal: in a round
+        // whose packed launches together ask for at least one workgroup per CU.  Inside the wider class every alignment of the
+        // joined blocks runs at their own width, so the reason to keep wide geometries apart (above) does not apply; one launch
+        // is what the deal over CUs models ("workgroup k runs on CU k mod #CU": two launches side by side each pick their own
+        // light CUs, and the hardware puts the second one's workgroups wherever there is room), one block queue has no launch
+        // that drains before the other, and the priority board ranks all co-residents by one cost.  Below that size nothing
+        // shares a CU and the launches stay apart.  SXG_POA_MERGE_WIDTH2=0: never (the plan of round 13), =1: at any size.
+        // (measured: profiles/r15.)
+        bool merge_w2 = width2_enabled();
+        if (const char* e = getenv("SXG_POA_MERGE_WIDTH2")) merge_w2 = merge_w2 && atoi(e) != 0;
+        else {
+            size_t packed = 0;
+            for (const auto& q : plans) if (q.variant.RM == 2) packed += q.work.size();
+            merge_w2 = merge_w2 && packed >= (size_t)std::max(h->num_cu, 1);
+        }
         for (size_t i = 0; i < plans.size(); ++i)
             for (size_t j = i + 1; j < plans.size();) {
                 const LaunchPlan &a = plans[i], &b = plans[j];
-                // (round 12, SXG_POA_MERGE_WIDTH2=1: a geometry whose strip width IS the second width of a wider one's class at the same
-                //  wave count joins it -- inside that launch its alignments all run at their own width, so the reason above is gone and
-                //  the cost-ordered dealing over CUs sees all blocks.  Off by default: see DESIGN section 5, round 12.)
+                // (neighbouring widths: see merge_w2 above)
                 const bool join_w2 = merge_w2 && a.variant.NW == b.variant.NW && b.variant.W == class_w2(CLASS_BLOCK, a.variant, a.sw);
                 if (same_kind(a.variant, b.variant) && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
                     (join_w2 || (double)b.variant.Lpad() >= (merge_env > 0 ? merge_env : (a.variant.Lpad() >= 4096 ? 0.92 : 0.75)) * (double)a.variant.Lpad())) {
@@ -1197,9 +1198,18 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         }
         const uint64_t budget = arena_budget(h);
         uint64_t want_bytes = 0;
+        // A block's cost depends on the launch it ended up in (poa_cost.h: rows x swept columns -- a W = 10 block merged into the
+        // W = 11 class runs every alignment at W2 = 10, one spread over twice the waves half the strip width), so it is priced
+        // here, from the launch's variant as prepare_plan settled it, and the launch's blocks are sorted by THAT cost.
+        h->blk_cost.assign((size_t)std::max(nb, 1), 0);
+        h->seq_done.assign((size_t)std::max<int64_t>(h->n_seqs, 1), 0);
         for (auto& pl : plans) {
-            std::stable_sort(pl.work.begin(), pl.work.end(), [&](int a, int b) { return h->meta[a].cost > h->meta[b].cost; });
             prepare_plan(h, pl, pl.tier);
+            const Variant& v = pl.variant;
+            for (int b : pl.work)
+                h->blk_cost[(size_t)b] = block_cost(h->h_seq_off.data() + h->h_blk_off[b], h->h_blk_off[b + 1] - h->h_blk_off[b], v.RM, v.T(), v.W, v.W2,
+                                                    h->seq_done.data() + h->h_blk_off[b]);
+            std::stable_sort(pl.work.begin(), pl.work.end(), [&](int a, int b) { return h->blk_cost[(size_t)a] > h->blk_cost[(size_t)b]; });
             want_bytes += (uint64_t)pl.want_slots * pl.lay.total;
         }
         // A geometry whose single arena does not fit the budget fails ITS blocks (per-block status, as the
@@ -1222,14 +1232,13 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         // running side by side should end together, so their WAVES are made proportional to their
         // work (cost model of SURVEY 8e): slots_p = lambda * cost_p / waves_per_slot_p, with the largest
         // lambda that respects the arena budget and the wave capacity of the device.
-        // (a block swept by a wider geometry than its own -- merged launches -- costs the columns of THAT geometry.  A launch of a
-        //  dual-width class is priced at its full width as well, which overestimates it: most of its alignments sweep W2, and the
-        //  headline's W = 11 launch now ends ~2 % before the W = 10 launch beside it.  Pricing by the per-alignment width is left
-        //  to a later round -- DESIGN section 5, round 12.)
+        // (the blocks' costs in THEIR launch, as priced above: a block swept by a wider geometry than its own -- merged launches --
+        //  costs the columns of that geometry, and an alignment that a dual-width class sweeps at W2 costs W2's.  Until round 14
+        //  a dual-width launch was priced at its full width, cost * Lpad / maxlen, and the headline's W = 11 launch, 80 % of whose
+        //  sweeps run at W2 = 10, ended ~2 % before the W = 10 launch beside it.)
         std::vector<double> pcost(plans.size(), 0.0);
         for (size_t i = 0; i < plans.size(); ++i)
-            for (int b : plans[i].work)
-                pcost[i] += std::max(h->meta[b].cost, 1.0) * (plans[i].variant.RM == 3 ? 1.0 : (double)plans[i].variant.Lpad() / (double)std::max(h->meta[b].maxlen, 1));
+            for (int b : plans[i].work) pcost[i] += (double)std::max<uint64_t>(h->blk_cost[(size_t)b], 1);
         const int oversub = getenv("SXG_POA_OVERSUB") ? std::max(1, atoi(getenv("SXG_POA_OVERSUB"))) : 2;
         auto slots_at = [&](size_t i, double lambda) {
             const double s = lambda * pcost[i] / (double)plans[i].variant.NW;
@@ -1275,6 +1284,8 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
             int rcb = h->d_board.ensure(board_bytes);
             if (rcb) return rcb;
             HIPCHK(hipMemsetAsync(h->d_board.p, 0, board_bytes, h->stream));
+            if ((rcb = h->d_est_done.ensure(8 * h->seq_done.size()))) return rcb;
+            HIPCHK(hipMemcpyAsync(h->d_est_done.p, h->seq_done.data(), 8 * h->seq_done.size(), hipMemcpyHostToDevice, h->stream));
         }
         HIPCHK(hipEventRecord(h->ev0, h->stream));
         int prio_base = 0;

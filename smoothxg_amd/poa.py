@@ -125,7 +125,7 @@ MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
 ST_TOO_LONG = 5
 MSA_FULL, MSA_TRIMMED = 1, 2   # SXG_MSA_FULL / SXG_MSA_TRIMMED: values of want_msa (True = the full MSA)
 
-EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_last_error", "sxg_poa_create",
+EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_compute_units", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
            "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_get_twin_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
@@ -161,6 +161,7 @@ def load_library(build_if_missing=True):
     L.sxg_poa_batch_device_view.argtypes = [vp, C.POINTER(DeviceView)]
     L.sxg_poa_align_batch.argtypes = [vp, C.POINTER(AlignIn), C.POINTER(AlignOut)]
     L.sxg_poa_align_free.argtypes = [C.POINTER(AlignOut)]
+    L.sxg_poa_compute_units.argtypes = [vp]
     L.sxg_poa_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.sxg_poa_get_width_stats.argtypes = [vp, C.POINTER(WidthStats)]
     L.sxg_poa_get_twin_stats.argtypes = [vp, C.POINTER(TwinStats)]
@@ -320,6 +321,10 @@ class PoaEngine:
         self.lib.sxg_poa_get_twin_stats(self.h, C.byref(tw))
         st.update(twin_steps=tw.twin_steps, join_rows=tw.join_rows)
         return st
+
+    def compute_units(self):
+        """Compute units of the engine's device (what the launch plan deals workgroups over)."""
+        return int(self.lib.sxg_poa_compute_units(self.h))
 
     def msa_geometry(self):
         """sxg_poa_msa_geometry: (kept letters of a row per work item of the rows kernel, bytes of its on-chip window)."""
