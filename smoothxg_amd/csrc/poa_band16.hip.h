@@ -172,7 +172,7 @@ __device__ __noinline__ DpResult dp_fill_band16(const Scoring S, const RowsView 
     };
 
 #ifdef SXG_ROW_PROF
-    unsigned long long racc[8] = {0};
+    unsigned long long racc[ROWP_SEGS] = {0};
 #define BP_MARK(seg) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long tn_ = __builtin_readcyclecounter(); racc[seg] += tn_ - rt_; rt_ = tn_; } while (0)
 #else
 #define BP_MARK(seg) do { } while (0)
@@ -612,7 +612,7 @@ __device__ __noinline__ DpResult dp_fill_band16(const Scoring S, const RowsView 
     }
 #ifdef SXG_ROW_PROF
     if (lane == 0 && B.row_prof)
-        for (int k = 0; k < 8; ++k) B.row_prof[k] += racc[k];
+        for (int k = 0; k < ROWP_SEGS; ++k) B.row_prof[k] += racc[k];
 #endif
 #undef BP_MARK
     (void)pbl; (void)pbh;

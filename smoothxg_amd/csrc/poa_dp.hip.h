@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "poa_types.h"
+#include "poa_slot_prof.h"
 
 namespace sxg {
 
@@ -184,7 +185,7 @@ struct DpBuffers {
     int prio_rank;     // launch rank of this workgroup among its CU's co-residents (see sxg_rotate_prio)
     uint32_t* prio_board;          // this CU's progress board (PRIO_BOARD_SLOTS words) or nullptr
     unsigned long long prio_rem0;  // estimated work this workgroup still has to do, at row 0 of this sweep: rows x swept columns (poa_cost.h)
-    unsigned long long* row_prof;  // SXG_ROW_PROF builds: 12 per-slot accumulators of row segments
+    unsigned long long* row_prof;  // SXG_ROW_PROF builds: the slot's row profile, ROWP_WORDS (13) accumulators (poa_slot_prof.h)
 };
 constexpr int PRIO_BOARD_SLOTS = 16;   // co-resident workgroups per CU the board can tell apart
 constexpr int PRIO_BOARD_CUS = 4096;   // __smid() & 0xfff

@@ -806,8 +806,8 @@ __device__ __noinline__ int traceback_p16(const RowsView R, const DpBuffers B, c
     if (lane == 0) { ctl[TBM_FLAG] = miss ? 1 : 0; ctl[TBM_ROW] = miss_row; ctl[TBM_DELTA] = miss_delta; ctl[TBM_RANGE] = range ? 1 : 0; }
 #ifdef SXG_ROW_PROF
     if (lane == 0 && B.row_prof) {
-        B.row_prof[8] += tb_steps; B.row_prof[9] += tb_loads;
-        B.row_prof[10] += __builtin_readcyclecounter() - tb_t0; B.row_prof[11] += tb_ld; B.row_prof[12] += tb_hits;
+        B.row_prof[ROWP_TB_STEPS] += tb_steps; B.row_prof[ROWP_TB_LOADS] += tb_loads;
+        B.row_prof[ROWP_TB_CYCLES] += __builtin_readcyclecounter() - tb_t0; B.row_prof[ROWP_TB_FILL_CYCLES] += tb_ld; B.row_prof[ROWP_TB_HITS] += tb_hits;
     }
 #endif
     __builtin_amdgcn_s_setprio(0);

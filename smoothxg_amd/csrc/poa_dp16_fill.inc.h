@@ -231,7 +231,7 @@
 #define P16_PROF_FETCH() do { } while (0)
 #endif
 #ifdef SXG_ROW_PROF
-    unsigned long long racc[8] = {0};  // per row segment; scalar registers (s_memtime deltas)
+    unsigned long long racc[ROWP_SEGS] = {0};  // per row segment; scalar registers (s_memtime deltas)
 #define RP_MARK(seg) do { const unsigned long long tn_ = __builtin_readcyclecounter(); racc[seg] += tn_ - rt_; rt_ = tn_; } while (0)
 #else
 #define RP_MARK(seg) do { } while (0)
@@ -512,7 +512,7 @@
 #undef P16_LDS_ROW
 #ifdef SXG_ROW_PROF
     if (t == 0 && B.row_prof)
-        for (int k = 0; k < 8; ++k) B.row_prof[k] += racc[k];
+        for (int k = 0; k < ROWP_SEGS; ++k) B.row_prof[k] += racc[k];
 #endif
 #undef RP_MARK
 #undef P16_DEC

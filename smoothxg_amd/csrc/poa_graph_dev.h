@@ -15,6 +15,7 @@
 //   int atomic_add(int32_t* p, int v);
 #pragma once
 #include "poa_types.h"
+#include "poa_slot_prof.h"
 
 namespace sxg {
 
@@ -443,6 +444,7 @@ SXG_HD_PHASE int spoa_walk_root(const GraphView& G, WP W, const int s0, SXG_GP i
     return w;
 }
 
+// (k: one of the RSP_PHASES phases of the slot's re-sort profile, poa_slot_prof.h)
 #if defined(SXG_RESORT_PROF) && defined(__HIP_DEVICE_COMPILE__)
 #define SXG_RSP(k) do { if (t == 0 && rprof) { const unsigned long long now_ = (unsigned long long)clock64(); rprof[k] += now_ - rt0_; rt0_ = now_; } } while (0)
 #define SXG_RSP_DECL unsigned long long rt0_ = (unsigned long long)clock64()
@@ -610,7 +612,7 @@ SXG_HD void spoa_resort_par(Ctx& c, const GraphView& G, WP W, const int n, const
         }
         changed = c.reduce_max(changed);   // (also the barrier between the rounds)
 #if defined(SXG_RESORT_PROF) && defined(__HIP_DEVICE_COMPILE__)
-        if (t == 0 && rprof) rprof[5] += 1;
+        if (t == 0 && rprof) rprof[RSP_ROUNDS] += 1;
 #endif
         if (!changed) break;
     }

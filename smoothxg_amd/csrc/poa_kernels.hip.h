@@ -10,6 +10,7 @@
 
 #include "../../include/sxg_poa.h"
 #include "poa_classes.h"
+#include "poa_slot_prof.h"
 #include "poa_dp.hip.h"
 #include "poa_dp16.hip.h"
 #include "poa_band16.hip.h"
@@ -60,7 +61,7 @@ inline SlotLayout make_layout(int nodes_cap, int rows_cap, int pool_slots, int s
     const size_t C = (size_t)nodes_cap + 4, S = (size_t)std::max(nodes_cap, Lpad) + 4, Rr = (size_t)rows_cap + 4;
     L.scratch_len = (int)S;
     size_t cur = 0;
-    L.hdr = lay(cur, 512);
+    L.hdr = lay(cur, SLOT_HDR_BYTES);
     L.code = lay(cur, C);
     L.rank = lay(cur, 4 * C); L.order = lay(cur, 4 * C); L.order_tmp = lay(cur, 4 * C); L.leader = lay(cur, 4 * C);
     L.gmem = lay(cur, 20 * C);
@@ -262,15 +263,16 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
         if (t == 0) { *V.G.n_nodes = 0; *V.G.n_edges = 0; }
         __syncthreads();
         int status = ST_OK;
-        unsigned long long* prof = (unsigned long long*)(A.arena + (size_t)blockIdx.x * A.lay.total + A.lay.hdr + 64);
-        V.B.row_prof = prof + 28;
+        unsigned long long* prof = (unsigned long long*)(A.arena + (size_t)blockIdx.x * A.lay.total + A.lay.hdr + SLOT_PROF_OFF);
+        V.B.row_prof = prof + SP_ROW;
         if ((t & 63) == 0) {  // placement of every wave (debug dump): smid | raw HW_ID, and the slot's start
-            prof[10 + (t >> 6)] = ((unsigned long long)__smid() << 32) | (unsigned long long)__builtin_amdgcn_s_getreg(GETREG_IMMED(31, 0, HW_ID));
-            if (t == 0 && prof[8] == 0) { prof[8] = (unsigned long long)wall_clock64(); prof[6] = (unsigned long long)clock64(); }
+            prof[SP_WAVE + (t >> 6)] = ((unsigned long long)__smid() << 32) | (unsigned long long)__builtin_amdgcn_s_getreg(GETREG_IMMED(31, 0, HW_ID));
+            if (t == 0 && prof[SP_WALL0] == 0) { prof[SP_WALL0] = (unsigned long long)wall_clock64(); prof[SP_CLOCK0] = (unsigned long long)clock64(); }
         }
         unsigned long long tc0 = clock64(), tc1;
         const unsigned long long tblk0 = tc0;
         int band_drift = 0, band_min = 0;   // packed sweep, adaptive band: largest drift of the block's walks, least width after a repeat (both in columns)
+// (k: one of the SP_PHASES phase words of the slot profile, poa_slot_prof.h)
 #define PROF(k) do { if (t == 0) { tc1 = clock64(); prof[k] += tc1 - tc0; tc0 = tc1; } } while (0)
         for (int s = s0; s < s1 && status == ST_OK; ++s) {
             const int64_t so = A.seq_off[s];
@@ -289,7 +291,7 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                 break;
             }
             if (N > 0 && len > 0) {
-                PROF(0);
+                PROF(SP_OTHER);
                 const int band_mode = RM == 3 ? (int)A.params[A.per_block_params ? b : 0].banded : 0;   // 1 = B2, 2 = adaptive (B4)
                 // (workgroups of one and two waves take more elements per thread and step: see WgCtxT)
                 const int hinted_ = RM == 3 ? (band_mode == 2 ? 3 : 2) : (RM == 2 ? 1 : 0);
@@ -298,13 +300,13 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                     static_assert(CT.graph_batch == 4, "twin classes: the plain workgroup context");
                     unsigned long long n2 = 0;   // twin steps | join rows << 32 among this thread's rows (sxg_poa_get_twin_stats)
                     status = prep_rows_twin(ctx, V.G, V.R, caps, hinted_, A.twin, &n2);
-                    if (status == ST_OK && n2) atomicAdd(&prof[55], n2);
+                    if (status == ST_OK && n2) atomicAdd(&prof[SP_TWIN], n2);
                 }
                 else if (CT.graph_batch == 16 || (CT.graph_batch == 8 && T <= 64)) { WgCtxT<16> c16{ctx.lds}; status = prep_rows(c16, V.G, V.R, caps, hinted_); }
                 else if (CT.graph_batch == 8) { WgCtxT<8> c8{ctx.lds}; status = prep_rows(c8, V.G, V.R, caps, hinted_); }
                 else status = prep_rows(ctx, V.G, V.R, caps, hinted_);
                 if (status != ST_OK) break;
-                PROF(1);
+                PROF(SP_PREP_ROWS);
                 DpResult res;
                 // what the block has left at row 0 of this sweep, in rows x swept columns: the host's estimate less its terms of the
                 // alignments that are done (a finished alignment advances it by ITS rows_k * cols_k of the model, so that it ends at
@@ -318,14 +320,14 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                     V.B.band_mode = band_mode;
                     res = dp_fill_band16<CVX, W, SW, SW ? CB : 4>(S, V.R, N, seq, len, V.B, smem, A.cells + s);
                     __syncthreads();
-                    PROF(2);
+                    PROF(SP_DP_FILL);
                     if (t == 0) lds[TBM_FLAG] = 0;
                     __syncthreads();
                     if (res.bi >= 0)
                         traceback_p16<false, W, CVX, true, SW ? CB : 4>(V.R, V.B, S, seq, len, res.best, T, min(256, (len << 8) / max(N, 1)), res.bi, res.bj,
                                                                         V.G.posnode, nullptr, nullptr, smem);
                     __syncthreads();
-                    PROF(3);
+                    PROF(SP_TRACEBACK);
                     // (a cell outside a row's band does not exist for the banded walk, so it cannot miss: if it ever reports one,
                     //  that is a defect -- the block fails with its own status instead of being re-run on a sweep with other semantics)
                     if (lds[TBM_FLAG]) { status = ST_INTERNAL; break; }
@@ -361,8 +363,8 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                         for (int att = 0;; ++att) {
                             V.B.band_strips = bs;
                             if (t == 0) {
-                                prof[47] += (unsigned long long)bs; prof[48] += 1;
-                                prof[49 + narrow] += 1; prof[51 + narrow] += (unsigned long long)(T * 2 * Wk); prof[53 + narrow] += (unsigned long long)N * (unsigned long long)(T * 2 * Wk);
+                                prof[SP_BAND_STRIPS] += (unsigned long long)bs; prof[SP_BAND_SWEEPS] += 1;
+                                prof[SP_SWEEPS + narrow] += 1; prof[SP_SWEPT_COLS + narrow] += (unsigned long long)(T * 2 * Wk); prof[SP_SWEPT_CELLS + narrow] += (unsigned long long)N * (unsigned long long)(T * 2 * Wk);
                             }
 #ifdef SXG_EXP
                             // (development: a sweep with parts switched off in front of the real one -- see dp_fill_p16's EXP)
@@ -371,14 +373,14 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                             if constexpr (CT.twin != 0) res = dp_fill_p16_twin<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
                             else res = dp_fill_p16<Wk, CVX, SW, CB, CT.rp, CT.tfix, DS>(S, V.R, N, seq, len, V.B, smem);
                             __syncthreads();
-                            PROF(2);
+                            PROF(SP_DP_FILL);
                             if (t == 0) { lds[TBM_FLAG] = 0; lds[TBM_RANGE] = 0; }
                             __syncthreads();
                             if (t < 64 && res.bi >= 0)
                                 traceback_p16<false, Wk, CVX, false, CB>(V.R, V.B, S, seq, len, res.best, T, min(256, (len << 8) / max(N, 1)), res.bi, res.bj,
                                                                          V.G.posnode, nullptr, nullptr, smem);
                             __syncthreads();
-                            PROF(3);
+                            PROF(SP_TRACEBACK);
                             if (lds[TBM_RANGE]) { status = ST_RANGE_OVERFLOW; break; }
                             if (!lds[TBM_FLAG]) break;
                             if (att == 5) { status = ST_BAND_MISS; break; }
@@ -386,7 +388,7 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                             __syncthreads();
                             for (int r2 = t; r2 < mrow; r2 += T) V.R.meta[8 * (size_t)r2 + 7] += mdelta;
                             for (int i2 = t; i2 < len; i2 += T) V.G.posnode[i2] = -1;
-                            if (t == 0) prof[27] += 1;
+                            if (t == 0) prof[SP_HINT_REPEATS] += 1;
                             bs = min(plane_round4(2 * bs), bs_cap);
                             band_min = bs * Wk;
                             __syncthreads();
@@ -411,10 +413,10 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                 } else {
                     dp_fill<W, CVX, H16, SW>(S, V.R, N, seq, len, V.B, smem, A.park_in_lds != 0, A.pf_off, res);
                     __syncthreads();
-                    PROF(2);
+                    PROF(SP_DP_FILL);
                     if (t == 0 && res.bi >= 0) traceback<false>(V.R, V.B, T, W, S.sw, res.bi, res.bj, V.G.posnode, nullptr, nullptr);
                     __syncthreads();
-                    PROF(3);
+                    PROF(SP_TRACEBACK);
                 }
                 score = res.bi >= 0 ? res.best : 0;
             }
@@ -428,12 +430,12 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                 typedef __attribute__((address_space(3))) uint8_t lds_u8;
                 // (N nodes before this alignment; the block's first re-sort builds everything, the later ones what the alignment touched)
                 spoa_resort(ctx, V.G, (lds_u8*)(size_t)((unsigned)__builtin_amdgcn_groupstaticsize() + (unsigned)LDS_CTL_BYTES), A.lds_bytes - LDS_CTL_BYTES,
-                            (int)(A.seq_off[s0 + 1] - A.seq_off[s0]), len, N, s == s0, prof + 41);
+                            (int)(A.seq_off[s0 + 1] - A.seq_off[s0]), len, N, s == s0, prof + SP_RESORT);
                 __syncthreads();
             }
-            PROF(4);
+            PROF(SP_ADD_ALIGNMENT);
         }
-        PROF(0);
+        PROF(SP_OTHER);
         __syncthreads();
         // results of the block
         const int N = *V.G.n_nodes, E = *V.G.n_edges;
@@ -454,8 +456,8 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
         } else if (t == 0) { A.n_nodes[b] = 0; A.n_edges[b] = 0; A.n_cons[b] = 0; }
         if (t == 0) { A.status[b] = status; if (A.blk_cycles) A.blk_cycles[b] = (unsigned long long)clock64() - tblk0; }
         if (t == 0 && V.B.prio_board) __hip_atomic_store(V.B.prio_board + V.B.prio_rank, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        PROF(5);
-        if (t == 0) { prof[9] = (unsigned long long)wall_clock64(); prof[7] = (unsigned long long)clock64(); }
+        PROF(SP_OUTPUT);
+        if (t == 0) { prof[SP_WALL1] = (unsigned long long)wall_clock64(); prof[SP_CLOCK1] = (unsigned long long)clock64(); }
 #undef PROF
     }
 }

@@ -747,18 +747,26 @@ static void prepare_plan(sxg_poa_handle* h, LaunchPlan& P, int attempt) {
     P.want_slots = std::min<int64_t>((int64_t)P.work.size(), (int64_t)h->num_cu * P.per_cu);
 }
 
+// The profiles of a launch's slots (poa_slot_prof.h), SLOT_PROF_WORDS words per slot: one strided copy out of the slot headers.
+static int fetch_slot_prof(const LaunchPlan& P, const PlanRes& R, std::vector<unsigned long long>& prof) {
+    prof.resize((size_t)std::max<int64_t>(P.n_slots, 0) * SLOT_PROF_WORDS);
+    if (!prof.empty())
+        HIPCHK(hipMemcpy2D(prof.data(), SLOT_PROF_BYTES, R.arena.as<uint8_t>() + P.lay.hdr + SLOT_PROF_OFF, P.lay.total, SLOT_PROF_BYTES, (size_t)P.n_slots,
+                           hipMemcpyDeviceToHost));
+    return SXG_OK;
+}
+
 // The shader clock a launch ran at: every slot reads the core-clock counter (s_memtime) and the constant 100 MHz counter
 // (s_memrealtime) when it starts and when it ends; cycles / ticks * 100 MHz, over a sample of slots.  bench.py
 // prices the VALU roof with it -- the boxes of the pool sustain different clocks under this kernel.
-static int sample_clock(const LaunchPlan& P, const PlanRes& R) {
+static int sample_clock(const LaunchPlan& P, const std::vector<unsigned long long>& prof) {
     unsigned long long cyc = 0, ticks = 0;
     const int64_t step = std::max<int64_t>(1, P.n_slots / 24);
     for (int64_t sl = 0; sl < P.n_slots; sl += step) {
-        unsigned long long v[10];
-        if (hipMemcpy(v, R.arena.as<uint8_t>() + (size_t)sl * P.lay.total + P.lay.hdr + 64, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-        if (v[9] <= v[8] || v[7] <= v[6]) continue;
-        cyc += v[7] - v[6];
-        ticks += v[9] - v[8];
+        const unsigned long long* v = prof.data() + (size_t)sl * SLOT_PROF_WORDS;
+        if (v[SP_WALL1] <= v[SP_WALL0] || v[SP_CLOCK1] <= v[SP_CLOCK0]) continue;
+        cyc += v[SP_CLOCK1] - v[SP_CLOCK0];
+        ticks += v[SP_WALL1] - v[SP_WALL0];
     }
     return ticks ? (int)((double)cyc / (double)ticks * 100.0 + 0.5) : 0;
 }
@@ -804,7 +812,7 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     band_adapt_args(A);
     A.twin = twin_enabled() ? 1 : 0;
     // every slot's header (counters, phase times, clock readings) starts a launch at zero: one strided memset
-    HIPCHK(hipMemset2DAsync(R.arena.as<uint8_t>() + P.lay.hdr, P.lay.total, 0, 512, (size_t)P.n_slots, R.stream));
+    HIPCHK(hipMemset2DAsync(R.arena.as<uint8_t>() + P.lay.hdr, P.lay.total, 0, SLOT_HDR_BYTES, (size_t)P.n_slots, R.stream));
     HIPCHK(hipStreamWaitEvent(R.stream, h->ev0, 0));
     HIPCHK(hipEventRecord(R.e0, R.stream));
     hipLaunchKernelGGL(P.kern, dim3((unsigned)P.n_slots), dim3(V.T()), (size_t)P.smem, R.stream, A);
@@ -814,46 +822,40 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     return SXG_OK;
 }
 
-// Packed sweep: what the launch's sweeps ran at, from the slot headers (words 27 and 49..55 of the counters the kernel keeps
-// there -- poa_kernels.hip.h), gathered with one strided copy.  Word 55: twin steps | join rows << 32 of the rows the slot prepared.
-static int width_stats_of(const LaunchPlan& P, const PlanRes& R, sxg_poa_width_stats& w, sxg_poa_twin_stats* tw = nullptr) {
-    if (P.variant.RM != 2 || P.n_slots <= 0) return SXG_OK;
-    constexpr int K0 = 27, K1 = 56;
-    std::vector<unsigned long long> v((size_t)P.n_slots * (K1 - K0));
-    HIPCHK(hipMemcpy2D(v.data(), (K1 - K0) * 8, R.arena.as<uint8_t>() + P.lay.hdr + 64 + K0 * 8, P.lay.total, (K1 - K0) * 8, (size_t)P.n_slots, hipMemcpyDeviceToHost));
+// Packed sweep: what the launch's sweeps ran at, from its slots' profiles (fetch_slot_prof).
+static void width_stats_of(const LaunchPlan& P, const std::vector<unsigned long long>& prof, sxg_poa_width_stats& w, sxg_poa_twin_stats* tw = nullptr) {
+    if (P.variant.RM != 2) return;
     for (int64_t sl = 0; sl < P.n_slots; ++sl) {
-        const unsigned long long* c = v.data() + (size_t)sl * (K1 - K0);
-        w.hint_shift_repeats += c[27 - K0];
-        for (int k = 0; k < 2; ++k) { w.sweeps[k] += c[49 + k - K0]; w.swept_cols[k] += c[51 + k - K0]; w.swept_cells[k] += c[53 + k - K0]; }
-        if (tw) { tw->twin_steps += c[55 - K0] & 0xffffffffull; tw->join_rows += c[55 - K0] >> 32; }
+        const unsigned long long* c = prof.data() + (size_t)sl * SLOT_PROF_WORDS;
+        w.hint_shift_repeats += c[SP_HINT_REPEATS];
+        for (int k = 0; k < 2; ++k) { w.sweeps[k] += c[SP_SWEEPS + k]; w.swept_cols[k] += c[SP_SWEPT_COLS + k]; w.swept_cells[k] += c[SP_SWEPT_CELLS + k]; }
+        if (tw) { tw->twin_steps += c[SP_TWIN] & 0xffffffffull; tw->join_rows += c[SP_TWIN] >> 32; }
     }
-    return SXG_OK;
 }
 
-static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt) {
+// SXG_POA_DEBUG: what a launch did, from its slots' profiles (stderr; SXG_POA_SLOT_CSV: one line per slot appended to that file)
+static void debug_plan(const LaunchPlan& P, const std::vector<unsigned long long>& prof, int attempt) {
     const Variant V = P.variant;
-    unsigned long long acc[8] = {0}, smin = ~0ull, smax = 0;
+    auto word_sum = [&](int k) {   // word k of the profile, summed over the slots
+        unsigned long long sum = 0;
+        for (int64_t sl = 0; sl < P.n_slots; ++sl) sum += prof[(size_t)sl * SLOT_PROF_WORDS + k];
+        return sum;
+    };
+    unsigned long long acc[SP_PHASES], smin = ~0ull, smax = 0;
+    for (int k = 0; k < SP_PHASES; ++k) acc[k] = word_sum(k);
     for (int64_t sl = 0; sl < P.n_slots; ++sl) {
-        unsigned long long one[8];
-        HIPCHK(hipMemcpy(one, R.arena.as<uint8_t>() + (size_t)sl * P.lay.total + P.lay.hdr + 64, 64, hipMemcpyDeviceToHost));
-        for (int k = 0; k < 8; ++k) acc[k] += one[k];
         unsigned long long st = 0;
-        for (int k = 0; k < 6; ++k) st += one[k];
+        for (int k = 0; k < SP_PHASES; ++k) st += prof[(size_t)sl * SLOT_PROF_WORDS + k];
         smin = std::min(smin, st); smax = std::max(smax, st);
     }
     if (V.RM == 2) {   // packed sweep: the width of the plane rows the sweeps kept (adaptive band) and the hint-shift repeats
-        unsigned long long rep = 0, wsum = 0, nsw = 0;
-        for (int64_t sl = 0; sl < P.n_slots; ++sl) {
-            unsigned long long v[49];
-            HIPCHK(hipMemcpy(v, R.arena.as<uint8_t>() + (size_t)sl * P.lay.total + P.lay.hdr + 64, sizeof(v), hipMemcpyDeviceToHost));
-            rep += v[27]; wsum += v[47]; nsw += v[48];
-        }
+        const unsigned long long rep = word_sum(SP_HINT_REPEATS), wsum = word_sum(SP_BAND_STRIPS), nsw = word_sum(SP_BAND_SWEEPS);
         fprintf(stderr, "[sxg]   band: %llu sweeps, mean width %.1f strips of %d (%.0f columns), %llu hint-shift repeats\n", nsw,
                 (double)wsum / (double)std::max(nsw, 1ull), P.lay.band_strips, (double)wsum / (double)std::max(nsw, 1ull) * V.W, rep);
         // (with a second width the band line's strips are a mix of both widths' and its columns an upper bound)
         sxg_poa_width_stats w{};
         sxg_poa_twin_stats tw{};
-        if (int rcw = width_stats_of(P, R, w, &tw)) return rcw;
+        width_stats_of(P, prof, w, &tw);
         fprintf(stderr, "[sxg]   width: W=%d %llu sweeps %llu columns %.4g cells; W2=%d %llu sweeps %llu columns %.4g cells\n", V.W, (unsigned long long)w.sweeps[0],
                 (unsigned long long)w.swept_cols[0], (double)w.swept_cells[0], P.lay.W2, (unsigned long long)w.sweeps[1], (unsigned long long)w.swept_cols[1], (double)w.swept_cells[1]);
         fprintf(stderr, "[sxg]   twin: %llu twin steps, %llu join rows\n", (unsigned long long)tw.twin_steps, (unsigned long long)tw.join_rows);
@@ -861,10 +863,9 @@ static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt)
     if (const char* path = getenv("SXG_POA_SLOT_CSV")) {  // per-slot placement and wall-clock span
         if (FILE* f = fopen(path, "a")) {
             for (int64_t sl = 0; sl < P.n_slots; ++sl) {
-                unsigned long long v[26];
-                HIPCHK(hipMemcpy(v, R.arena.as<uint8_t>() + (size_t)sl * P.lay.total + P.lay.hdr + 64, sizeof(v), hipMemcpyDeviceToHost));
-                fprintf(f, "%lld,%llu,%llu", (long long)sl, v[8], v[9]);
-                for (int w = 0; w < V.NW && w < 16; ++w) fprintf(f, ",%llx", v[10 + w]);
+                const unsigned long long* v = prof.data() + (size_t)sl * SLOT_PROF_WORDS;
+                fprintf(f, "%lld,%llu,%llu", (long long)sl, v[SP_WALL0], v[SP_WALL1]);
+                for (int w = 0; w < V.NW && w < SP_WAVES; ++w) fprintf(f, ",%llx", v[SP_WAVE + w]);
                 fprintf(f, "\n");
             }
             fclose(f);
@@ -872,41 +873,34 @@ static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt)
     }
 #ifdef SXG_ROW_PROF
     {
-        unsigned long long ra[13] = {0};
-        for (int64_t sl = 0; sl < P.n_slots; ++sl) {
-            unsigned long long one[13];
-            HIPCHK(hipMemcpy(one, R.arena.as<uint8_t>() + (size_t)sl * P.lay.total + P.lay.hdr + 64 + 28 * 8, sizeof(one), hipMemcpyDeviceToHost));
-            for (int k = 0; k < 13; ++k) ra[k] += one[k];
-        }
+        unsigned long long ra[ROWP_WORDS];
+        for (int k = 0; k < ROWP_WORDS; ++k) ra[k] = word_sum(SP_ROW + k);
         double rt = 1e-9;
-        for (int k = 0; k < 8; ++k) rt += (double)ra[k];
-        static const char* seg16[8] = {"setup", "pass1+scan", "wait left wave", "combine+pass2", "wait right wave", "hand-over+end cell", "stored row fetch", "outgoing+row store"};
-        static const char* segb[8] = {"descriptor+band", "predecessor fetch+fold", "pass1+scan+pass2", "end cell+best-cell search", "outgoing+band stores", "-", "-", "-"};
+        for (int k = 0; k < ROWP_SEGS; ++k) rt += (double)ra[k];
+        static const char* seg16[ROWP_SEGS] = {"setup", "pass1+scan", "wait left wave", "combine+pass2", "wait right wave", "hand-over+end cell", "stored row fetch", "outgoing+row store"};
+        static const char* segb[ROWP_SEGS] = {"descriptor+band", "predecessor fetch+fold", "pass1+scan+pass2", "end cell+best-cell search", "outgoing+band stores", "-", "-", "-"};
         const char* const* seg = V.RM == 3 ? segb : seg16;
         fprintf(stderr, "[sxg]   row profile:");
-        for (int k = 0; k < 8; ++k) fprintf(stderr, " %s %.1f%%", seg[k], 100.0 * (double)ra[k] / rt);
+        for (int k = 0; k < ROWP_SEGS; ++k) fprintf(stderr, " %s %.1f%%", seg[k], 100.0 * (double)ra[k] / rt);
         fprintf(stderr, "\n");
         fprintf(stderr, "[sxg]   traceback: %.3g steps, %.1f steps per window, %.0f %% of the windows prefetched, %.0f cycles per step of which %.0f in window fills\n",
-                (double)ra[8], (double)ra[8] / std::max<double>((double)ra[9], 1), 100.0 * (double)ra[12] / std::max<double>((double)ra[9], 1),
-                (double)ra[10] / std::max<double>((double)ra[8], 1), (double)ra[11] / std::max<double>((double)ra[8], 1));
+                (double)ra[ROWP_TB_STEPS], (double)ra[ROWP_TB_STEPS] / std::max<double>((double)ra[ROWP_TB_LOADS], 1),
+                100.0 * (double)ra[ROWP_TB_HITS] / std::max<double>((double)ra[ROWP_TB_LOADS], 1),
+                (double)ra[ROWP_TB_CYCLES] / std::max<double>((double)ra[ROWP_TB_STEPS], 1), (double)ra[ROWP_TB_FILL_CYCLES] / std::max<double>((double)ra[ROWP_TB_STEPS], 1));
     }
 #endif
 #ifdef SXG_RESORT_PROF
     {   // phases of the S7' re-sort (poa_graph_dev.h::spoa_resort_par), thread 0's clock
-        unsigned long long ra[6] = {0};
-        for (int64_t sl = 0; sl < P.n_slots; ++sl) {
-            unsigned long long one[6];
-            HIPCHK(hipMemcpy(one, R.arena.as<uint8_t>() + (size_t)sl * P.lay.total + P.lay.hdr + 64 + 41 * 8, sizeof(one), hipMemcpyDeviceToHost));
-            for (int k = 0; k < 6; ++k) ra[k] += one[k];
-        }
+        unsigned long long ra[RSP_WORDS];
+        for (int k = 0; k < RSP_WORDS; ++k) ra[k] = word_sum(SP_RESORT + k);
         double rt = 1e-9;
-        for (int k = 0; k < 5; ++k) rt += (double)ra[k];
+        for (int k = 0; k < RSP_PHASES; ++k) rt += (double)ra[k];
         fprintf(stderr, "[sxg]   re-sort: records %.1f%% first() %.1f%% counts %.1f%% walks %.1f%% ranks %.1f%%; %.3g cycles per slot, %.1f rounds per slot\n",
-                100 * ra[0] / rt, 100 * ra[1] / rt, 100 * ra[2] / rt, 100 * ra[3] / rt, 100 * ra[4] / rt, rt / (double)P.n_slots, (double)ra[5] / (double)P.n_slots);
+                100 * ra[0] / rt, 100 * ra[1] / rt, 100 * ra[2] / rt, 100 * ra[3] / rt, 100 * ra[4] / rt, rt / (double)P.n_slots, (double)ra[RSP_ROUNDS] / (double)P.n_slots);
     }
 #endif
     double tot = 1e-9;
-    for (int k = 0; k < 6; ++k) tot += (double)acc[k];
+    for (int k = 0; k < SP_PHASES; ++k) tot += (double)acc[k];
     size_t fr = 0, tt = 0;
     (void)hipMemGetInfo(&fr, &tt);
     fprintf(stderr, "[sxg] variant T=%d W=%d cvx=%d rowmode=%d attempt=%d work=%zu slots=%lld per_cu=%d smem=%d slot_bytes=%zu free=%zu ms=%.2f tmax=%d cb=%d ds=%d w2=%d\n",
@@ -915,8 +909,8 @@ static int debug_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, int attempt)
     fprintf(stderr, "[sxg]   slot busy (of the longest slot): min %.1f%% mean %.1f%%\n", 100.0 * (double)smin / (double)std::max(smax, 1ull),
             100.0 * tot / (double)P.n_slots / (double)std::max(smax, 1ull));
     fprintf(stderr, "[sxg]   slot time: other %.1f%% prep_rows %.1f%% dp_fill %.1f%% traceback %.1f%% add_alignment %.1f%% output %.1f%%\n",
-            100 * acc[0] / tot, 100 * acc[1] / tot, 100 * acc[2] / tot, 100 * acc[3] / tot, 100 * acc[4] / tot, 100 * acc[5] / tot);
-    return SXG_OK;
+            100 * acc[SP_OTHER] / tot, 100 * acc[SP_PREP_ROWS] / tot, 100 * acc[SP_DP_FILL] / tot, 100 * acc[SP_TRACEBACK] / tot, 100 * acc[SP_ADD_ALIGNMENT] / tot,
+            100 * acc[SP_OUTPUT] / tot);
 }
 
 // A9 + A10 of every block on the device (block_graph_kernel), after the batch's alignments: outputs in per-block
@@ -1096,6 +1090,288 @@ extern "C" int sxg_poa_get_msa_stats(sxg_poa_handle* h, double* cols_ms, double*
     return SXG_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// The steps of sxg_poa_batch_execute, in the order a round runs them.
+
+// group by (variant, convex, local, capacity tier): one launch per group, all groups concurrently
+static void group_pending(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, const std::vector<int32_t>& pending) {
+    for (int b : pending) {
+        const BlockMeta& m = h->meta[b];
+        LaunchPlan* pl = nullptr;
+        for (auto& q : plans)
+            if (q.variant == m.variant && q.cvx == m.cvx && q.sw == m.sw && q.tier == m.tier && q.wide_band == m.wide_band) { pl = &q; break; }
+        if (!pl) { plans.emplace_back(); pl = &plans.back(); pl->variant = m.variant; pl->cvx = m.cvx; pl->sw = m.sw; pl->tier = m.tier; pl->wide_band = m.wide_band; }
+        pl->work.push_back(b);
+    }
+    std::sort(plans.begin(), plans.end(), [](const LaunchPlan& a, const LaunchPlan& b) { return a.variant.Lpad() > b.variant.Lpad(); });
+}
+
+static void merge_plans(sxg_poa_handle* h, std::vector<LaunchPlan>& plans) {
+    // a geometry with at least 75 % of the columns of a wider one of the same kind joins it: fewer,
+    // fuller launches beat many partial ones, but every joined block sweeps the wider geometry's columns
+    // (measured on the mixed batch, round 2 with over-subscribed launches: 0.60 39.6 s, 0.75 33.8 s, 0.90 34.3 s)
+    // Round 4, with ONE priority board for all launches of a round: the headline's two geometries (5 120 and 5 632 columns)
+    // run 2.4 % faster apart than merged (2 137 -> 2 088 ms, same box) and the mixed batch 1.8 %; the small geometries of
+    // config 2 (three launches of 1-2 waves per block) still lose 15 % apart.  So: wide geometries merge only within 8 %,
+    // the others within 25 % as before.
+    const double merge_env = getenv("SXG_POA_MERGE") ? atof(getenv("SXG_POA_MERGE")) : 0.0;
+    // Round 14: neighbouring widths -- a geometry whose strip width IS the second width of a wider one's class at the same wave
+    // count (the headline's W = 10 beside its W = 11) -- run as ONE launch wherever there is something to deal: in a round
+    // whose packed launches together ask for at least one workgroup per CU.  Inside the wider class every alignment of the
+    // joined blocks runs at their own width, so the reason to keep wide geometries apart (above) does not apply; one launch
+    // is what the deal over CUs models ("workgroup k runs on CU k mod #CU": two launches side by side each pick their own
+    // light CUs, and the hardware puts the second one's workgroups wherever there is room), one block queue has no launch
+    // that drains before the other, and the priority board ranks all co-residents by one cost.  Below that size nothing
+    // shares a CU and the launches stay apart.  SXG_POA_MERGE_WIDTH2=0: never (the plan of round 13), =1: at any size.
+    // (measured: profiles/r15.)
+    bool merge_w2 = width2_enabled();
+    if (const char* e = getenv("SXG_POA_MERGE_WIDTH2")) merge_w2 = merge_w2 && atoi(e) != 0;
+    else {
+        size_t packed = 0;
+        for (const auto& q : plans) if (q.variant.RM == 2) packed += q.work.size();
+        merge_w2 = merge_w2 && packed >= (size_t)std::max(h->num_cu, 1);
+    }
+    for (size_t i = 0; i < plans.size(); ++i)
+        for (size_t j = i + 1; j < plans.size();) {
+            const LaunchPlan &a = plans[i], &b = plans[j];
+            // (neighbouring widths: see merge_w2 above)
+            const bool join_w2 = merge_w2 && a.variant.NW == b.variant.NW && b.variant.W == class_w2(CLASS_BLOCK, a.variant, a.sw);
+            if (same_kind(a.variant, b.variant) && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
+                (join_w2 || (double)b.variant.Lpad() >= (merge_env > 0 ? merge_env : (a.variant.Lpad() >= 4096 ? 0.92 : 0.75)) * (double)a.variant.Lpad())) {
+                plans[i].work.insert(plans[i].work.end(), b.work.begin(), b.work.end());
+                plans.erase(plans.begin() + (long)j);
+            } else ++j;
+        }
+}
+
+static void spread_small_plans(sxg_poa_handle* h, std::vector<LaunchPlan>& plans) {
+    // A batch that cannot fill the device with one workgroup per block (1000 blocks of 1 kbp are 1000 waves of 4096)
+    // gives every block twice the waves at half the strip width: the same columns, shorter rows.
+    if (!getenv("SXG_POA_NO_SPREAD")) {
+        uint64_t waves = 0;
+        for (auto& pl : plans) waves += (uint64_t)pl.work.size() * (uint64_t)pl.variant.NW;
+        for (auto& pl : plans) {
+            Variant& v = pl.variant;
+            while (v.RM == 2 && v.NW <= 2 && v.W % 2 == 0 && v.W / 2 >= 4 && 2 * waves <= (uint64_t)h->num_cu * 16u) {
+                waves += (uint64_t)pl.work.size() * (uint64_t)v.NW;
+                v = Variant{v.W / 2, 2 * v.NW, class_tmax(v.W / 2, 2 * v.NW, 2, v.CB, true), 2, v.CB, v.DS};   // (NW 1 -> 2: the two-wave class; 2 -> 4: the four-wave class)
+            }
+        }
+    }
+}
+
+static void price_plans(sxg_poa_handle* h, std::vector<LaunchPlan>& plans) {
+    // A block's cost depends on the launch it ended up in (poa_cost.h: rows x swept columns -- a W = 10 block merged into the
+    // W = 11 class runs every alignment at W2 = 10, one spread over twice the waves half the strip width), so it is priced
+    // here, from the launch's variant as prepare_plan settled it, and the launch's blocks are sorted by THAT cost.
+    h->blk_cost.assign((size_t)std::max(h->n_blocks, 1), 0);
+    h->seq_done.assign((size_t)std::max<int64_t>(h->n_seqs, 1), 0);
+    for (auto& pl : plans) {
+        prepare_plan(h, pl, pl.tier);
+        const Variant& v = pl.variant;
+        for (int b : pl.work)
+            h->blk_cost[(size_t)b] = block_cost(h->h_seq_off.data() + h->h_blk_off[b], h->h_blk_off[b + 1] - h->h_blk_off[b], v.RM, v.T(), v.W, v.W2,
+                                                h->seq_done.data() + h->h_blk_off[b]);
+        std::stable_sort(pl.work.begin(), pl.work.end(), [&](int a, int b) { return h->blk_cost[(size_t)a] > h->blk_cost[(size_t)b]; });
+    }
+}
+
+static void drop_over_budget(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, const uint64_t budget, std::vector<int32_t>& status,
+                             std::vector<int32_t>& nomem_blocks) {
+    // A geometry whose single arena does not fit the budget fails ITS blocks (per-block status, as the
+    // ABI promises) and the rest of the batch goes on.
+    for (size_t i = 0; i < plans.size();) {
+        if ((uint64_t)plans[i].lay.total > budget && plans[i].wide_band) {
+            // the every-strip plane (rows x columns dwords) is what does not fit: these blocks are not final -- their
+            // status stays ST_BAND_MISS and the round's bookkeeping below sends them down the widening ladder
+            // (packed -> 32-bit sweep, one byte per cell), which is where a band miss went before the wide plane existed
+            for (int b : plans[i].work) { h->meta[b].wide_band = false; h->meta[b].no_wide = true; }
+            plans.erase(plans.begin() + (long)i);
+        } else if ((uint64_t)plans[i].lay.total > budget) {
+            for (int b : plans[i].work) status[b] = plans[i].tier >= 2 ? ST_POOL_OVERFLOW : ST_ROWS_OVERFLOW;
+            g_err = "memory budget too small for a block arena of " + std::to_string(plans[i].lay.total) + " bytes";
+            nomem_blocks.insert(nomem_blocks.end(), plans[i].work.begin(), plans[i].work.end());
+            plans.erase(plans.begin() + (long)i);
+        } else ++i;
+    }
+}
+
+static void size_slots(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, const uint64_t budget) {
+    // Slots per launch.  One geometry: as many as there are blocks / as fit.  Several geometries
+    // running side by side should end together, so their WAVES are made proportional to their
+    // work (cost model of SURVEY 8e): slots_p = lambda * cost_p / waves_per_slot_p, with the largest
+    // lambda that respects the arena budget and the wave capacity of the device.
+    // (the blocks' costs in THEIR launch, as priced above: a block swept by a wider geometry than its own -- merged launches --
+    //  costs the columns of that geometry, and an alignment that a dual-width class sweeps at W2 costs W2's.  Until round 14
+    //  a dual-width launch was priced at its full width, cost * Lpad / maxlen, and the headline's W = 11 launch, 80 % of whose
+    //  sweeps run at W2 = 10, ended ~2 % before the W = 10 launch beside it.)
+    std::vector<double> pcost(plans.size(), 0.0);
+    for (size_t i = 0; i < plans.size(); ++i)
+        for (int b : plans[i].work) pcost[i] += (double)std::max<uint64_t>(h->blk_cost[(size_t)b], 1);
+    const int oversub = getenv("SXG_POA_OVERSUB") ? std::max(1, atoi(getenv("SXG_POA_OVERSUB"))) : 2;
+    auto slots_at = [&](size_t i, double lambda) {
+        const double s = lambda * pcost[i] / (double)plans[i].variant.NW;
+        return (int64_t)std::min<double>((double)plans[i].want_slots, std::max(1.0, std::floor(s)));
+    };
+    auto fits = [&](double lambda) {
+        uint64_t bytes = 0, waves = 0;
+        for (size_t i = 0; i < plans.size(); ++i) {
+            const int64_t n = slots_at(i, lambda);
+            bytes += (uint64_t)n * plans[i].lay.total;
+            waves += (uint64_t)n * (uint64_t)plans[i].variant.NW;
+        }
+        // Side by side the launches may ask for up to TWICE the wave slots of the device: workgroups that find no room wait
+        // in their hardware queue and start -- pulling from their launch's block queue -- as soon as another launch
+        // drains, so a launch the cost model under-estimated is not left alone on a half-empty chip at the end.
+        return bytes <= budget && (plans.size() == 1 || waves <= (uint64_t)h->num_cu * 16u * (uint64_t)oversub);
+    };
+    double lam_lo = 0.0, lam_hi = 1.0;
+    while (lam_hi < 1e30 && fits(lam_hi)) {
+        bool all_full = true;
+        for (size_t i = 0; i < plans.size(); ++i) all_full = all_full && slots_at(i, lam_hi) >= plans[i].want_slots;
+        if (all_full) break;
+        lam_hi *= 2.0;
+    }
+    if (!fits(lam_hi))
+        for (int it = 0; it < 100; ++it) {
+            const double mid = 0.5 * (lam_lo + lam_hi);
+            if (fits(mid)) lam_lo = mid; else lam_hi = mid;
+        }
+    const double lambda = fits(lam_hi) ? lam_hi : lam_lo;
+    for (size_t i = 0; i < plans.size(); ++i) plans[i].n_slots = slots_at(i, lambda);
+}
+
+// launches the round, waits for it, and collects its times and statistics
+static int launch_round(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, const int attempt, const bool dbg, float& ms_total) {
+    while (h->planres.size() < plans.size()) {
+        PlanRes* r = new PlanRes();
+        HIPCHK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+        HIPCHK(hipEventCreate(&r->e0));
+        HIPCHK(hipEventCreate(&r->e1));
+        h->planres.push_back(r);
+    }
+    {
+        const size_t board_bytes = (size_t)PRIO_BOARD_CUS * PRIO_BOARD_SLOTS * 4;
+        int rcb = h->d_board.ensure(board_bytes);
+        if (rcb) return rcb;
+        HIPCHK(hipMemsetAsync(h->d_board.p, 0, board_bytes, h->stream));
+        if ((rcb = h->d_est_done.ensure(8 * h->seq_done.size()))) return rcb;
+        HIPCHK(hipMemcpyAsync(h->d_est_done.p, h->seq_done.data(), 8 * h->seq_done.size(), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    int prio_base = 0;
+    for (size_t i = 0; i < plans.size(); ++i) {
+        int rc = launch_plan(h, plans[i], *h->planres[i], prio_base);
+        if (rc) return rc;
+        prio_base += (int)((plans[i].n_slots + h->num_cu - 1) / std::max(h->num_cu, 1));
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    // While the kernels run: pin the host buffer the step lists will be downloaded into (first call of a handle, or a
+    // bigger batch than before; afterwards the pool already has it).  n_bases bounds the number of steps.
+    if (attempt == 0 && h->want_block_graph && h->pins && h->n_bases >= ((int64_t)16 << 20) && !getenv("SXG_POA_NO_PINNED")) {
+        if (h->pin_thread.joinable()) h->pin_thread.join();
+        try {
+            h->pin_thread = std::thread([pool = h->pins, dev = h->device, bytes = 4 * (size_t)h->n_bases] {
+                if (hipSetDevice(dev) == hipSuccess) pool->prewarm(bytes);
+            });
+        } catch (...) {}   // (no thread: the download pins, or falls back to pageable memory, itself)
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    ms_total += ms;
+    std::vector<unsigned long long> prof;   // the slot profiles of one launch
+    for (size_t i = 0; i < plans.size(); ++i) {
+        HIPCHK(hipEventElapsedTime(&plans[i].ms, h->planres[i]->e0, h->planres[i]->e1));
+        if (int rcp = fetch_slot_prof(plans[i], *h->planres[i], prof)) return rcp;
+        plans[i].clock_mhz = sample_clock(plans[i], prof);
+        h->stats.dp_launches += 1;
+        h->stats.n_slots += (int)plans[i].n_slots;
+        h->stats.device_bytes += (uint64_t)plans[i].n_slots * plans[i].lay.total;
+        width_stats_of(plans[i], prof, h->wstats, &h->tstats);
+        if (dbg) debug_plan(plans[i], prof, attempt);
+    }
+    return SXG_OK;
+}
+
+// the statuses of the blocks that ran, and from them the blocks of the next round: `pending`
+static int advance_ladders(sxg_poa_handle* h, const std::vector<LaunchPlan>& plans, const int attempt, const bool dbg, std::vector<int32_t>& status,
+                           std::vector<int32_t>& pending, const std::vector<int32_t>& nomem_blocks) {
+    const int nb = h->n_blocks;
+    {
+        std::vector<int32_t> dev(std::max(nb, 1));
+        HIPCHK(hipMemcpy(dev.data(), h->d_status.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        for (auto& pl : plans) for (int b : pl.work) status[b] = dev[b];   // only blocks that ran this round
+    }
+    std::vector<int32_t> again;
+    if (dbg) {
+        int cnt[16] = {0};
+        for (int b : pending) cnt[status[b] & 15]++;
+        fprintf(stderr, "[sxg] round %d: ok %d rows %d pool %d steps %d nodes %d long %d range %d band %d\n", attempt, cnt[0], cnt[1], cnt[2], cnt[3],
+                cnt[4], cnt[5], cnt[6], cnt[7]);
+    }
+    for (int b : pending) {
+        BlockMeta& m = h->meta[b];
+        if (std::find(nomem_blocks.begin(), nomem_blocks.end(), b) != nomem_blocks.end()) continue;
+        if (status[b] == ST_ROWS_OVERFLOW || status[b] == ST_POOL_OVERFLOW || status[b] == ST_TBX_OVERFLOW || status[b] == ST_NODES_OVERFLOW) {
+            if (m.tier < 3) { m.tier += 1; again.push_back(b); }
+        } else if (status[b] == ST_BAND_MISS && m.rm == 2 && !m.wide_band && !m.no_wide) {
+            // The traceback kept leaving the ~1100 columns the plane holds around the backbone hints (a structural variant
+            // that carries the alignment further off).  The same packed sweep is repeated with a plane that keeps EVERY
+            // strip of every row -- rows x columns dwords, up to ~6 GB for a 26 kbp block, but it cannot miss, it covers
+            // every length the packed sweep covers (the 32-bit sweeps end at SXG_POA_MAX_SEQ_LEN_WIDE) and it runs at the
+            // packed sweep's speed.
+            m.wide_band = true;
+            again.push_back(b);
+        } else if (status[b] == ST_RANGE_OVERFLOW || status[b] == ST_BAND_MISS) {
+            // one step wider at the same capacity tier: packed -> int16 row words -> int32 row words
+            if (m.rm != 1) {
+                classify_block(m, m.rm >= 2 ? 0 : 1, false);
+                if (m.fits) again.push_back(b);
+                else status[b] = ST_TOO_LONG;    // (a score range beyond int16 on a sequence beyond SXG_POA_MAX_SEQ_LEN_WIDE)
+            } else status[b] = ST_TOO_LONG;      // (unreachable: the int32 sweep reports neither)
+        }
+    }
+    h->stats.retries += (int)again.size();
+    pending.swap(again);
+    return SXG_OK;
+}
+
+// cells and bytes of the blocks that succeeded, and the dominant launch, into h->stats
+static int account_cells(sxg_poa_handle* h, std::vector<LaunchPlan>& all_plans, const std::vector<int32_t>& status) {
+    const int nb = h->n_blocks;
+    std::vector<unsigned long long> cells((size_t)std::max<int64_t>(h->n_seqs, 1));
+    if (h->n_seqs) HIPCHK(hipMemcpy(cells.data(), h->d_cells.p, 8 * (size_t)h->n_seqs, hipMemcpyDeviceToHost));
+    uint64_t total = 0, bytes = 0;
+    std::vector<uint64_t> blk_cells(std::max(nb, 1), 0), blk_bytes(std::max(nb, 1), 0);
+    for (int b = 0; b < nb; ++b) {
+        if (status[b] != ST_OK) continue;
+        uint64_t cb = 0;
+        for (int s = h->h_blk_off[b]; s < h->h_blk_off[b + 1]; ++s) cb += cells[s];
+        const BlockMeta& m = h->meta[b];
+        const int ncross = m.S.convex ? 3 : (m.S.g == m.S.e ? 1 : 2);
+        const int sz = m.rm == 1 ? 4 : 2;   // (banded: cells = band cells, as counted by the kernel)
+        blk_cells[b] = cb; blk_bytes[b] = cb * (uint64_t)(2 * ncross * sz + 1);
+        total += cb;
+        bytes += blk_bytes[b];
+    }
+    // dominant launch = the one that evaluated the most cells
+    for (auto& pl : all_plans) {
+        for (int b : pl.work) if (status[b] == ST_OK) { pl.cells += blk_cells[b]; pl.bytes += blk_bytes[b]; }
+        if (pl.cells >= h->stats.dom_cells) {
+            h->stats.dom_cells = pl.cells; h->stats.dom_algo_bytes = pl.bytes; h->stats.dom_kernel_ms = pl.ms;
+            h->stats.dom_threads = pl.variant.T(); h->stats.dom_cols_per_lane = pl.variant.W * (pl.variant.RM >= 2 ? 2 : 1);
+            h->stats.dom_row_mode = pl.variant.RM;
+            h->stats.dom_clock_mhz = pl.clock_mhz;
+            // (dom_cols_per_lane stays the class's W: an upper bound of the columns a dual-width launch's alignments swept)
+            h->wstats.dom_width = pl.variant.W; h->wstats.dom_width2 = pl.lay.W2;
+        }
+    }
+    h->stats.cells = total;
+    h->stats.algo_bytes = bytes;
+    return SXG_OK;
+}
+
 extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
     if (!h) return fail(SXG_E_INVALID, "handle is NULL");
     if (!h->have_batch) return fail(SXG_E_INVALID, "no batch uploaded");
@@ -1137,261 +1413,26 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
     // capacity tier; a band miss first repeats the packed sweep with a plane that keeps every strip).  3 + 3 steps at most, so 7
     // rounds always suffice; neither internal status is ever final.
     for (int attempt = 0; attempt < 7 && !pending.empty(); ++attempt) {
-        // group by (variant, convex, local, capacity tier): one launch per group, all groups concurrently
         std::vector<LaunchPlan> plans;
-        for (int b : pending) {
-            const BlockMeta& m = h->meta[b];
-            LaunchPlan* pl = nullptr;
-            for (auto& q : plans)
-                if (q.variant == m.variant && q.cvx == m.cvx && q.sw == m.sw && q.tier == m.tier && q.wide_band == m.wide_band) { pl = &q; break; }
-            if (!pl) { plans.emplace_back(); pl = &plans.back(); pl->variant = m.variant; pl->cvx = m.cvx; pl->sw = m.sw; pl->tier = m.tier; pl->wide_band = m.wide_band; }
-            pl->work.push_back(b);
-        }
-        std::sort(plans.begin(), plans.end(), [](const LaunchPlan& a, const LaunchPlan& b) { return a.variant.Lpad() > b.variant.Lpad(); });
-        // a geometry with at least 75 % of the columns of a wider one of the same kind joins it: fewer,
-        // fuller launches beat many partial ones, but every joined block sweeps the wider geometry's columns
-        // (measured on the mixed batch, round 2 with over-subscribed launches: 0.60 39.6 s, 0.75 33.8 s, 0.90 34.3 s)
-        // Round 4, with ONE priority board for all launches of a round: the headline's two geometries (5 120 and 5 632 columns)
-        // run 2.4 % faster apart than merged (2 137 -> 2 088 ms, same box) and the mixed batch 1.8 %; the small geometries of
-        // config 2 (three launches of 1-2 waves per block) still lose 15 % apart.  So: wide geometries merge only within 8 %,
-        // the others within 25 % as before.
-        const double merge_env = getenv("SXG_POA_MERGE") ? atof(getenv("SXG_POA_MERGE")) : 0.0;
-        // Round 14: neighbouring widths -- a geometry whose strip width IS the second width of a wider one's class at the same wave
-        // count (the headline's W = 10 beside its W = 11) -- run as ONE launch wherever there is something to deal: in a round
-        // whose packed launches together ask for at least one workgroup per CU.  Inside the wider class every alignment of the
-        // joined blocks runs at their own width, so the reason to keep wide geometries apart (above) does not apply; one launch
-        // is what the deal over CUs models ("workgroup k runs on CU k mod #CU": two launches side by side each pick their own
-        // light CUs, and the hardware puts the second one's workgroups wherever there is room), one block queue has no launch
-        // that drains before the other, and the priority board ranks all co-residents by one cost.  Below that size nothing
-        // shares a CU and the launches stay apart.  SXG_POA_MERGE_WIDTH2=0: never (the plan of round 13), =1: at any size.
-        // (measured: profiles/r15.)
-        bool merge_w2 = width2_enabled();
-        if (const char* e = getenv("SXG_POA_MERGE_WIDTH2")) merge_w2 = merge_w2 && atoi(e) != 0;
-        else {
-            size_t packed = 0;
-            for (const auto& q : plans) if (q.variant.RM == 2) packed += q.work.size();
-            merge_w2 = merge_w2 && packed >= (size_t)std::max(h->num_cu, 1);
-        }
-        for (size_t i = 0; i < plans.size(); ++i)
-            for (size_t j = i + 1; j < plans.size();) {
-                const LaunchPlan &a = plans[i], &b = plans[j];
-                // (neighbouring widths: see merge_w2 above)
-                const bool join_w2 = merge_w2 && a.variant.NW == b.variant.NW && b.variant.W == class_w2(CLASS_BLOCK, a.variant, a.sw);
-                if (same_kind(a.variant, b.variant) && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
-                    (join_w2 || (double)b.variant.Lpad() >= (merge_env > 0 ? merge_env : (a.variant.Lpad() >= 4096 ? 0.92 : 0.75)) * (double)a.variant.Lpad())) {
-                    plans[i].work.insert(plans[i].work.end(), b.work.begin(), b.work.end());
-                    plans.erase(plans.begin() + (long)j);
-                } else ++j;
-            }
-        // A batch that cannot fill the device with one workgroup per block (1000 blocks of 1 kbp are 1000 waves of 4096)
-        // gives every block twice the waves at half the strip width: the same columns, shorter rows.
-        if (!getenv("SXG_POA_NO_SPREAD")) {
-            uint64_t waves = 0;
-            for (auto& pl : plans) waves += (uint64_t)pl.work.size() * (uint64_t)pl.variant.NW;
-            for (auto& pl : plans) {
-                Variant& v = pl.variant;
-                while (v.RM == 2 && v.NW <= 2 && v.W % 2 == 0 && v.W / 2 >= 4 && 2 * waves <= (uint64_t)h->num_cu * 16u) {
-                    waves += (uint64_t)pl.work.size() * (uint64_t)v.NW;
-                    v = Variant{v.W / 2, 2 * v.NW, class_tmax(v.W / 2, 2 * v.NW, 2, v.CB, true), 2, v.CB, v.DS};   // (NW 1 -> 2: the two-wave class; 2 -> 4: the four-wave class)
-                }
-            }
-        }
+        group_pending(h, plans, pending);
+        merge_plans(h, plans);
+        spread_small_plans(h, plans);
         const uint64_t budget = arena_budget(h);
-        uint64_t want_bytes = 0;
-        // A block's cost depends on the launch it ended up in (poa_cost.h: rows x swept columns -- a W = 10 block merged into the
-        // W = 11 class runs every alignment at W2 = 10, one spread over twice the waves half the strip width), so it is priced
-        // here, from the launch's variant as prepare_plan settled it, and the launch's blocks are sorted by THAT cost.
-        h->blk_cost.assign((size_t)std::max(nb, 1), 0);
-        h->seq_done.assign((size_t)std::max<int64_t>(h->n_seqs, 1), 0);
-        for (auto& pl : plans) {
-            prepare_plan(h, pl, pl.tier);
-            const Variant& v = pl.variant;
-            for (int b : pl.work)
-                h->blk_cost[(size_t)b] = block_cost(h->h_seq_off.data() + h->h_blk_off[b], h->h_blk_off[b + 1] - h->h_blk_off[b], v.RM, v.T(), v.W, v.W2,
-                                                    h->seq_done.data() + h->h_blk_off[b]);
-            std::stable_sort(pl.work.begin(), pl.work.end(), [&](int a, int b) { return h->blk_cost[(size_t)a] > h->blk_cost[(size_t)b]; });
-            want_bytes += (uint64_t)pl.want_slots * pl.lay.total;
-        }
-        // A geometry whose single arena does not fit the budget fails ITS blocks (per-block status, as the
-        // ABI promises) and the rest of the batch goes on.
-        for (size_t i = 0; i < plans.size();) {
-            if ((uint64_t)plans[i].lay.total > budget && plans[i].wide_band) {
-                // the every-strip plane (rows x columns dwords) is what does not fit: these blocks are not final -- their
-                // status stays ST_BAND_MISS and the round's bookkeeping below sends them down the widening ladder
-                // (packed -> 32-bit sweep, one byte per cell), which is where a band miss went before the wide plane existed
-                for (int b : plans[i].work) { h->meta[b].wide_band = false; h->meta[b].no_wide = true; }
-                plans.erase(plans.begin() + (long)i);
-            } else if ((uint64_t)plans[i].lay.total > budget) {
-                for (int b : plans[i].work) status[b] = plans[i].tier >= 2 ? ST_POOL_OVERFLOW : ST_ROWS_OVERFLOW;
-                g_err = "memory budget too small for a block arena of " + std::to_string(plans[i].lay.total) + " bytes";
-                nomem_blocks.insert(nomem_blocks.end(), plans[i].work.begin(), plans[i].work.end());
-                plans.erase(plans.begin() + (long)i);
-            } else ++i;
-        }
-        // Slots per launch.  One geometry: as many as there are blocks / as fit.  Several geometries
-        // running side by side should end together, so their WAVES are made proportional to their
-        // work (cost model of SURVEY 8e): slots_p = lambda * cost_p / waves_per_slot_p, with the largest
-        // lambda that respects the arena budget and the wave capacity of the device.
-        // (the blocks' costs in THEIR launch, as priced above: a block swept by a wider geometry than its own -- merged launches --
-        //  costs the columns of that geometry, and an alignment that a dual-width class sweeps at W2 costs W2's.  Until round 14
-        //  a dual-width launch was priced at its full width, cost * Lpad / maxlen, and the headline's W = 11 launch, 80 % of whose
-        //  sweeps run at W2 = 10, ended ~2 % before the W = 10 launch beside it.)
-        std::vector<double> pcost(plans.size(), 0.0);
-        for (size_t i = 0; i < plans.size(); ++i)
-            for (int b : plans[i].work) pcost[i] += (double)std::max<uint64_t>(h->blk_cost[(size_t)b], 1);
-        const int oversub = getenv("SXG_POA_OVERSUB") ? std::max(1, atoi(getenv("SXG_POA_OVERSUB"))) : 2;
-        auto slots_at = [&](size_t i, double lambda) {
-            const double s = lambda * pcost[i] / (double)plans[i].variant.NW;
-            return (int64_t)std::min<double>((double)plans[i].want_slots, std::max(1.0, std::floor(s)));
-        };
-        auto fits = [&](double lambda) {
-            uint64_t bytes = 0, waves = 0;
-            for (size_t i = 0; i < plans.size(); ++i) {
-                const int64_t n = slots_at(i, lambda);
-                bytes += (uint64_t)n * plans[i].lay.total;
-                waves += (uint64_t)n * (uint64_t)plans[i].variant.NW;
-            }
-            // Side by side the launches may ask for up to TWICE the wave slots of the device: workgroups that find no room wait
-            // in their hardware queue and start -- pulling from their launch's block queue -- as soon as another launch
-            // drains, so a launch the cost model under-estimated is not left alone on a half-empty chip at the end.
-            return bytes <= budget && (plans.size() == 1 || waves <= (uint64_t)h->num_cu * 16u * (uint64_t)oversub);
-        };
-        double lam_lo = 0.0, lam_hi = 1.0;
-        while (lam_hi < 1e30 && fits(lam_hi)) {
-            bool all_full = true;
-            for (size_t i = 0; i < plans.size(); ++i) all_full = all_full && slots_at(i, lam_hi) >= plans[i].want_slots;
-            if (all_full) break;
-            lam_hi *= 2.0;
-        }
-        if (!fits(lam_hi))
-            for (int it = 0; it < 100; ++it) {
-                const double mid = 0.5 * (lam_lo + lam_hi);
-                if (fits(mid)) lam_lo = mid; else lam_hi = mid;
-            }
-        const double lambda = fits(lam_hi) ? lam_hi : lam_lo;
-        (void)want_bytes;
-        while (h->planres.size() < plans.size()) {
-            PlanRes* r = new PlanRes();
-            HIPCHK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-            HIPCHK(hipEventCreate(&r->e0));
-            HIPCHK(hipEventCreate(&r->e1));
-            h->planres.push_back(r);
-        }
-        for (size_t i = 0; i < plans.size(); ++i) plans[i].n_slots = slots_at(i, lambda);
+        price_plans(h, plans);
+        drop_over_budget(h, plans, budget, status, nomem_blocks);
+        size_slots(h, plans, budget);
         lap("plan");
-        {
-            const size_t board_bytes = (size_t)PRIO_BOARD_CUS * PRIO_BOARD_SLOTS * 4;
-            int rcb = h->d_board.ensure(board_bytes);
-            if (rcb) return rcb;
-            HIPCHK(hipMemsetAsync(h->d_board.p, 0, board_bytes, h->stream));
-            if ((rcb = h->d_est_done.ensure(8 * h->seq_done.size()))) return rcb;
-            HIPCHK(hipMemcpyAsync(h->d_est_done.p, h->seq_done.data(), 8 * h->seq_done.size(), hipMemcpyHostToDevice, h->stream));
-        }
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
-        int prio_base = 0;
-        for (size_t i = 0; i < plans.size(); ++i) {
-            int rc = launch_plan(h, plans[i], *h->planres[i], prio_base);
-            if (rc) return rc;
-            prio_base += (int)((plans[i].n_slots + h->num_cu - 1) / std::max(h->num_cu, 1));
-        }
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        // While the kernels run: pin the host buffer the step lists will be downloaded into (first call of a handle, or a
-        // bigger batch than before; afterwards the pool already has it).  n_bases bounds the number of steps.
-        if (attempt == 0 && h->want_block_graph && h->pins && h->n_bases >= ((int64_t)16 << 20) && !getenv("SXG_POA_NO_PINNED")) {
-            if (h->pin_thread.joinable()) h->pin_thread.join();
-            try {
-                h->pin_thread = std::thread([pool = h->pins, dev = h->device, bytes = 4 * (size_t)h->n_bases] {
-                    if (hipSetDevice(dev) == hipSuccess) pool->prewarm(bytes);
-                });
-            } catch (...) {}   // (no thread: the download pins, or falls back to pageable memory, itself)
-        }
-        HIPCHK(hipStreamSynchronize(h->stream));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        ms_total += ms;
-        for (size_t i = 0; i < plans.size(); ++i) {
-            HIPCHK(hipEventElapsedTime(&plans[i].ms, h->planres[i]->e0, h->planres[i]->e1));
-            plans[i].clock_mhz = sample_clock(plans[i], *h->planres[i]);
-            h->stats.dp_launches += 1;
-            h->stats.n_slots += (int)plans[i].n_slots;
-            h->stats.device_bytes += (uint64_t)plans[i].n_slots * plans[i].lay.total;
-            if (int rcw = width_stats_of(plans[i], *h->planres[i], h->wstats, &h->tstats)) return rcw;
-            if (dbg) debug_plan(h, plans[i], *h->planres[i], attempt);
-        }
+        if (int rc = launch_round(h, plans, attempt, dbg, ms_total)) return rc;
         lap("launches");
-        {
-            std::vector<int32_t> dev(std::max(nb, 1));
-            HIPCHK(hipMemcpy(dev.data(), h->d_status.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-            for (auto& pl : plans) for (int b : pl.work) status[b] = dev[b];   // only blocks that ran this round
-        }
-        std::vector<int32_t> again;
-        if (dbg) {
-            int cnt[16] = {0};
-            for (int b : pending) cnt[status[b] & 15]++;
-            fprintf(stderr, "[sxg] round %d: ok %d rows %d pool %d steps %d nodes %d long %d range %d band %d\n", attempt, cnt[0], cnt[1], cnt[2], cnt[3],
-                    cnt[4], cnt[5], cnt[6], cnt[7]);
-        }
-        for (int b : pending) {
-            BlockMeta& m = h->meta[b];
-            if (std::find(nomem_blocks.begin(), nomem_blocks.end(), b) != nomem_blocks.end()) continue;
-            if (status[b] == ST_ROWS_OVERFLOW || status[b] == ST_POOL_OVERFLOW || status[b] == ST_TBX_OVERFLOW || status[b] == ST_NODES_OVERFLOW) {
-                if (m.tier < 3) { m.tier += 1; again.push_back(b); }
-            } else if (status[b] == ST_BAND_MISS && m.rm == 2 && !m.wide_band && !m.no_wide) {
-                // The traceback kept leaving the ~1100 columns the plane holds around the backbone hints (a structural variant
-                // that carries the alignment further off).  The same packed sweep is repeated with a plane that keeps EVERY
-                // strip of every row -- rows x columns dwords, up to ~6 GB for a 26 kbp block, but it cannot miss, it covers
-                // every length the packed sweep covers (the 32-bit sweeps end at SXG_POA_MAX_SEQ_LEN_WIDE) and it runs at the
-                // packed sweep's speed.
-                m.wide_band = true;
-                again.push_back(b);
-            } else if (status[b] == ST_RANGE_OVERFLOW || status[b] == ST_BAND_MISS) {
-                // one step wider at the same capacity tier: packed -> int16 row words -> int32 row words
-                if (m.rm != 1) {
-                    classify_block(m, m.rm >= 2 ? 0 : 1, false);
-                    if (m.fits) again.push_back(b);
-                    else status[b] = ST_TOO_LONG;    // (a score range beyond int16 on a sequence beyond SXG_POA_MAX_SEQ_LEN_WIDE)
-                } else status[b] = ST_TOO_LONG;      // (unreachable: the int32 sweep reports neither)
-            }
-        }
-        h->stats.retries += (int)again.size();
-        pending.swap(again);
+        if (int rc = advance_ladders(h, plans, attempt, dbg, status, pending, nomem_blocks)) return rc;
         for (auto& pl : plans) all_plans.push_back(std::move(pl));
     }
     for (int b : pending) status[b] = ST_POOL_OVERFLOW;  // (unreachable: the ladders are shorter than the round limit)
     if (nb) HIPCHK(hipMemcpy(h->d_status.p, status.data(), 4 * (size_t)nb, hipMemcpyHostToDevice));
     lap("status");
-    // accounting
-    std::vector<unsigned long long> cells((size_t)std::max<int64_t>(h->n_seqs, 1));
-    if (h->n_seqs) HIPCHK(hipMemcpy(cells.data(), h->d_cells.p, 8 * (size_t)h->n_seqs, hipMemcpyDeviceToHost));
-    uint64_t total = 0, bytes = 0;
-    std::vector<uint64_t> blk_cells(std::max(nb, 1), 0), blk_bytes(std::max(nb, 1), 0);
-    for (int b = 0; b < nb; ++b) {
-        if (status[b] != ST_OK) continue;
-        uint64_t cb = 0;
-        for (int s = h->h_blk_off[b]; s < h->h_blk_off[b + 1]; ++s) cb += cells[s];
-        const BlockMeta& m = h->meta[b];
-        const int ncross = m.S.convex ? 3 : (m.S.g == m.S.e ? 1 : 2);
-        const int sz = m.rm == 1 ? 4 : 2;   // (banded: cells = band cells, as counted by the kernel)
-        blk_cells[b] = cb; blk_bytes[b] = cb * (uint64_t)(2 * ncross * sz + 1);
-        total += cb;
-        bytes += blk_bytes[b];
-    }
-    // dominant launch = the one that evaluated the most cells
-    for (auto& pl : all_plans) {
-        for (int b : pl.work) if (status[b] == ST_OK) { pl.cells += blk_cells[b]; pl.bytes += blk_bytes[b]; }
-        if (pl.cells >= h->stats.dom_cells) {
-            h->stats.dom_cells = pl.cells; h->stats.dom_algo_bytes = pl.bytes; h->stats.dom_kernel_ms = pl.ms;
-            h->stats.dom_threads = pl.variant.T(); h->stats.dom_cols_per_lane = pl.variant.W * (pl.variant.RM >= 2 ? 2 : 1);
-            h->stats.dom_row_mode = pl.variant.RM;
-            h->stats.dom_clock_mhz = pl.clock_mhz;
-            // (dom_cols_per_lane stays the class's W: an upper bound of the columns a dual-width launch's alignments swept)
-            h->wstats.dom_width = pl.variant.W; h->wstats.dom_width2 = pl.lay.W2;
-        }
-    }
+    if (int rc = account_cells(h, all_plans, status)) return rc;
     lap("accounting");
     h->stats.kernel_ms = ms_total;
-    h->stats.cells = total;
-    h->stats.algo_bytes = bytes;
     h->executed = true;
     if (h->want_block_graph) {
         int rc = run_block_graphs(h, status);
