@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-/* 5 (addition, no number change, no struct change): want_msa = SXG_MSA_TRIMMED -- the rows of the MAF built on the device -- and
+/* 5 (addition, no number change, no struct change): sxg_poa_group_* -- one process, several GPUs: a group of handles, one host
+ *    thread per member, the results reassembled in the batch's block order (trimmed MSA and block cycles included).
+ * 5 (addition, no number change, no struct change): want_msa = SXG_MSA_TRIMMED -- the rows of the MAF built on the device -- and
  *    sxg_poa_get_msa_stats.
  * 5 (addition, no number change): sxg_poa_path_sgd_order and struct sxg_poa_sgd_in -- the path-guided SGD node order of prep
  *    (src/prep.cpp:11-163) on the device, decree Y.
@@ -370,6 +372,48 @@ int sxg_poa_sharded_info(sxg_poa_handle *h, int32_t *ranks_seen, uint64_t *bytes
 int sxg_poa_sharded_timing(sxg_poa_handle *h, double *pack_ms, double *exchange_ms);
 /* Test entry: the same partition / packing / assembly with `nranks` simulated ranks on this one GPU. */
 int sxg_poa_batch_run_sharded_local(sxg_poa_handle *h, const sxg_poa_batch_in *in, int nranks, sxg_poa_batch_out *out);
+
+/* Device group (an addition to ABI 5): ONE process, several GPUs, every result reassembled.  A group owns one engine handle
+ * per entry of `devices` (1 <= n <= 16, each an existing device; anything else is SXG_E_INVALID).  The SAME device id may
+ * appear more than once: every entry is an independent handle with its own streams and arenas, so a group of {0, 0} runs --
+ * and is tested -- on a machine with one GPU (it shows that members coexist, not a speed-up).  There is no communicator, no
+ * rank, no collective, no timeout and no SXG_NOT_ROOT.
+ *   Deal: a function of the batch alone (smoothxg_amd/csrc/poa_deal.h): the prefix sum of the blocks' cost -- the cost the
+ *     sharded deal uses -- is cut at total * k / n, member k runs the contiguous slice of blocks that START in its window.  A
+ *     member carries at most total / n plus one block; a group with more members than blocks has empty members.
+ *   Run: one host thread per member with work, each on its member's device; upload, execute and download of a member run on
+ *     that member's streams at the same time as the others'; every thread is joined before a call returns, on success and on
+ *     failure.  SXG_POA_GROUP_SERIAL=1 runs the members one after the other on the calling thread (A/B runs, debugging).
+ *   Memory: sxg_poa_group_set_memory_budget sets the arena cap of every member.  The default cap of a handle (3/4 of its
+ *     device's free memory) is divided by the number of members on the same device, so that members which share a device do
+ *     not starve each other.
+ *   Result: everything sxg_poa_batch_run returns for the same input, in the batch's block order and byte for byte the same
+ *     arrays, for any n, any order of `devices`, concurrent or serial: statuses, scores, cells, raw graphs, per-base paths,
+ *     consensus, the full and the TRIMMED MSA (msa_off, msa_cols, msa), block graphs at want_block_graph 1, 2 and 3 (the rule
+ *     that a full MSA turns 2 and 3 into 1 applies unchanged), per-block params; block_cycles is present, one entry per block
+ *     (timings: not comparable between runs).  Every member downloads its slice as a single handle would; the slices are
+ *     copied into place by one thread per member and only the offsets are rebased.  Release with sxg_poa_batch_free.
+ *   Errors: a failed block sets status[b] and the call returns SXG_E_BLOCK with every other block complete, as
+ *     sxg_poa_batch_run does.  A member that fails as a whole (SXG_E_NOMEM, SXG_E_NODEVICE, ...) makes the call return that
+ *     code after all threads have joined, with `out` zeroed; the caller's thread then reads "group member <i> (device <d>)
+ *     failed in <stage>: <the member's message>" from the error text.
+ * sxg_poa_group_batch_run has the signature of the host library's provider (sxg_poa_run_fn) with the group as ctx;
+ * _upload / _execute / _download are its stages (_execute is repeatable).  sxg_poa_group_member returns member i (NULL out of
+ * range), owned by the group: for its stats and for the split, identity and SGD calls, which stay single-device.
+ * sxg_poa_group_timing, after a download: member_ms[n] host-clock milliseconds of every member's last execute + download (0
+ * for a member without blocks), pack_ms the longest member download (the device-side compaction of its arrays and their copy
+ * to the host), assemble_ms the reassembly on the host; any pointer may be NULL. */
+typedef struct sxg_poa_group sxg_poa_group;
+int sxg_poa_group_create(const int32_t *devices, int32_t n, sxg_poa_group **out);
+void sxg_poa_group_destroy(sxg_poa_group *g);
+int sxg_poa_group_size(const sxg_poa_group *g);
+sxg_poa_handle *sxg_poa_group_member(sxg_poa_group *g, int32_t i);
+int sxg_poa_group_set_memory_budget(sxg_poa_group *g, uint64_t bytes_per_member);
+int sxg_poa_group_batch_run(sxg_poa_group *g, const sxg_poa_batch_in *in, sxg_poa_batch_out *out);
+int sxg_poa_group_batch_upload(sxg_poa_group *g, const sxg_poa_batch_in *in);
+int sxg_poa_group_batch_execute(sxg_poa_group *g);
+int sxg_poa_group_batch_download(sxg_poa_group *g, sxg_poa_batch_out *out);
+int sxg_poa_group_timing(sxg_poa_group *g, double *member_ms, double *pack_ms, double *assemble_ms);
 
 /* sxg_poa_stats after the call: dp_launches, kernel_ms and n_slots of its launches (one per geometry, gap model and alignment
  * mode), dom_threads / dom_cols_per_lane / dom_row_mode / dom_kernel_ms of the launch with the most rows x letters. */

@@ -10,4 +10,4 @@ import os as _os
 # run side by side (read when the runtime initialises; see sxg_poa_create)
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from .poa import PoaEngine, PoaError, Params, params_from_cli, load_library, xxh64  # noqa: F401
+from .poa import PoaEngine, PoaGroup, PoaError, Params, params_from_cli, load_library, xxh64  # noqa: F401

@@ -24,6 +24,7 @@
 #include <dlfcn.h>
 #include "poa_kernels.hip.h"       // slot layout, launch arguments, the persistent kernels (device side)
 #include "poa_cost.h"              // a block's cost in its launch (rows x swept columns), the deal over CUs
+#include "poa_deal.h"              // the deal of a batch over the members of a device group (contiguous cuts of the cost)
 #include "poa_kern_tables.hip.h"   // kernel classes by geometry; instantiated in the kern_*.hip translation units
 #include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
@@ -305,6 +306,7 @@ struct sxg_poa_handle {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     int num_cu = 256;
     uint64_t mem_budget = 0;
+    int budget_share = 1;   // members of a device group on this handle's device: the default arena cap is divided among them
     // resident batch
     bool have_batch = false, executed = false;
     int n_blocks = 0;
@@ -532,7 +534,7 @@ static uint64_t arena_budget(sxg_poa_handle* h) {
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 8ull << 30;
     uint64_t avail = (uint64_t)fr + h->d_arena.cap;  // the arenas we already hold can be reused
     for (PlanRes* r : h->planres) avail += r->arena.cap;
-    uint64_t b = avail / 4 * 3;
+    uint64_t b = avail / 4 * 3 / (uint64_t)std::max(h->budget_share, 1);
     if (h->mem_budget && h->mem_budget < b) b = h->mem_budget;
     return b;
 }
@@ -1479,7 +1481,8 @@ struct OutOwner {
     std::vector<int32_t> status, score, msa_cols;
     hvec<int32_t> node_rank, node_group, edge_tail, edge_head, cons_nodes;
     int32_t* seq_path_nodes = nullptr;   // one node id per base: the big one (1.3 GB on the headline batch), never zero-filled
-    ~OutOwner() { free(seq_path_nodes); if (bg_steps_pinned && pin_pool) pin_pool->release(bg_steps_pinned); }
+    std::vector<void*> raw;              // arrays of a device group's reassembled result (host_big_alloc)
+    ~OutOwner() { free(seq_path_nodes); if (bg_steps_pinned && pin_pool) pin_pool->release(bg_steps_pinned); for (void* q : raw) free(q); }
     std::vector<int64_t> node_off, edge_off, cons_off, msa_off;
     hvec<uint8_t> node_code;
     hvec<uint32_t> edge_weight;
@@ -2398,6 +2401,334 @@ extern "C" int sxg_poa_batch_run_sharded_local(sxg_poa_handle* h, const sxg_poa_
     rc = assemble(in, parts, blobs, counts, out);
     if (rc && rc != SXG_E_BLOCK) sxg_poa_batch_free(out);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------
+// Device group: one process, several GPUs (include/sxg_poa.h).  A group owns one engine handle per entry
+// of its device list; a batch is dealt over the members in contiguous slices of equal cost (poa_deal.h), every member runs
+// the single-handle upload / execute / download on its slice from a host thread of its own -- on its own device, streams and
+// arenas, at the same time as the others --, and the results, being slices of the batch's dense arrays, are put back with one
+// copy per array and member.  No communicator, no rank, no collective, and no blob: what a member downloads IS its part of
+// the result (trimmed MSA rows, block graphs and block cycles included), only the offsets are rebased.
+struct sxg_poa_group {
+    std::vector<sxg_poa_handle*> members;
+    // the uploaded batch: its deal (member m runs blocks cut[m] .. cut[m + 1] - 1), where the slices start, who has work
+    bool have_batch = false, executed = false;
+    int n_blocks = 0;
+    int64_t n_seqs = 0;
+    std::vector<int32_t> cut, seq0;
+    std::vector<int64_t> base0;
+    std::vector<char> active;
+    // last execute + download: wall milliseconds per member, the longest download, the reassembly on the host
+    std::vector<double> exec_ms, down_ms;
+    double assemble_ms = 0;
+};
+
+namespace {
+bool group_serial() {
+    const char* e = getenv("SXG_POA_GROUP_SERIAL");
+    return e && atoi(e) != 0;
+}
+// fn(m) for every member with work, one host thread per member (SXG_POA_GROUP_SERIAL=1: one after the other on the calling
+// thread); every thread is joined before this returns.  A member that failed as a whole (anything but SXG_E_BLOCK) makes the
+// call return its code, with the member and the text of ITS thread's error in the caller's sxg_poa_last_error(); otherwise
+// SXG_E_BLOCK if some member reported failed blocks, else SXG_OK.
+template <class F>
+int group_for_each(sxg_poa_group* g, const char* what, F fn) {
+    const int n = (int)g->members.size();
+    std::vector<int> rc((size_t)n, SXG_OK);
+    std::vector<std::string> err((size_t)n);
+    auto body = [&](int m) {
+        const hipError_t e = hipSetDevice(g->members[(size_t)m]->device);
+        if (e != hipSuccess) { rc[(size_t)m] = SXG_E_NODEVICE; err[(size_t)m] = std::string("hipSetDevice: ") + hipGetErrorString(e); return; }
+        rc[(size_t)m] = fn(m);
+        if (rc[(size_t)m]) err[(size_t)m] = g_err;   // (the error text is per thread: carried over to the caller's below)
+    };
+    std::vector<std::thread> threads;
+    const bool serial = group_serial();
+    for (int m = 0; m < n; ++m) {
+        if (!g->active[(size_t)m]) continue;
+        bool started = false;
+        if (!serial) {
+            try { threads.emplace_back(body, m); started = true; } catch (...) { started = false; }   // (no thread to be had: run it here)
+        }
+        if (!started) body(m);
+    }
+    for (auto& t : threads) t.join();
+    for (int m = 0; m < n; ++m)
+        if (rc[(size_t)m] && rc[(size_t)m] != SXG_E_BLOCK)
+            return fail(rc[(size_t)m], std::string("group member ") + std::to_string(m) + " (device " + std::to_string(g->members[(size_t)m]->device) + ") failed in " +
+                                           what + ": " + err[(size_t)m]);
+    for (int m = 0; m < n; ++m)
+        if (rc[(size_t)m]) return fail(SXG_E_BLOCK, std::string("group member ") + std::to_string(m) + ": " + err[(size_t)m]);
+    return SXG_OK;
+}
+double ms_since(const std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+// The result struct's arrays by the index their offsets run over: the reassembly treats them alike.  Fields are addressed by
+// their place in the (standard-layout) struct; every one of them is a data pointer.
+struct GroupPayload { size_t field, elem; };
+struct GroupRagged { size_t off_field; int per_seq; GroupPayload pay[3]; };   // offsets [blocks + 1] (per_seq: [sequences + 1]) and what they index
+struct GroupFlat { size_t field, elem; int index; };                         // one entry per block (0), sequence (1) or base (2)
+#define SXG_GF(f) offsetof(sxg_poa_batch_out, f)
+const GroupRagged GROUP_RAGGED[] = {
+    {SXG_GF(node_off), 0, {{SXG_GF(node_code), 1}, {SXG_GF(node_rank), 4}, {SXG_GF(node_group), 4}}},
+    {SXG_GF(edge_off), 0, {{SXG_GF(edge_tail), 4}, {SXG_GF(edge_head), 4}, {SXG_GF(edge_weight), 4}}},
+    {SXG_GF(cons_off), 0, {{SXG_GF(cons_nodes), 4}, {0, 0}, {0, 0}}},
+    {SXG_GF(msa_off), 0, {{SXG_GF(msa), 1}, {0, 0}, {0, 0}}},
+    {SXG_GF(bg_node_off), 0, {{SXG_GF(bg_node_len), 4}, {SXG_GF(bg_node_outdeg), 4}, {SXG_GF(bg_node_indeg), 1}}},
+    {SXG_GF(bg_seq_off), 0, {{SXG_GF(bg_seq), 1}, {0, 0}, {0, 0}}},
+    {SXG_GF(bg_edge_off), 0, {{SXG_GF(bg_edge_to), 4}, {0, 0}, {0, 0}}},
+    {SXG_GF(bg_step_off), 1, {{SXG_GF(bg_steps), 4}, {0, 0}, {0, 0}}},
+    {SXG_GF(bg_cons_off), 0, {{SXG_GF(bg_cons_steps), 4}, {0, 0}, {0, 0}}},
+};
+const GroupFlat GROUP_FLAT[] = {
+    {SXG_GF(status), 4, 0}, {SXG_GF(msa_cols), 4, 0}, {SXG_GF(block_cycles), 8, 0},
+    {SXG_GF(score), 4, 1}, {SXG_GF(cells), 8, 1}, {SXG_GF(seq_path_nodes), 4, 2},
+};
+#undef SXG_GF
+constexpr int GROUP_N_RAGGED = (int)(sizeof(GROUP_RAGGED) / sizeof(GROUP_RAGGED[0])), GROUP_N_FLAT = (int)(sizeof(GROUP_FLAT) / sizeof(GROUP_FLAT[0]));
+void* get_field(const sxg_poa_batch_out& o, size_t at) { void* q; memcpy(&q, (const char*)&o + at, sizeof(q)); return q; }
+void set_field(sxg_poa_batch_out& o, size_t at, void* q) { memcpy((char*)&o + at, &q, sizeof(q)); }
+}  // namespace
+
+extern "C" int sxg_poa_group_create(const int32_t* devices, int32_t n, sxg_poa_group** out) {
+    if (!out) return fail(SXG_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!devices || n < 1 || n > 16) return fail(SXG_E_INVALID, "a group has 1 to 16 members");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(SXG_E_NODEVICE, "no HIP device available");
+    for (int i = 0; i < n; ++i)
+        if (devices[i] < 0 || devices[i] >= ndev) return fail(SXG_E_INVALID, "group member " + std::to_string(i) + ": device index out of range");
+    sxg_poa_group* g = new sxg_poa_group();
+    for (int i = 0; i < n; ++i) {
+        sxg_poa_handle* h = nullptr;
+        const int rc = sxg_poa_create(devices[i], &h);
+        if (rc) {
+            const std::string keep = g_err;
+            sxg_poa_group_destroy(g);
+            return fail(rc, "group member " + std::to_string(i) + ": " + keep);
+        }
+        g->members.push_back(h);
+    }
+    // members that share a device share its memory: each takes 1/k of what one handle would take by default
+    for (sxg_poa_handle* h : g->members) {
+        int k = 0;
+        for (sxg_poa_handle* o : g->members) k += o->device == h->device;
+        h->budget_share = k;
+    }
+    g->active.assign((size_t)n, 0);
+    g->exec_ms.assign((size_t)n, 0.0); g->down_ms.assign((size_t)n, 0.0);
+    *out = g;
+    return SXG_OK;
+}
+
+extern "C" void sxg_poa_group_destroy(sxg_poa_group* g) {
+    if (!g) return;
+    for (sxg_poa_handle* h : g->members) sxg_poa_destroy(h);
+    delete g;
+}
+
+extern "C" int sxg_poa_group_size(const sxg_poa_group* g) { return g ? (int)g->members.size() : 0; }
+
+extern "C" sxg_poa_handle* sxg_poa_group_member(sxg_poa_group* g, int32_t i) {
+    return g && i >= 0 && i < (int32_t)g->members.size() ? g->members[(size_t)i] : nullptr;
+}
+
+extern "C" int sxg_poa_group_set_memory_budget(sxg_poa_group* g, uint64_t bytes_per_member) {
+    if (!g) return fail(SXG_E_INVALID, "group is NULL");
+    for (sxg_poa_handle* h : g->members) h->mem_budget = bytes_per_member;
+    return SXG_OK;
+}
+
+extern "C" int sxg_poa_group_batch_upload(sxg_poa_group* g, const sxg_poa_batch_in* in) {
+    if (!g || !in) return fail(SXG_E_INVALID, "NULL argument");
+    g->have_batch = false; g->executed = false;
+    const int nb = in->n_blocks, n = (int)g->members.size();
+    if (nb < 0 || (nb > 0 && (!in->blk_off || !in->seq_off || !in->params))) return fail(SXG_E_INVALID, "batch_in has NULL arrays");
+    // (what the deal reads is checked here; everything else by every member's own upload)
+    if (nb > 0 && in->blk_off[0] != 0) return fail(SXG_E_INVALID, "blk_off[0] must be 0");
+    for (int b = 0; b < nb; ++b)
+        if (in->blk_off[b + 1] < in->blk_off[b]) return fail(SXG_E_INVALID, "blk_off not monotone");
+    const int64_t ns = nb ? in->blk_off[nb] : 0;
+    if (ns > 0 && in->seq_off[0] != 0) return fail(SXG_E_INVALID, "seq_off[0] must be 0");
+    for (int64_t s = 0; s < ns; ++s)
+        if (in->seq_off[s + 1] < in->seq_off[s]) return fail(SXG_E_INVALID, "seq_off not monotone");
+    if (ns > 0 && in->seq_off[ns] > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
+    sxg::deal_batch(nb, in->blk_off, in->seq_off, n, g->cut);
+    g->n_blocks = nb; g->n_seqs = ns;
+    g->seq0.assign((size_t)n + 1, 0); g->base0.assign((size_t)n + 1, 0);
+    struct Slice { std::vector<int32_t> blk_off; std::vector<int64_t> seq_off; sxg_poa_batch_in in; };
+    std::vector<Slice> slices((size_t)n);
+    for (int m = 0; m < n; ++m) {
+        const int b0 = g->cut[(size_t)m], b1 = g->cut[(size_t)m + 1];
+        const int32_t s0 = nb ? in->blk_off[b0] : 0, s1 = nb ? in->blk_off[b1] : 0;
+        const int64_t x0 = ns ? in->seq_off[s0] : 0;
+        g->seq0[(size_t)m] = s0; g->base0[(size_t)m] = x0;
+        g->active[(size_t)m] = b1 > b0 || (nb == 0 && m == 0);   // (a batch without blocks is member 0's: it answers as one handle does)
+        if (!g->active[(size_t)m]) continue;
+        Slice& S = slices[(size_t)m];
+        S.in = *in;
+        if (nb == 0) continue;
+        S.blk_off.resize((size_t)(b1 - b0) + 1); S.seq_off.resize((size_t)(s1 - s0) + 1);
+        for (int k = 0; k <= b1 - b0; ++k) S.blk_off[(size_t)k] = in->blk_off[b0 + k] - s0;
+        for (int k = 0; k <= s1 - s0; ++k) S.seq_off[(size_t)k] = in->seq_off[s0 + k] - x0;
+        // the slice reads the caller's letters, weights, params and trims in place: only the offsets are rebased
+        S.in.n_blocks = b1 - b0; S.in.blk_off = S.blk_off.data(); S.in.seq_off = S.seq_off.data();
+        S.in.bases = in->bases ? in->bases + x0 : nullptr;
+        S.in.weights = in->weights ? in->weights + s0 : nullptr;
+        S.in.params = in->per_block_params ? in->params + b0 : in->params;
+        S.in.bg_trim = in->bg_trim ? in->bg_trim + b0 : nullptr;
+    }
+    g->seq0[(size_t)n] = (int32_t)ns; g->base0[(size_t)n] = ns ? in->seq_off[ns] : 0;
+    const int rc = group_for_each(g, "upload", [&](int m) { return sxg_poa_batch_upload(g->members[(size_t)m], &slices[(size_t)m].in); });
+    if (rc) return rc;
+    g->have_batch = true;
+    return SXG_OK;
+}
+
+extern "C" int sxg_poa_group_batch_execute(sxg_poa_group* g) {
+    if (!g) return fail(SXG_E_INVALID, "group is NULL");
+    if (!g->have_batch) return fail(SXG_E_INVALID, "no batch uploaded");
+    g->executed = false;
+    std::fill(g->exec_ms.begin(), g->exec_ms.end(), 0.0);
+    std::fill(g->down_ms.begin(), g->down_ms.end(), 0.0);
+    g->assemble_ms = 0;
+    const int rc = group_for_each(g, "execute", [&](int m) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int r = sxg_poa_batch_execute(g->members[(size_t)m]);
+        g->exec_ms[(size_t)m] = ms_since(t0);
+        return r;
+    });
+    if (rc && rc != SXG_E_BLOCK) return rc;
+    g->executed = true;
+    if (rc) {   // the first failed block, by its number in the batch (as sxg_poa_batch_execute names it)
+        for (int m = 0; m < (int)g->members.size(); ++m) {
+            if (!g->active[(size_t)m]) continue;
+            const sxg_poa_handle* h = g->members[(size_t)m];
+            std::vector<int32_t> st((size_t)std::max(h->n_blocks, 1), 0);
+            if (h->n_blocks && (hipSetDevice(h->device) != hipSuccess ||
+                                hipMemcpy(st.data(), h->d_status.p, 4 * (size_t)h->n_blocks, hipMemcpyDeviceToHost) != hipSuccess))
+                return fail(SXG_E_NODEVICE, "group member " + std::to_string(m) + ": reading the block status failed");
+            for (int k = 0; k < h->n_blocks; ++k)
+                if (st[(size_t)k] != ST_OK)
+                    return fail(SXG_E_BLOCK, "block " + std::to_string(g->cut[(size_t)m] + k) + " failed with status " + std::to_string(st[(size_t)k]));
+        }
+    }
+    return rc;
+}
+
+extern "C" int sxg_poa_group_batch_download(sxg_poa_group* g, sxg_poa_batch_out* out) {
+    if (!g || !out) return fail(SXG_E_INVALID, "NULL argument");
+    memset(out, 0, sizeof(*out));
+    if (!g->have_batch || !g->executed) return fail(SXG_E_INVALID, "no executed batch to download");
+    const int n = (int)g->members.size(), nb = g->n_blocks;
+    const int64_t ns = g->n_seqs;
+    std::vector<sxg_poa_batch_out> outs((size_t)n);
+    for (auto& o : outs) memset(&o, 0, sizeof(o));
+    auto drop = [&] { for (auto& o : outs) sxg_poa_batch_free(&o); };
+    int rc = group_for_each(g, "download", [&](int m) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int r = sxg_poa_batch_download(g->members[(size_t)m], &outs[(size_t)m]);
+        g->down_ms[(size_t)m] = ms_since(t0);
+        return r;
+    });
+    if (rc) { const std::string keep = g_err; drop(); return fail(rc, keep); }
+    const auto t_asm = std::chrono::steady_clock::now();
+    int first = -1, n_active = 0;
+    for (int m = 0; m < n; ++m)
+        if (g->active[(size_t)m]) { if (first < 0) first = m; ++n_active; }
+    if (n_active == 1) {
+        *out = outs[(size_t)first];   // one slice is the whole batch: the member's result is the group's
+        memset(&outs[(size_t)first], 0, sizeof(sxg_poa_batch_out));
+    } else {
+        // Several slices: offsets first (each member's start at 0: rebased by what the members before it hold), then every
+        // member's arrays into their places, one thread per member.
+        OutOwner* o = new OutOwner();
+        out->_owner = o; out->n_blocks = nb; out->n_seqs = ns;
+        bool oom = false;
+        auto alloc = [&](size_t bytes) -> void* {
+            void* q = host_big_alloc(std::max<size_t>(bytes, 8));
+            if (q) o->raw.push_back(q); else oom = true;
+            return q;
+        };
+        const sxg_poa_batch_out& T = outs[(size_t)first];   // (every member was handed the same request: the same arrays are present)
+        std::vector<int64_t> start((size_t)GROUP_N_RAGGED * (size_t)n, 0), total((size_t)GROUP_N_RAGGED * (size_t)n, 0);
+        for (int a = 0; a < GROUP_N_RAGGED && !oom; ++a) {
+            const GroupRagged& A = GROUP_RAGGED[a];
+            if (!get_field(T, A.off_field)) continue;
+            int64_t* off = (int64_t*)alloc(8 * (size_t)((A.per_seq ? ns : (int64_t)nb) + 1));
+            if (!off) break;
+            int64_t running = 0;
+            off[0] = 0;
+            for (int m = 0; m < n; ++m) {
+                if (!g->active[(size_t)m]) continue;
+                const int64_t* src = (const int64_t*)get_field(outs[(size_t)m], A.off_field);
+                const int64_t i0 = A.per_seq ? g->seq0[(size_t)m] : g->cut[(size_t)m];
+                const int64_t cnt = A.per_seq ? g->seq0[(size_t)m + 1] - g->seq0[(size_t)m] : g->cut[(size_t)m + 1] - g->cut[(size_t)m];
+                for (int64_t k = 0; k <= cnt; ++k) off[i0 + k] = running + src[k];
+                start[(size_t)a * n + m] = running; total[(size_t)a * n + m] = src[cnt];
+                running += src[cnt];
+            }
+            set_field(*out, A.off_field, off);
+            for (const GroupPayload& P : A.pay)
+                if (P.elem && get_field(T, P.field)) set_field(*out, P.field, alloc((size_t)running * P.elem));
+        }
+        for (int f = 0; f < GROUP_N_FLAT && !oom; ++f) {
+            const GroupFlat& F = GROUP_FLAT[f];
+            if (!get_field(T, F.field)) continue;
+            const int64_t cnt = F.index == 0 ? nb : F.index == 1 ? ns : g->base0[(size_t)n];
+            set_field(*out, F.field, alloc((size_t)cnt * F.elem));
+        }
+        if (oom) { drop(); sxg_poa_batch_free(out); return fail(SXG_E_NOMEM, "host allocation of the group's result failed"); }
+        rc = group_for_each(g, "reassembly", [&](int m) {
+            const sxg_poa_batch_out& M = outs[(size_t)m];
+            for (int a = 0; a < GROUP_N_RAGGED; ++a)
+                for (const GroupPayload& P : GROUP_RAGGED[a].pay) {
+                    uint8_t* dst = P.elem ? (uint8_t*)get_field(*out, P.field) : nullptr;
+                    const size_t bytes = (size_t)total[(size_t)a * n + m] * P.elem;
+                    if (dst && bytes) memcpy(dst + (size_t)start[(size_t)a * n + m] * P.elem, get_field(M, P.field), bytes);
+                }
+            for (const GroupFlat& F : GROUP_FLAT) {
+                uint8_t* dst = (uint8_t*)get_field(*out, F.field);
+                const int64_t i0 = F.index == 0 ? g->cut[(size_t)m] : F.index == 1 ? g->seq0[(size_t)m] : g->base0[(size_t)m];
+                const int64_t i1 = F.index == 0 ? g->cut[(size_t)m + 1] : F.index == 1 ? g->seq0[(size_t)m + 1] : g->base0[(size_t)m + 1];
+                if (dst && i1 > i0) memcpy(dst + (size_t)i0 * F.elem, get_field(M, F.field), (size_t)(i1 - i0) * F.elem);
+            }
+            return SXG_OK;
+        });
+        if (rc) { const std::string keep = g_err; drop(); sxg_poa_batch_free(out); return fail(rc, keep); }
+    }
+    drop();
+    g->assemble_ms = ms_since(t_asm);
+    return SXG_OK;
+}
+
+extern "C" int sxg_poa_group_batch_run(sxg_poa_group* g, const sxg_poa_batch_in* in, sxg_poa_batch_out* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!out) return fail(SXG_E_INVALID, "NULL argument");
+    int rc = sxg_poa_group_batch_upload(g, in);
+    if (rc) return rc;
+    rc = sxg_poa_group_batch_execute(g);
+    if (rc && rc != SXG_E_BLOCK) return rc;
+    const std::string keep = g_err;
+    const int rc2 = sxg_poa_group_batch_download(g, out);
+    if (rc2) return rc2;
+    if (rc) g_err = keep;
+    return rc;
+}
+
+extern "C" int sxg_poa_group_timing(sxg_poa_group* g, double* member_ms, double* pack_ms, double* assemble_ms) {
+    if (!g) return fail(SXG_E_INVALID, "group is NULL");
+    double longest = 0;
+    for (size_t m = 0; m < g->members.size(); ++m) {
+        if (member_ms) member_ms[m] = g->exec_ms[m] + g->down_ms[m];
+        longest = std::max(longest, g->down_ms[m]);
+    }
+    if (pack_ms) *pack_ms = longest;
+    if (assemble_ms) *assemble_ms = g->assemble_ms;
+    return SXG_OK;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -131,7 +131,10 @@ EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_km
            "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_get_twin_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
            "sxg_poa_comm_attach", "sxg_poa_comm_destroy", "sxg_poa_batch_run_sharded", "sxg_poa_batch_run_sharded_local",
            "sxg_poa_batch_upload_sharded", "sxg_poa_batch_execute_sharded", "sxg_poa_batch_download_sharded", "sxg_poa_sharded_info",
-           "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available", "sxg_poa_get_msa_stats", "sxg_poa_msa_geometry"]
+           "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available", "sxg_poa_get_msa_stats", "sxg_poa_msa_geometry",
+           "sxg_poa_group_create", "sxg_poa_group_destroy", "sxg_poa_group_size", "sxg_poa_group_member", "sxg_poa_group_set_memory_budget",
+           "sxg_poa_group_batch_run", "sxg_poa_group_batch_upload", "sxg_poa_group_batch_execute", "sxg_poa_group_batch_download",
+           "sxg_poa_group_timing"]
 COMM_ID_BYTES = 128
 NOT_ROOT = 1
 
@@ -182,6 +185,18 @@ def load_library(build_if_missing=True):
     L.sxg_poa_batch_download_sharded.argtypes = [vp, C.POINTER(BatchIn), C.POINTER(BatchOut)]
     L.sxg_poa_sharded_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
     L.sxg_poa_sharded_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.sxg_poa_group_create.argtypes = [_i32p, C.c_int32, C.POINTER(vp)]
+    L.sxg_poa_group_destroy.argtypes = [vp]
+    L.sxg_poa_group_destroy.restype = None
+    L.sxg_poa_group_size.argtypes = [vp]
+    L.sxg_poa_group_member.argtypes = [vp, C.c_int32]
+    L.sxg_poa_group_member.restype = vp
+    L.sxg_poa_group_set_memory_budget.argtypes = [vp, C.c_uint64]
+    L.sxg_poa_group_batch_run.argtypes = [vp, C.POINTER(BatchIn), C.POINTER(BatchOut)]
+    L.sxg_poa_group_batch_upload.argtypes = [vp, C.POINTER(BatchIn)]
+    L.sxg_poa_group_batch_execute.argtypes = [vp]
+    L.sxg_poa_group_batch_download.argtypes = [vp, C.POINTER(BatchOut)]
+    L.sxg_poa_group_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.sxg_poa_pair_identity_batch.argtypes = [vp, C.c_int64, _i64p, _u8p, C.c_int64, _i32p, _i32p, _u8p, _i32p, _i32p, _i32p, _i32p]
     L.sxg_poa_split_batch.argtypes = [vp, C.POINTER(SplitIn), C.POINTER(SplitOut)]
     L.sxg_poa_split_free.argtypes = [C.POINTER(SplitOut)]
@@ -718,6 +733,117 @@ class PoaEngine:
                     for k in range(n)]
         finally:
             self.lib.sxg_poa_align_free(C.byref(out))
+
+
+class _MemberEngine(PoaEngine):
+    """Member i of a PoaGroup as an engine: the handle is the group's, so close() leaves it alone."""
+
+    def __init__(self, lib, h):
+        self.lib, self.h, self._keep, self._shape = lib, h, None, None
+
+    def close(self):
+        self.h = None
+
+
+class PoaGroup:
+    """One process, several GPUs (sxg_poa_group): one engine handle per entry of `devices` -- the same device may appear more
+    than once --, a batch dealt over them in contiguous slices of equal cost, one host thread per member, the results
+    reassembled in the batch's block order.  Mirrors PoaEngine: run_flat / run_blocks / upload / execute / download return
+    what a single engine returns for the same input."""
+
+    def __init__(self, devices):
+        self.lib = load_library()
+        if self.lib.sxg_poa_device_count() <= 0:
+            raise PoaError("no HIP device: the blocked-POA engine has no CPU fallback")
+        devices = [int(d) for d in devices]
+        arr = (C.c_int32 * max(len(devices), 1))(*devices)
+        h = C.c_void_p()
+        if self.lib.sxg_poa_group_create(arr, len(devices), C.byref(h)):
+            raise PoaError("sxg_poa_group_create: %s" % self.lib.sxg_poa_last_error().decode())
+        self.h = h
+        self.devices = devices
+        self._keep = None
+        self._shape = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.sxg_poa_group_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return int(self.lib.sxg_poa_group_size(self.h))
+
+    _err = PoaEngine._err
+    _mk_in = PoaEngine._mk_in
+    _unpack = PoaEngine._unpack
+    run_blocks = PoaEngine.run_blocks
+
+    def set_memory_budget(self, nbytes_per_member):
+        self.lib.sxg_poa_group_set_memory_budget(self.h, int(nbytes_per_member))
+
+    def member(self, i):
+        """Member i as a PoaEngine (owned by the group): its stats, and the split, identity and SGD calls, which stay
+        single-device."""
+        h = self.lib.sxg_poa_group_member(self.h, int(i))
+        if not h:
+            raise IndexError("no such group member: %r" % (i,))
+        return _MemberEngine(self.lib, C.c_void_p(h))
+
+    def stats(self, i):
+        return self.member(i).stats()
+
+    def timing(self):
+        """sxg_poa_group_timing of the last execute + download: milliseconds per member, of the longest member download and
+        of the reassembly on the host."""
+        n = len(self)
+        ms = (C.c_double * n)()
+        pk, asm = C.c_double(), C.c_double()
+        self.lib.sxg_poa_group_timing(self.h, ms, C.byref(pk), C.byref(asm))
+        return {"member_ms": list(ms), "pack_ms": pk.value, "assemble_ms": asm.value}
+
+    def upload(self, bases, seq_off, blk_off, weights, params, want_consensus=False, want_msa=False, block_graph=0,
+               bg_trim=None, bg_cons_visited_only=False):
+        bi = self._mk_in(bases, seq_off, blk_off, weights, params, want_consensus, want_msa, block_graph, bg_trim,
+                         bg_cons_visited_only)
+        if self.lib.sxg_poa_group_batch_upload(self.h, C.byref(bi)):
+            raise self._err("sxg_poa_group_batch_upload")
+        self._shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy(), int(want_msa))
+
+    def execute(self, check=True):
+        rc = self.lib.sxg_poa_group_batch_execute(self.h)
+        if rc and (check or rc != -4):
+            raise self._err("sxg_poa_group_batch_execute")
+        return rc
+
+    def download(self):
+        out = BatchOut()
+        if self.lib.sxg_poa_group_batch_download(self.h, C.byref(out)):
+            raise self._err("sxg_poa_group_batch_download")
+        try:
+            return self._unpack(out)
+        finally:
+            self.lib.sxg_poa_batch_free(C.byref(out))
+
+    def run_flat(self, bases, seq_off, blk_off, weights, params, want_consensus=False, want_msa=False,
+                 check=True, block_graph=0, bg_trim=None, bg_cons_visited_only=False):
+        bi = self._mk_in(bases, seq_off, blk_off, weights, params, want_consensus, want_msa, block_graph, bg_trim,
+                         bg_cons_visited_only)
+        self._shape = (np.asarray(blk_off).copy(), np.asarray(seq_off).copy(), int(want_msa))
+        out = BatchOut()
+        rc = self.lib.sxg_poa_group_batch_run(self.h, C.byref(bi), C.byref(out))
+        self.last_rc = rc      # (0, or -4 = SXG_E_BLOCK with check=False: some block failed, see the results' status)
+        try:
+            if rc and (check or rc != -4):
+                raise self._err("sxg_poa_group_batch_run")
+            return self._unpack(out)
+        finally:
+            self.lib.sxg_poa_batch_free(C.byref(out))
 
 
 def xxh64(data: bytes, seed=0):

@@ -133,8 +133,14 @@ def adaptive_poa_scores(est_identity_threshold, set_scores=(1, 4, 6, 2, 26, 1)):
 
 def gpu_provider(engine, sharded=False):
     """(run, free, ctx) backed by the GPU engine: raw C entry points of libsxgpoa.so.  sharded=True: the multi-GPU
-    entry (sxg_poa_batch_run_sharded over the engine's communicator): every rank runs the same iteration, rank 0 laces."""
+    entry (sxg_poa_batch_run_sharded over the engine's communicator): every rank runs the same iteration, rank 0 laces.
+    A PoaGroup in place of the engine: sxg_poa_group_batch_run with the group as ctx -- every provider call of the iteration
+    spreads over the group's members; the identity, split and sort providers take one of its members (group.member(i))."""
     L = engine.lib
+    if isinstance(engine, _poa.PoaGroup):
+        if sharded:
+            raise ValueError("a device group runs in one process: it has no sharded entry")
+        return C.cast(L.sxg_poa_group_batch_run, C.c_void_p), C.cast(L.sxg_poa_batch_free, C.c_void_p), engine.h
     run = C.cast(L.sxg_poa_batch_run_sharded if sharded else L.sxg_poa_batch_run, C.c_void_p)
     fre = C.cast(L.sxg_poa_batch_free, C.c_void_p)
     return run, fre, engine.h
