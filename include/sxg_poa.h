@@ -73,6 +73,13 @@ extern "C" {
  * touched are walked again -- 1.01 x the kernel time on 64 x 5 kbp blocks, 1.05 x on 8000 blocks of 16 x 1 kbp; the
  * host library sets the flag by default. */
 #define SXG_ORDER_SPOA 0x10
+/* OR-ed into sxg_poa_params::mode, only together with SXG_ORDER_SPOA (alone: SXG_E_INVALID): the new nodes of a sequence get
+ * their ids in the order spoa's Graph::AddAlignment is BELIEVED to create them (decree S6' of DESIGN.md section 2, restated
+ * from memory, unverified) -- the unaligned prefix chain, then the unaligned suffix chain, then the new nodes inside the span
+ * the alignment covers -- instead of in sequence order (decree S6).  Ids decide where the re-sort's walks start, hence ranks,
+ * ties of later alignments and MSA columns.  Global alignments cover every position: there the flag changes nothing.  An
+ * addition (no struct changed): the ABI version stays 5.  Off by default everywhere. */
+#define SXG_IDS_SPOA 0x20
 
 /* return codes */
 #define SXG_OK 0

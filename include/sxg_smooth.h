@@ -76,7 +76,10 @@ typedef struct sxg_smooth_params {
                                                          graph.AddAlignment does at src/smooth.cpp:764, and the re-sort is a
                                                          parallel, incremental device phase now (1-5 % of the kernel time at full batches,
                                                          DESIGN.md).  Ignored with use_abpoa (abPOA does not call spoa's sort).
-                                                         0 = the order of rounds 1-5. */
+                                                         0 = the order of rounds 1-5.
+                                                         2 = as 1, and the new nodes of a sequence get their ids in the order spoa's
+                                                         AddAlignment is believed to create them (SXG_IDS_SPOA, decree S6', restated
+                                                         from memory, unverified); opt-in, dropped with use_abpoa as 1 is. */
 } sxg_smooth_params;
 
 void sxg_smooth_default_params(sxg_smooth_params *p);

@@ -122,9 +122,11 @@ SXG_HD int group_end(const GraphView& G, int leader, int n_old) {
 // neither reads nor keeps the incrementally kept order): the slots of the new nodes, the shift of the old ones and the copy of
 // the order -- the gathers through the groups' ranks and two passes over all nodes -- are left out.
 // (Reads the walk's result, posnode, per sequence POSITION: the strip width the sweep and its traceback ran at does not reach it.)
+// ids_spoa (decree S6', sxg_poa_params::mode | SXG_IDS_SPOA, LOCAL mode only -- a global walk holds every position and the
+// caller passes false): the new nodes are numbered prefix chain, suffix chain, span; only with keep_order = false.
 template <class Ctx>
 SXG_HD_PHASE void add_alignment(Ctx& c, const GraphView& G_, const uint8_t* seq_, int len,
-                          uint32_t weight, int32_t* path_out_, const bool keep_order = true) {
+                          uint32_t weight, int32_t* path_out_, const bool keep_order = true, const bool ids_spoa = false) {
     const GraphView G = sxg_scalar_view(G_);   // (pointers through the scalar unit once: see poa_types.h)
     SXG_GP const uint8_t* const seq = sxg_scalar_ptr((SXG_GP const uint8_t*)seq_);   // both live in HBM
     SXG_GP int32_t* const path_out = sxg_scalar_ptr((SXG_GP int32_t*)path_out_);
@@ -160,13 +162,23 @@ SXG_HD_PHASE void add_alignment(Ctx& c, const GraphView& G_, const uint8_t* seq_
     array_suffix_min(c, len, [&](int i) { return G.kind[i] != 2 ? i : BIG; }, G.nexta);
     if (keep_order) for (int r = t; r <= n_old; r += T) G.slotadd[r] = 0;
     c.sync();
+    // S6' (ids_spoa): ids in spoa's AddAlignment order -- the unaligned prefix [0, first), then the unaligned suffix (last, len),
+    // then the new nodes of the span [first, last] the walk covers.  first / last: the first / last aligned position (a local
+    // walk neither begins nor ends on an insertion); an empty walk (first = BIG) is one chain.  Both are read
+    // here, before P4 takes nexta for its own use.  Without the flag the span is the whole sequence: the offset is newidx.
+    const bool id_span = ids_spoa && len > 0;
+    const int id_first = id_span ? G.nexta[0] : 0, id_last = id_span ? G.preva[len - 1] : len - 1;
+    const int id_sfx = len - 1 - id_last;   // nodes of the suffix chain
+    auto new_id = [&](const int i, const int k) -> int {
+        return n_old + (i < id_first ? k : (i > id_last ? id_first + (i - id_last - 1) : k + id_sfx));
+    };
     // P2: create the new nodes, hand out slots (S7) and final ranks of the new nodes
     for (int i = t; i < len; i += T) {
         const int kind = G.kind[i];
         if (kind == 0) { path_out[i] = G.target[i]; continue; }
         const int cc = seq[i] > 4 ? 4 : seq[i];
         const int k = G.newidx[i];
-        const int v = n_old + k;
+        const int v = new_id(i, k);
         G.code[v] = (uint8_t)cc;
         G.in_head[v] = G.in_tail[v] = G.out_head[v] = G.out_tail[v] = -1;
         G.in_deg[v] = G.out_deg[v] = 0;
@@ -203,7 +215,7 @@ SXG_HD_PHASE void add_alignment(Ctx& c, const GraphView& G_, const uint8_t* seq_
     c.sync();
     for (int i = t; i < len; i += T) {
         if (G.kind[i] == 0) continue;
-        const int v = n_old + G.newidx[i];
+        const int v = new_id(i, G.newidx[i]);
         if (G.kind[i] == 1) G.gmem[5 * G.leader[v] + G.code[v]] = v;
         G.target[i] = v;
     }

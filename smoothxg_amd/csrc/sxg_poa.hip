@@ -561,8 +561,11 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
     const int np = in->per_block_params ? nb : 1;
     for (int k = 0; k < np && nb > 0; ++k) {
         const sxg_poa_params& p = in->params[k];
-        if (p.m < 0 || p.n > 0 || p.g > 0 || p.e > 0 || p.q > 0 || p.c > 0 || (p.mode & ~(1 | SXG_ORDER_SPOA)) != 0 || p.banded > 2)
+        if (p.m < 0 || p.n > 0 || p.g > 0 || p.e > 0 || p.q > 0 || p.c > 0 || (p.mode & ~(1 | SXG_ORDER_SPOA | SXG_IDS_SPOA)) != 0 || p.banded > 2)
             return fail(SXG_E_INVALID, "scores must follow spoa's sign convention (m>=0, others <=0), mode 0|1");
+        // (S6' numbers the new nodes for the re-sort S7'; the incrementally kept order places them by their sequence-order index)
+        if ((p.mode & SXG_IDS_SPOA) && !(p.mode & SXG_ORDER_SPOA))
+            return fail(SXG_E_INVALID, "mode | SXG_IDS_SPOA needs SXG_ORDER_SPOA");
     }
     h->n_blocks = nb; h->n_seqs = ns; h->n_bases = nbases;
     h->want_consensus = in->want_consensus; h->want_msa = in->want_msa;

@@ -678,7 +678,9 @@ void add_to_batch(batch_t& B, const collected_t& c) {
 sxg_poa_params poa_params(const sxg_smooth_params& p) {  // src/smooth.cpp:2098-2106
     sxg_poa_params q;
     // (spoa's node order belongs to the spoa path: smooth_abpoa never calls spoa's sort, the `-A` path keeps the engine's own order)
-    q.mode = (uint8_t)((p.local_alignment ? SXG_MODE_LOCAL : SXG_MODE_GLOBAL) | (p.poa_spoa_order && !p.use_abpoa ? SXG_ORDER_SPOA : 0)); q.banded = 0;
+    // (poa_spoa_order = 2: spoa's node ids as well, decree S6' -- with the order, and dropped with it)
+    q.mode = (uint8_t)((p.local_alignment ? SXG_MODE_LOCAL : SXG_MODE_GLOBAL) | (p.poa_spoa_order && !p.use_abpoa ? SXG_ORDER_SPOA : 0) |
+                       (p.poa_spoa_order == 2 && !p.use_abpoa ? SXG_IDS_SPOA : 0)); q.banded = 0;
     if (!p.use_abpoa) {
         q.m = (int8_t)p.poa_m; q.n = (int8_t)-p.poa_n; q.g = (int8_t)-p.poa_g; q.e = (int8_t)-p.poa_e; q.q = (int8_t)-p.poa_q; q.c = (int8_t)-p.poa_c;
         return q;

@@ -14,6 +14,8 @@ import numpy as np
 from . import build as _build
 
 MODE_LOCAL, MODE_GLOBAL = 0, 1
+ORDER_SPOA = 0x10   # SXG_ORDER_SPOA, OR-ed into Params.mode: spoa's depth-first re-sort after every alignment (decree S7')
+IDS_SPOA = 0x20     # SXG_IDS_SPOA, only with ORDER_SPOA: new node ids in spoa's AddAlignment order (decree S6')
 
 
 class Params(C.Structure):
