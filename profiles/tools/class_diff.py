@@ -68,6 +68,10 @@ def functions(co):
 
     def close():
         if cur is not None:
+            # (what follows a function's last instruction -- s_nop 0 and "..." -- pads the next symbol to its alignment: it moves
+            #  with the sizes of the functions before it, not with this one)
+            while lines and lines[-1].strip() in ("s_nop 0", "..."):
+                lines.pop()
             text = "\n".join(lines)
             loose = "\n".join(CALL_LIT.sub(r"\1<rel>", l) for l in lines)
             funcs[cur] = (hashlib.sha1(text.encode()).hexdigest(), hashlib.sha1(loose.encode()).hexdigest(), len(lines))

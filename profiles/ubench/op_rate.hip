@@ -93,7 +93,11 @@ BODY(k_max3_f32, "v_max3_f32 %0, %0, %1, %2")
 BODY(k_pk_max_i16_opsel, "v_pk_max_i16 %0, %0, %1 op_sel:[0,1] op_sel_hi:[1,0]")
 BODY(k_mix_sub_pkmax, "v_sub_u32 %0, %0, %1\n\tv_pk_max_i16 %0, %0, %2")
 BODY(k_mix_sub_pkmaxf16, "v_sub_u32 %0, %0, %1\n\tv_pk_max_f16 %0, %0, %2")
-BODY(k_add_u32_sdwa, "v_add_u32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0")
+// (round 18: the three-input binary16 maximum that can stand for two v_pk_max_i16 on the biased local fields)
+BODY(k_pk_maximum3_f16, "v_pk_maximum3_f16 %0, %0, %1, %2")
+BODY(k_pk_minimum3_f16, "v_pk_minimum3_f16 %0, %0, %1, %2")
+BODY(k_mix_sub_pkmaximum3, "v_sub_u32 %0, %0, %1\n\tv_pk_maximum3_f16 %0, %0, %2, %1")
+BODY(k_add_u32_sdwa,"v_add_u32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0")
 BODY(k_max_i16_sdwa, "v_max_i16_sdwa %0, %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_1")
 typedef void (*kern_t)(int*, unsigned long long*, int, int);
 static FILE* g_json = nullptr;
@@ -139,7 +143,7 @@ int main(int argc, char** argv) {
     R(k_cndmask_b32) R(k_cndmask_e64_sgpr) R(k_cmp_then_cndmask) R(k_cmp_e64_then_cndmask_e64) R(k_cmp_gt_i32) R(k_max_i16) R(k_max_u16) R(k_add_u16) R(k_max_f16) R(k_pk_max_u16) R(k_pk_add_u16) R(k_pk_max_f16) R(k_pk_min_f16)
     R(k_pk_add_f16) R(k_pk_mul_f16) R(k_pk_fma_f16) R(k_pk_lshlrev_b16) R(k_pk_ashrrev_i16) R(k_mov_dpp_shr) R(k_add_dpp_shr) R(k_maxf_dpp_shr) R(k_mov_dpp_wshr)
     R(k_mad_u32_u24) R(k_mul_u32_u24) R(k_bfe_u32) R(k_alignbit_b32) R(k_alignbyte_b32) R(k_lshl_add_u32) R(k_add_lshl_u32) R(k_med3_i32) R(k_min3_u32) R(k_max3_f32)
-    R(k_pk_max_i16_opsel) R(k_mix_sub_pkmax) R(k_mix_sub_pkmaxf16) R(k_add_u32_sdwa) R(k_max_i16_sdwa)
+    R(k_pk_max_i16_opsel) R(k_mix_sub_pkmax) R(k_mix_sub_pkmaxf16) R(k_pk_maximum3_f16) R(k_pk_minimum3_f16) R(k_mix_sub_pkmaximum3) R(k_add_u32_sdwa) R(k_max_i16_sdwa)
     for (int w : {1, 2, 8}) { run("k_pk_add_i16", k_pk_add_i16, w); run("k_pk_max_i16", k_pk_max_i16, w); run("k_perm_b32", k_perm_b32, w); run("k_max_dpp_shr", k_max_dpp_shr, w); run("k_add_u32", k_add_u32, w); }
     if (g_json) { fprintf(g_json, "\n]\n"); fclose(g_json); }
     return 0;

@@ -34,6 +34,7 @@
 #include <utility>
 #include "poa_dp.hip.h"
 #include "poa_rowcode.h"
+#include "poa_fields.h"
 
 namespace sxg {
 
@@ -50,24 +51,22 @@ constexpr int NEGP = -16384;  // "minus infinity" of the packed sweep
 // reports ST_RANGE_OVERFLOW and the block is re-run on the 32-bit sweep, as before.  (Rounds 1-4 sent every global
 // alignment whose corner did not fit down that ladder up front: 130 blocks/s instead of the packed sweep's rate.)
 constexpr int P16_NWFLOOR = -16000;
-// smoothxg's default scores in the engine's (spoa's) sign convention: the score set the DS kernel classes are compiled for
-constexpr int P16_DEF_M = 1, P16_DEF_N = -4, P16_DEF_G = -6, P16_DEF_E = -2, P16_DEF_Q = -26, P16_DEF_C = -1;
+// (the default scores P16_DEF_* the DS kernel classes are compiled for: poa_fields.h)
 __host__ __device__ inline bool p16_default_scores(const Scoring& S) {
     return S.convex && S.m == P16_DEF_M && S.n == P16_DEF_N && S.g == P16_DEF_G && S.e == P16_DEF_E && S.q == P16_DEF_Q && S.c == P16_DEF_C;
 }
-// LOCAL alignments run the packed sweep on BIASED fields: a register half holds score + P16_BIAS, always inside
-// [P16_FLOOR, 32767].  Every reachable value of a local alignment is >= min(g, q) >= -120 (H >= 0, every gap state is
-// some H plus at most one opening) and the few "minus infinity" inputs (the column left of column 0, a carry that enters
-// strip 0) are replaced by P16_FLOOR - P16_BIAS = -512, which never wins a maximum.  Fields that never leave
-// [0, 65535] make a PLAIN 32-bit add/subtract of a constant -- or of any register whose fields do not underflow --
-// correct on both halves at once (no borrow ever crosses bit 16), and on gfx950 v_add_u32 / v_sub_u32 issue every 2
-// cycles per wave where every VOP3P instruction (v_pk_add_i16, v_pk_max_i16, ...) takes 4
-// (profiles/r03/op_rate.txt): 37 % of the row loop's VALU instructions were packed adds and subtracts.
-constexpr int P16_BIAS = 1024, P16_FLOOR = 512;
+// (LOCAL alignments run the packed sweep on BIASED fields: P16_BIAS, P16_FLOOR and the range they stay in -- poa_fields.h)
 
 __device__ __forceinline__ int pk_add(int a, int b) { return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, a) + __builtin_bit_cast(s16x2, b))); }
 __device__ __forceinline__ int pk_sub(int a, int b) { return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, a) - __builtin_bit_cast(s16x2, b))); }
 __device__ __forceinline__ int pk_max(int a, int b) { return __builtin_bit_cast(int, __builtin_elementwise_max(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b))); }
+// Three-way maximum of BIASED fields in one instruction (v_pk_maximum3_f16): exactly pk_max(pk_max(a, b), c) while every field
+// of a, b, c is a pattern in [0, P16_F16_TOP] -- the local classes compiled for the default scores (poa_fields.h has the
+// argument and the bound).  The builtin form, not inline asm: the scheduler and the hazard recogniser know the instruction.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ int pk_max3(int a, int b, int c) {
+    return __builtin_bit_cast(int, __builtin_elementwise_maximum(__builtin_elementwise_maximum(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b)), __builtin_bit_cast(f16x2, c)));
+}
 __device__ __forceinline__ int pk_mad(int a, int b, int c) { return __builtin_bit_cast(int, (s16x2)(__builtin_bit_cast(s16x2, a) * __builtin_bit_cast(s16x2, b) + __builtin_bit_cast(s16x2, c))); }
 __device__ __forceinline__ int pk_lshr(int a, int sh) { return __builtin_bit_cast(int, (u16x2)(__builtin_bit_cast(u16x2, a) >> __builtin_bit_cast(u16x2, sh))); }
 __device__ __forceinline__ int pk2(int lo, int hi) { return (lo & 0xffff) | (hi << 16); }

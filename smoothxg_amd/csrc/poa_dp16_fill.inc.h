@@ -31,6 +31,10 @@
     const int G2 = pk2(g, g), E2 = pk2(e, e), Q2 = pk2(q, q), C2 = pk2(c, c);
     // local alignment: biased fields (see P16_BIAS); "x + K" for a penalty K <= 0 is then x - |K| * 0x10001 in 32 bits
     constexpr int BIAS = SW ? P16_BIAS : 0, FLOORV = SW ? P16_FLOOR : NEGP;
+    // the local classes compiled for the default scores take three-way maxima of their biased fields as ONE binary16
+    // instruction (pk_max3): the fields stay inside the patterns whose binary16 order is the integer order (poa_fields.h)
+    constexpr bool MAX3 = SW && DS && CVX;
+    static_assert(!MAX3 || p16_fields_are_f16_ordered(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, W), "biased fields leave the ordered binary16 patterns");
     const int NEG2 = pk2(FLOORV, FLOORV), B2 = pk2(BIAS, BIAS), NWF2 = pk2(P16_NWFLOOR, P16_NWFLOOR);
     const unsigned Gm = (unsigned)(-g) * 0x10001u, Em = (unsigned)(-e) * 0x10001u, Qm = (unsigned)(-q) * 0x10001u, Cm = (unsigned)(-c) * 0x10001u;
 #define P16_DEC(x, Km, K2) (SW ? (int)((unsigned)(x) - (Km)) : pk_add((x), (K2)))   /* x + K */

@@ -28,8 +28,12 @@
             if ((k & 1) || k == W - 1) sc4 = __builtin_amdgcn_perm(SC_T1, SC_T0, let[k >> 1]);
             const int sc = (int)__builtin_amdgcn_perm(0u, (k & 1) ? (sc4 << 8) : sc4, 0x09030801u);
             int h = pk_add(k ? Hp[k - 1] : Hleft, sc);    // diagonal + (match ? m : n)
-            h = pk_max(h, Fp[k]);
-            if (CVX) h = pk_max(h, Op[k]);
+            // (MAX3: the three-way maximum of biased fields in one instruction -- pk_max3, poa_fields.h)
+            if constexpr (MAX3) h = pk_max3(h, Fp[k], Op[k]);
+            else {
+                h = pk_max(h, Fp[k]);
+                if (CVX) h = pk_max(h, Op[k]);
+            }
             Hc[k] = h;
             // a = max_k' (h_k' - (k'-k) e) over the columns k' >= k done so far: "the gap is e longer, or restarts here";
             // shifted by (W-1) e below it is max_k (h_k + (W-1-k) e), the carry the strip hands on.  The opening cost
@@ -88,8 +92,12 @@
 #pragma unroll
         for (int k = 0; k < W; ++k) {
             if (EXP & 64) { rowmax = pk_max(rowmax, Hc[k] ^ E ^ Q); continue; }
-            int h = pk_max(Hc[k], E);
-            if (CVX) h = pk_max(h, Q);
+            int h;
+            if constexpr (MAX3) h = pk_max3(Hc[k], E, Q);
+            else {
+                h = pk_max(Hc[k], E);
+                if (CVX) h = pk_max(h, Q);
+            }
             h = pk_max(h, SW ? B2 : NWF2);   // (local: 0; global: P16_NWFLOOR)
             Hc[k] = h;
             if constexpr (W >= 12 || !SW) rowmax = pk_max(rowmax, h);
@@ -108,10 +116,21 @@
                 int t_[W];
 #pragma unroll
                 for (int k = 0; k < W; ++k) t_[k] = Hc[k];
+                if constexpr (MAX3) {
+                    // three-input nodes: 5 instead of 9 instructions at W = 10 (a node writes t_[k] after reading t_[3 k ..])
+#pragma unroll
+                    for (int n = W; n > 1; n = n / 3 + (n % 3 ? 1 : 0)) {
+#pragma unroll
+                        for (int k = 0; k < n / 3; ++k) t_[k] = pk_max3(t_[3 * k], t_[3 * k + 1], t_[3 * k + 2]);
+                        if (n % 3 == 1) t_[n / 3] = t_[n - 1];
+                        if (n % 3 == 2) t_[n / 3] = pk_max(t_[n - 2], t_[n - 1]);
+                    }
+                } else {
 #pragma unroll
                 for (int n = W; n > 1; n = (n + 1) / 2)
 #pragma unroll
                     for (int k = 0; k < n / 2; ++k) t_[k] = pk_max(t_[k], t_[n - 1 - k]);
+                }
                 rowmax = t_[0];
             }
         }

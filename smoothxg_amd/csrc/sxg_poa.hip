@@ -190,7 +190,7 @@ static bool p16_safe(const Scoring& S, int maxlen, int rows, bool clamp_ok = fal
     // stored rows keep H - max(H+g, F+e) and H - max(H+q, O+c) in one byte each
     if (std::abs(S.g) > 120 || std::abs(S.q) > 120) return false;
     // local alignment: every existing cell has 0 <= H <= m * L and F, O, E, Q >= -|q|; the range is one-sided
-    if (S.sw) return (long)std::abs(S.m) * maxlen < 30000;
+    if (S.sw) return (long)std::abs(S.m) * maxlen < P16_LOCAL_LIMIT;
     if ((long)std::abs(S.m) * maxlen >= 15800) return false;
     // (the walk may dip to -16 000 + m L + m before it is called clamped: 1 500 below zero at the limit -- a global alignment of
     //  related sequences stays far above; one that does not is re-run on the 32-bit sweep while that sweep reaches it, 12 287 letters)
