@@ -25,6 +25,7 @@
 #include "poa_kernels.hip.h"       // slot layout, launch arguments, the persistent kernels (device side)
 #include "poa_cost.h"              // a block's cost in its launch (rows x swept columns), the deal over CUs
 #include "poa_deal.h"              // the deal of a batch over the members of a device group (contiguous cuts of the cost)
+#include "poa_results.h"           // the table of the result arrays, the reassembly of a batch's result from its parts, the full MSA
 #include "poa_kern_tables.hip.h"   // kernel classes by geometry; instantiated in the kern_*.hip translation units
 #include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
@@ -1466,52 +1467,138 @@ static void* host_big_alloc(size_t bytes) {
     madvise(q, bytes, MADV_HUGEPAGE);
     return q;
 }
-template <class T> struct host_noinit_alloc : std::allocator<T> {
-    template <class U> struct rebind { typedef host_noinit_alloc<U> other; };
-    T* allocate(size_t n) {
-        void* q = host_big_alloc(n * sizeof(T));
-        if (!q) throw std::bad_alloc();
-        return (T*)q;
-    }
-    void deallocate(T* q, size_t) noexcept { free(q); }
-    template <class U> void construct(U* q) noexcept { ::new ((void*)q) U; }
-    template <class U, class... A> void construct(U* q, A&&... a) { ::new ((void*)q) U(std::forward<A>(a)...); }
-};
-template <class T> using hvec = std::vector<T, host_noinit_alloc<T>>;
+// What a result owns: its arrays (every one from host_big_alloc) and, when the step lists went into a borrowed pinned buffer,
+// that buffer and the pool it goes back to.
 struct OutOwner {
     std::shared_ptr<PinPool> pin_pool;
-    int32_t* bg_steps_pinned = nullptr;   // the step lists when they were downloaded into a borrowed pinned buffer
-    std::vector<int32_t> status, score, msa_cols;
-    hvec<int32_t> node_rank, node_group, edge_tail, edge_head, cons_nodes;
-    int32_t* seq_path_nodes = nullptr;   // one node id per base: the big one (1.3 GB on the headline batch), never zero-filled
-    std::vector<void*> raw;              // arrays of a device group's reassembled result (host_big_alloc)
-    ~OutOwner() { free(seq_path_nodes); if (bg_steps_pinned && pin_pool) pin_pool->release(bg_steps_pinned); for (void* q : raw) free(q); }
-    std::vector<int64_t> node_off, edge_off, cons_off, msa_off;
-    hvec<uint8_t> node_code;
-    hvec<uint32_t> edge_weight;
-    std::vector<uint64_t> cells, block_cycles;
-    std::vector<char> msa;
-    // block graphs
-    std::vector<int64_t> bg_node_off, bg_seq_off, bg_edge_off, bg_step_off, bg_cons_off;
-    hvec<int32_t> bg_node_len, bg_node_outdeg, bg_edge_to, bg_steps, bg_cons_steps;
-    hvec<uint8_t> bg_node_indeg, bg_seq;
-    hvec<uint8_t> msa_rows;   // the trimmed MSA, copied as the device wrote it
+    void* pinned = nullptr;
+    std::vector<void*> raw;
+    ~OutOwner() { if (pinned && pin_pool) pin_pool->release(pinned); for (void* q : raw) free(q); }
+    void* alloc(size_t bytes) {
+        void* q = host_big_alloc(bytes);
+        if (q) raw.push_back(q);
+        return q;
+    }
 };
 
-template <class Tv>
-static int gather_download(sxg_poa_handle* h, const DevBuf& src, const std::vector<int64_t>& dst_off, DevBuf& d_srcoff,
-                           DevBuf& d_dstoff, DevBuf& d_dense, hvec<Tv>& out) {
+// Where the arrays of the result table (poa_results.h) live on the device after an execute, entry for entry beside
+// sxg::RESULT_FAMILIES / RESULT_FLAT: the handle's buffer, the per-block offsets its entries start at there (SRC_DENSE: the
+// buffer already is the dense array), and when the array is part of the result.
+enum { SRC_DENSE, SRC_BASE /* the block's first base: the worst-case layout of the raw graphs */, SRC_NODE, SRC_EDGE /* bg_node_o, bg_edge_o */, SRC_N };
+enum { WHEN_ALWAYS, WHEN_GRAPHS, WHEN_CONS, WHEN_GRAPHS_CONS, WHEN_PATHS, WHEN_BG, WHEN_BG_CONS, WHEN_MSA_ROWS };
+struct DevSource { DevBuf sxg_poa_handle::*buf; int src, when; };
+struct FamilySource { int when; DevSource pay[3]; };
+static const FamilySource FAMILY_SRC[] = {
+    /* node_off    */ {WHEN_ALWAYS, {{&sxg_poa_handle::d_node_code, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_node_rank, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_node_group, SRC_BASE, WHEN_GRAPHS}}},
+    /* edge_off    */ {WHEN_ALWAYS, {{&sxg_poa_handle::d_edge_tail, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_edge_head, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_edge_w, SRC_BASE, WHEN_GRAPHS}}},
+    /* cons_off    */ {WHEN_CONS, {{&sxg_poa_handle::d_cons, SRC_BASE, WHEN_GRAPHS_CONS}}},
+    /* msa_off     */ {WHEN_MSA_ROWS, {{&sxg_poa_handle::d_msa, SRC_DENSE, WHEN_MSA_ROWS}}},   // (the trimmed MSA; the full one is formatted on the host)
+    /* bg_node_off */ {WHEN_BG, {{&sxg_poa_handle::d_bg_len, SRC_NODE, WHEN_BG}, {&sxg_poa_handle::d_bg_od, SRC_NODE, WHEN_BG}, {&sxg_poa_handle::d_bg_id, SRC_NODE, WHEN_BG}}},
+    /* bg_seq_off  */ {WHEN_BG, {{&sxg_poa_handle::d_bg_seq, SRC_NODE, WHEN_BG}}},
+    /* bg_edge_off */ {WHEN_BG, {{&sxg_poa_handle::d_bg_eto, SRC_EDGE, WHEN_BG}}},
+    /* bg_step_off */ {WHEN_BG, {{&sxg_poa_handle::d_bg_steps, SRC_BASE, WHEN_BG}}},
+    /* bg_cons_off */ {WHEN_BG_CONS, {{&sxg_poa_handle::d_bg_cons, SRC_NODE, WHEN_BG_CONS}}},
+};
+static const DevSource FLAT_SRC[] = {
+    {&sxg_poa_handle::d_status, SRC_DENSE, WHEN_ALWAYS}, {nullptr /* msa_cols_h, on the host */, SRC_DENSE, WHEN_MSA_ROWS}, {&sxg_poa_handle::d_blk_cycles, SRC_DENSE, WHEN_ALWAYS},
+    {&sxg_poa_handle::d_score, SRC_DENSE, WHEN_ALWAYS}, {&sxg_poa_handle::d_cells, SRC_DENSE, WHEN_ALWAYS}, {&sxg_poa_handle::d_paths, SRC_DENSE, WHEN_PATHS},
+};
+static_assert(sizeof(FAMILY_SRC) / sizeof(FAMILY_SRC[0]) == sxg::N_RESULT_FAMILIES && sizeof(FLAT_SRC) / sizeof(FLAT_SRC[0]) == sxg::N_RESULT_FLAT,
+              "one device source per entry of the result table");
+static bool present(const sxg_poa_handle* h, int when) {
+    const bool bg = h->want_block_graph && h->bg_done;
+    const bool graphs = !(h->want_block_graph == 3 && h->bg_done);   // (3: the caller laces block graphs and reads nothing else)
+    switch (when) {
+    case WHEN_GRAPHS: return graphs;
+    case WHEN_CONS: return h->want_consensus != 0;
+    case WHEN_GRAPHS_CONS: return graphs && h->want_consensus;
+    case WHEN_PATHS: return !(h->want_block_graph >= 2 && h->bg_done);
+    case WHEN_BG: return bg;
+    case WHEN_BG_CONS: return bg && h->want_consensus;
+    case WHEN_MSA_ROWS: return h->want_msa == SXG_MSA_TRIMMED;
+    default: return true;
+    }
+}
+
+// The dense layout of the executed batch: the offsets of every family the run produced (the others stay empty) and, per block,
+// where its entries start in the device buffers.  From the per-block counts of the POA kernels and of the block-graph kernel.
+struct DenseLayout {
+    std::vector<int64_t> off[sxg::N_RESULT_FAMILIES];
+    std::vector<int64_t> src[SRC_N];
+    std::vector<int64_t> step_blocks;   // bg_step_off at every block's first sequence: what a gather of the step lists runs over
+    int resident = SRC_DENSE;           // which of src[] the device copy of the source offsets (d_tmp_a) holds: none yet
+    const std::vector<int64_t>& per_block(int a) const { return sxg::RESULT_FAMILIES[a].per_seq ? step_blocks : off[a]; }
+};
+static int dense_layout(sxg_poa_handle* h, DenseLayout& D) {
     const int nb = h->n_blocks;
-    const int64_t total = dst_off[nb];
-    out.resize((size_t)std::max<int64_t>(total, 1));
-    if (total == 0) return SXG_OK;
-    int rc;
-    if ((rc = d_dense.ensure(sizeof(Tv) * (size_t)total))) return rc;
-    hipLaunchKernelGGL((gather_kernel<Tv>), dim3((unsigned)std::min(nb, 4096)), dim3(256), 0, h->stream, src.as<Tv>(),
-                       d_dense.as<Tv>(), d_srcoff.as<int64_t>(), d_dstoff.as<int64_t>(), nb);
+    const int64_t ns = h->n_seqs;
+    if (h->want_msa == SXG_MSA_TRIMMED && !h->msa_done) return fail(SXG_E_INVALID, "the trimmed MSA of this batch was not built");
+    std::vector<int32_t> status(std::max(nb, 1)), nn(std::max(nb, 1)), ne(std::max(nb, 1)), nc(std::max(nb, 1));
+    if (nb) {
+        HIPCHK(hipMemcpy(status.data(), h->d_status.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nn.data(), h->d_nn.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(ne.data(), h->d_ne.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nc.data(), h->d_nc.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+    }
+    for (int a = 0; a < sxg::N_RESULT_FAMILIES; ++a)
+        if (present(h, FAMILY_SRC[a].when)) D.off[a].assign((size_t)(sxg::RESULT_FAMILIES[a].per_seq ? ns : (int64_t)nb) + 1, 0);
+    for (auto& s : D.src) s.assign((size_t)nb + 1, 0);
+    const bool cons = present(h, WHEN_CONS), bg = present(h, WHEN_BG);
+    if (bg) {
+        std::vector<int32_t> nsteps((size_t)std::max<int64_t>(ns, 1), 0);
+        if (ns) HIPCHK(hipMemcpy(nsteps.data(), h->d_bg_nsteps.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
+        for (int64_t sq = 0; sq < ns; ++sq) D.off[sxg::RF_BG_STEP][(size_t)sq + 1] = D.off[sxg::RF_BG_STEP][(size_t)sq] + nsteps[(size_t)sq];
+        D.step_blocks.assign((size_t)nb + 1, 0);
+    }
+    for (int b = 0; b < nb; ++b) {
+        D.off[sxg::RF_NODE][b + 1] = D.off[sxg::RF_NODE][b] + nn[b];
+        D.off[sxg::RF_EDGE][b + 1] = D.off[sxg::RF_EDGE][b] + ne[b];
+        if (cons) D.off[sxg::RF_CONS][b + 1] = D.off[sxg::RF_CONS][b] + nc[b];
+        D.src[SRC_BASE][b] = h->h_seq_off[h->h_blk_off[b]];
+        if (!bg) continue;
+        const int32_t* c = h->bg_counts.data() + (size_t)BGC_N * b;
+        const bool ok = status[b] == ST_OK;
+        D.off[sxg::RF_BG_NODE][b + 1] = D.off[sxg::RF_BG_NODE][b] + (ok ? c[BGC_NODES] : 0);
+        D.off[sxg::RF_BG_SEQ][b + 1] = D.off[sxg::RF_BG_SEQ][b] + (ok ? c[BGC_SEQ] : 0);
+        D.off[sxg::RF_BG_EDGE][b + 1] = D.off[sxg::RF_BG_EDGE][b] + (ok ? c[BGC_EDGES] : 0);
+        if (cons) D.off[sxg::RF_BG_CONS][b + 1] = D.off[sxg::RF_BG_CONS][b] + (ok ? c[BGC_CONS] : 0);
+        D.step_blocks[b + 1] = D.off[sxg::RF_BG_STEP][(size_t)h->h_blk_off[b + 1]];
+        D.src[SRC_NODE][b] = h->bg_node_o[(size_t)b]; D.src[SRC_EDGE][b] = h->bg_edge_o[(size_t)b];
+    }
+    if (present(h, WHEN_MSA_ROWS)) {
+        if (h->msa_off_h.size() != (size_t)nb + 1) return fail(SXG_E_INVALID, "the trimmed MSA's offsets do not match the batch");
+        D.off[sxg::RF_MSA] = h->msa_off_h;
+    }
+    int rc;   // (the two offset vectors of a gather)
+    if ((rc = h->d_tmp_a.ensure(8 * (size_t)(nb + 1))) || (rc = h->d_tmp_b.ensure(8 * (size_t)(nb + 1)))) return rc;
+    return SXG_OK;
+}
+
+// One gather launch on the handle's stream (not waited for), for a payload of family a whose entries start at D.src[kind] in
+// src: dst[dst_off[b] ..) = src[src_off[b] ..) for every block, `elem` bytes per entry, dst_off[b + 1] - dst_off[b] entries.
+// Both ranges are checked against the buffers first: a mistake in the tables above comes back as a return code, not as a
+// fault of the device.  The source offsets are uploaded when they change, the destination offsets every time.
+static int gather(sxg_poa_handle* h, DenseLayout& D, int kind, int a, const DevBuf& src, size_t elem, void* dst, size_t dst_bytes) {
+    const int nb = h->n_blocks;
+    const std::vector<int64_t>&src_off = D.src[kind], &dst_off = D.per_block(a);
+    if (src_off.size() != (size_t)nb + 1 || dst_off.size() != (size_t)nb + 1 || (elem != 1 && elem != 4) || !dst || !src.p || dst_off[0] != 0 ||
+        (uint64_t)dst_off[nb] > dst_bytes / elem)
+        return fail(SXG_E_INVALID, "gather: the dense array does not fit its buffer");
+    for (int b = 0; b < nb; ++b) {
+        const int64_t cnt = dst_off[b + 1] - dst_off[b];
+        if (cnt < 0 || (cnt > 0 && (src_off[b] < 0 || (uint64_t)(src_off[b] + cnt) > src.cap / elem)))
+            return fail(SXG_E_INVALID, "gather: block " + std::to_string(b) + " reads outside its device buffer");
+    }
+    if (nb == 0 || dst_off[nb] == 0) return SXG_OK;
+    if (D.resident != kind) HIPCHK(hipMemcpy(h->d_tmp_a.p, src_off.data(), 8 * (size_t)(nb + 1), hipMemcpyHostToDevice));
+    D.resident = kind;
+    HIPCHK(hipMemcpy(h->d_tmp_b.p, dst_off.data(), 8 * (size_t)(nb + 1), hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)std::min(nb, 4096)), block(256);
+    if (elem == 1)
+        hipLaunchKernelGGL((gather_kernel<uint8_t>), grid, block, 0, h->stream, src.as<uint8_t>(), (uint8_t*)dst, h->d_tmp_a.as<int64_t>(), h->d_tmp_b.as<int64_t>(), nb);
+    else
+        hipLaunchKernelGGL((gather_kernel<uint32_t>), grid, block, 0, h->stream, src.as<uint32_t>(), (uint32_t*)dst, h->d_tmp_a.as<int64_t>(), h->d_tmp_b.as<int64_t>(), nb);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out.data(), d_dense.p, sizeof(Tv) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
     return SXG_OK;
 }
 
@@ -1523,184 +1610,65 @@ extern "C" int sxg_poa_batch_download(sxg_poa_handle* h, sxg_poa_batch_out* out)
     const RoctxRange range_("sxg_poa_batch_download");
     HostLaps laps;
     const int nb = h->n_blocks;
-    const int64_t ns = h->n_seqs;
     OutOwner* o = new OutOwner();
     out->_owner = o;
-    out->n_blocks = nb; out->n_seqs = ns;
-    o->status.resize(std::max(nb, 1));
-    std::vector<int32_t> nn(std::max(nb, 1)), ne(std::max(nb, 1)), nc(std::max(nb, 1));
-    if (nb) {
-        HIPCHK(hipMemcpy(o->status.data(), h->d_status.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(nn.data(), h->d_nn.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ne.data(), h->d_ne.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(nc.data(), h->d_nc.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-    }
-    o->node_off.assign(nb + 1, 0); o->edge_off.assign(nb + 1, 0); o->cons_off.assign(nb + 1, 0);
-    std::vector<int64_t> src_off(nb + 1, 0);
-    for (int b = 0; b < nb; ++b) {
-        o->node_off[b + 1] = o->node_off[b] + nn[b];
-        o->edge_off[b + 1] = o->edge_off[b] + ne[b];
-        o->cons_off[b + 1] = o->cons_off[b] + nc[b];
-        src_off[b] = h->h_seq_off[h->h_blk_off[b]];
-    }
-    int rc;
-    if ((rc = h->d_tmp_a.ensure(8 * (size_t)(nb + 1))) || (rc = h->d_tmp_b.ensure(8 * (size_t)(nb + 1)))) { sxg_poa_batch_free(out); return rc; }
-    HIPCHK(hipMemcpy(h->d_tmp_a.p, src_off.data(), 8 * (size_t)(nb + 1), hipMemcpyHostToDevice));
-    auto put_off = [&](const std::vector<int64_t>& off) -> int {
-        hipError_t e = hipMemcpy(h->d_tmp_b.p, off.data(), 8 * (size_t)(nb + 1), hipMemcpyHostToDevice);
-        return e == hipSuccess ? SXG_OK : fail(SXG_E_NODEVICE, hipGetErrorString(e));
-    };
-#define GD(T, src, off, dst)                                                                         \
-    if ((rc = put_off(off)) || (rc = gather_download<T>(h, src, off, h->d_tmp_a, h->d_tmp_b, h->d_tmp_c, dst))) { \
-        sxg_poa_batch_free(out);                                                                     \
-        return rc;                                                                                   \
-    }
-    const bool with_graphs = !(h->want_block_graph == 3 && h->bg_done);   // (3: the caller laces block graphs and reads nothing else)
-    if (with_graphs) {
-    GD(uint8_t, h->d_node_code, o->node_off, o->node_code)
-    GD(int32_t, h->d_node_rank, o->node_off, o->node_rank)
-    GD(int32_t, h->d_node_group, o->node_off, o->node_group)
-    GD(int32_t, h->d_edge_tail, o->edge_off, o->edge_tail)
-    GD(int32_t, h->d_edge_head, o->edge_off, o->edge_head)
-    GD(uint32_t, h->d_edge_w, o->edge_off, o->edge_weight)
-    if (h->want_consensus) { GD(int32_t, h->d_cons, o->cons_off, o->cons_nodes) }
-    }
-#undef GD
-    laps.lap("download: POA graphs");
-    const bool with_paths = !(h->want_block_graph >= 2 && h->bg_done);
-    if (with_paths) {
-        o->seq_path_nodes = (int32_t*)host_big_alloc(4 * (size_t)std::max<int64_t>(h->n_bases, 1));
-        if (!o->seq_path_nodes) { sxg_poa_batch_free(out); return fail(SXG_E_NOMEM, "host allocation of the path array failed"); }
-        if (h->n_bases) HIPCHK(hipMemcpy(o->seq_path_nodes, h->d_paths.p, 4 * (size_t)h->n_bases, hipMemcpyDeviceToHost));
-    }
-    o->score.resize((size_t)std::max<int64_t>(ns, 1));
-    o->cells.resize((size_t)std::max<int64_t>(ns, 1));
-    laps.lap("download: paths");
-    if (h->want_block_graph && h->bg_done) {
-        // dense offsets from the per-block counts of the block-graph kernel; the arrays are gathered on the device
-        o->bg_node_off.assign(nb + 1, 0); o->bg_seq_off.assign(nb + 1, 0); o->bg_edge_off.assign(nb + 1, 0); o->bg_cons_off.assign(nb + 1, 0);
-        std::vector<int64_t> blk_steps(nb + 1, 0), src_no(nb + 1, 0), src_eo(nb + 1, 0);
-        std::vector<int32_t> nsteps((size_t)std::max<int64_t>(ns, 1), 0);
-        if (ns) HIPCHK(hipMemcpy(nsteps.data(), h->d_bg_nsteps.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
-        o->bg_step_off.assign((size_t)ns + 1, 0);
-        for (int64_t sq = 0; sq < ns; ++sq) o->bg_step_off[(size_t)sq + 1] = o->bg_step_off[(size_t)sq] + nsteps[(size_t)sq];
-        for (int b = 0; b < nb; ++b) {
-            const int32_t* c = h->bg_counts.data() + (size_t)BGC_N * b;
-            const bool ok = o->status[b] == ST_OK;
-            o->bg_node_off[b + 1] = o->bg_node_off[b] + (ok ? c[BGC_NODES] : 0);
-            o->bg_seq_off[b + 1] = o->bg_seq_off[b] + (ok ? c[BGC_SEQ] : 0);
-            o->bg_edge_off[b + 1] = o->bg_edge_off[b] + (ok ? c[BGC_EDGES] : 0);
-            o->bg_cons_off[b + 1] = o->bg_cons_off[b] + (ok && h->want_consensus ? c[BGC_CONS] : 0);
-            blk_steps[b + 1] = o->bg_step_off[(size_t)h->h_blk_off[b + 1]];
-            src_no[b] = h->bg_node_o[(size_t)b]; src_eo[b] = h->bg_edge_o[(size_t)b];
-        }
-        auto put_src = [&](const std::vector<int64_t>& off) -> int {
-            hipError_t e = hipMemcpy(h->d_tmp_a.p, off.data(), 8 * (size_t)(nb + 1), hipMemcpyHostToDevice);
-            return e == hipSuccess ? SXG_OK : fail(SXG_E_NODEVICE, hipGetErrorString(e));
-        };
-#define GB_(T, srcoff, src, off, dst)                                                                                      \
-        if ((rc = put_src(srcoff)) || (rc = put_off(off)) || (rc = gather_download<T>(h, src, off, h->d_tmp_a, h->d_tmp_b, h->d_tmp_c, dst))) { \
-            sxg_poa_batch_free(out);                                                                                       \
-            return rc;                                                                                                     \
-        }
-        GB_(int32_t, src_no, h->d_bg_len, o->bg_node_off, o->bg_node_len)
-        GB_(int32_t, src_no, h->d_bg_od, o->bg_node_off, o->bg_node_outdeg)
-        GB_(uint8_t, src_no, h->d_bg_id, o->bg_node_off, o->bg_node_indeg)
-        GB_(uint8_t, src_no, h->d_bg_seq, o->bg_seq_off, o->bg_seq)
-        GB_(int32_t, src_eo, h->d_bg_eto, o->bg_edge_off, o->bg_edge_to)
-        {   // the step lists: into a borrowed pinned buffer when the pool has one (see PinPool)
-            const int64_t total = blk_steps[nb];
-            if (h->pin_thread.joinable()) h->pin_thread.join();
-            if (total >= ((int64_t)16 << 20) && h->pins && !getenv("SXG_POA_NO_PINNED")) {
-                if (void* q = h->pins->acquire(4 * (size_t)total)) { o->pin_pool = h->pins; o->bg_steps_pinned = (int32_t*)q; }
+    out->n_blocks = nb; out->n_seqs = h->n_seqs;
+    auto bail = [&](int code) { sxg_poa_batch_free(out); return code; };
+    auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? SXG_OK : fail(SXG_E_NODEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
+    DenseLayout D;
+    int rc = dense_layout(h, D);
+    if (rc) return bail(rc);
+    for (int a = 0; a < sxg::N_RESULT_FAMILIES; ++a) {
+        const sxg::ResultFamily& A = sxg::RESULT_FAMILIES[a];
+        if (a == sxg::RF_MSA) laps.lap("download: POA graphs");
+        if (a == sxg::RF_BG_NODE) laps.lap("download: MSA rows");
+        if (!present(h, FAMILY_SRC[a].when)) continue;
+        int64_t* off = (int64_t*)o->alloc(8 * D.off[a].size());
+        if (!off) return bail(fail(SXG_E_NOMEM, "host allocation of the result failed"));
+        memcpy(off, D.off[a].data(), 8 * D.off[a].size());
+        sxg::set_field(*out, A.off_field, off);
+        const size_t total = (size_t)D.off[a].back();
+        for (int p = 0; p < 3; ++p) {
+            const DevSource& S = FAMILY_SRC[a].pay[p];
+            const size_t elem = A.pay[p].elem;
+            if (!elem || !present(h, S.when)) continue;
+            void* dst = nullptr;
+            if (A.pay[p].field == offsetof(sxg_poa_batch_out, bg_steps)) {   // the step lists: into a borrowed pinned buffer when the pool has one (see PinPool)
+                if (h->pin_thread.joinable()) h->pin_thread.join();
+                if (total >= ((size_t)16 << 20) && h->pins && !getenv("SXG_POA_NO_PINNED") && (dst = h->pins->acquire(elem * total))) { o->pin_pool = h->pins; o->pinned = dst; }
             }
-            if (o->bg_steps_pinned) {
-                if ((rc = put_src(src_off)) || (rc = put_off(blk_steps)) || (rc = h->d_tmp_c.ensure(4 * (size_t)total))) { sxg_poa_batch_free(out); return rc; }
-                hipLaunchKernelGGL((gather_kernel<int32_t>), dim3((unsigned)std::min(nb, 4096)), dim3(256), 0, h->stream, h->d_bg_steps.as<int32_t>(),
-                                   h->d_tmp_c.as<int32_t>(), h->d_tmp_a.as<int64_t>(), h->d_tmp_b.as<int64_t>(), nb);
-                hipError_t e = hipGetLastError();
-                if (e == hipSuccess) e = hipMemcpyAsync(o->bg_steps_pinned, h->d_tmp_c.p, 4 * (size_t)total, hipMemcpyDeviceToHost, h->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-                if (e != hipSuccess) { sxg_poa_batch_free(out); return fail(SXG_E_NODEVICE, std::string("download of the step lists: ") + hipGetErrorString(e)); }
-            } else {
-                GB_(int32_t, src_off, h->d_bg_steps, blk_steps, o->bg_steps)
+            if (!dst && !(dst = o->alloc(elem * total))) return bail(fail(SXG_E_NOMEM, "host allocation of the result failed"));
+            sxg::set_field(*out, A.pay[p].field, dst);
+            if (!total) continue;
+            const DevBuf& src = h->*S.buf;
+            if (S.src == SRC_DENSE) {   // (the rows of the trimmed MSA, as the device wrote them)
+                if ((rc = hip(hipMemcpy(dst, src.p, elem * total, hipMemcpyDeviceToHost), "download of the MSA rows"))) return bail(rc);
+                continue;
             }
+            if ((rc = h->d_tmp_c.ensure(elem * total)) || (rc = gather(h, D, S.src, a, src, elem, h->d_tmp_c.p, h->d_tmp_c.cap)) ||
+                (rc = hip(hipMemcpyAsync(dst, h->d_tmp_c.p, elem * total, hipMemcpyDeviceToHost, h->stream), "download of a gathered array")) ||
+                (rc = hip(hipStreamSynchronize(h->stream), "download of a gathered array")))
+                return bail(rc);
         }
-        if (h->want_consensus) { GB_(int32_t, src_no, h->d_bg_cons, o->bg_cons_off, o->bg_cons_steps) }
-#undef GB_
-        out->bg_node_off = o->bg_node_off.data(); out->bg_node_len = o->bg_node_len.data(); out->bg_node_outdeg = o->bg_node_outdeg.data();
-        out->bg_node_indeg = o->bg_node_indeg.data(); out->bg_seq_off = o->bg_seq_off.data(); out->bg_seq = (char*)o->bg_seq.data();
-        out->bg_edge_off = o->bg_edge_off.data(); out->bg_edge_to = o->bg_edge_to.data(); out->bg_step_off = o->bg_step_off.data();
-        out->bg_steps = o->bg_steps_pinned ? o->bg_steps_pinned : o->bg_steps.data();
-        if (h->want_consensus) { out->bg_cons_off = o->bg_cons_off.data(); out->bg_cons_steps = o->bg_cons_steps.data(); }
-        laps.lap("download: block graphs");
     }
-    o->block_cycles.assign((size_t)std::max(nb, 1), 0);
-    if (nb) HIPCHK(hipMemcpy(o->block_cycles.data(), h->d_blk_cycles.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
-    out->block_cycles = o->block_cycles.data();
-    if (ns) {
-        HIPCHK(hipMemcpy(o->score.data(), h->d_score.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(o->cells.data(), h->d_cells.p, 8 * (size_t)ns, hipMemcpyDeviceToHost));
+    laps.lap("download: block graphs");
+    for (int f = 0; f < sxg::N_RESULT_FLAT; ++f) {
+        const sxg::ResultFlat& F = sxg::RESULT_FLAT[f];
+        if (!present(h, FLAT_SRC[f].when)) continue;
+        const size_t bytes = F.elem * (size_t)(F.index == 0 ? nb : F.index == 1 ? h->n_seqs : h->n_bases);
+        void* dst = o->alloc(bytes);   // (seq_path_nodes, one node id per base, is the big one: 1.3 GB on the headline batch, one straight copy)
+        if (!dst) return bail(fail(SXG_E_NOMEM, "host allocation of the result failed"));
+        sxg::set_field(*out, F.field, dst);
+        if (!bytes) continue;
+        if (!FLAT_SRC[f].buf) memcpy(dst, h->msa_cols_h.data(), std::min(bytes, 4 * h->msa_cols_h.size()));
+        else if ((rc = hip(hipMemcpy(dst, (h->*FLAT_SRC[f].buf).p, bytes, hipMemcpyDeviceToHost), "download of a flat array"))) return bail(rc);
     }
-    out->status = o->status.data();
-    out->node_off = o->node_off.data(); out->edge_off = o->edge_off.data();
-    if (with_graphs) {
-        out->node_code = o->node_code.data(); out->node_rank = o->node_rank.data(); out->node_group = o->node_group.data();
-        out->edge_tail = o->edge_tail.data(); out->edge_head = o->edge_head.data(); out->edge_weight = o->edge_weight.data();
-    }
-    out->seq_path_nodes = o->seq_path_nodes; out->score = o->score.data(); out->cells = o->cells.data();
-    if (h->want_consensus) { out->cons_off = o->cons_off.data(); if (with_graphs) out->cons_nodes = o->cons_nodes.data(); }
-    if (h->want_msa == SXG_MSA_TRIMMED) {
-        if (!h->msa_done) { sxg_poa_batch_free(out); return fail(SXG_E_INVALID, "the trimmed MSA of this batch was not built"); }
-        o->msa_off = h->msa_off_h; o->msa_cols = h->msa_cols_h;
-        const int64_t total = o->msa_off[nb];
-        o->msa_rows.resize((size_t)std::max<int64_t>(total, 1));
-        if (total) {
-            const hipError_t e = hipMemcpy(o->msa_rows.data(), h->d_msa.p, (size_t)total, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { sxg_poa_batch_free(out); return fail(SXG_E_NODEVICE, std::string("download of the MSA rows: ") + hipGetErrorString(e)); }
-        }
-        out->msa_off = o->msa_off.data(); out->msa_cols = o->msa_cols.data(); out->msa = (char*)o->msa_rows.data();
-        laps.lap("download: MSA rows");
-    } else if (h->want_msa && o->seq_path_nodes) {
-        // S8: MSA column = aligned group in rank order; pure formatting of device results
-        static const char dec[5] = {'A', 'C', 'G', 'T', 'N'};
-        o->msa_off.assign(nb + 1, 0); o->msa_cols.assign(std::max(nb, 1), 0);
-        std::vector<std::vector<int32_t>> cols(nb);
-        for (int b = 0; b < nb; ++b) {
-            const int64_t n0 = o->node_off[b];
-            const int n = nn[b];
-            std::vector<int32_t> by_rank(n);
-            for (int v = 0; v < n; ++v) by_rank[o->node_rank[n0 + v]] = v;
-            cols[b].assign(n, 0);
-            int ncol = 0;
-            for (int r = 0; r < n; ++r) {
-                const int v = by_rank[r];
-                if (r > 0 && o->node_group[n0 + by_rank[r - 1]] == o->node_group[n0 + v]) cols[b][v] = ncol - 1;
-                else cols[b][v] = ncol++;
-            }
-            o->msa_cols[b] = ncol;
-            const int rows = (h->h_blk_off[b + 1] - h->h_blk_off[b]) + (h->want_consensus ? 1 : 0);
-            o->msa_off[b + 1] = o->msa_off[b] + (o->status[b] == ST_OK ? (int64_t)rows * ncol : 0);
-        }
-        o->msa.assign((size_t)std::max<int64_t>(o->msa_off[nb], 1), '-');
-        for (int b = 0; b < nb; ++b) {
-            if (o->status[b] != ST_OK) continue;
-            const int64_t n0 = o->node_off[b];
-            const int ncol = o->msa_cols[b];
-            char* base = o->msa.data() + o->msa_off[b];
-            int row = 0;
-            for (int s = h->h_blk_off[b]; s < h->h_blk_off[b + 1]; ++s, ++row)
-                for (int64_t k = h->h_seq_off[s]; k < h->h_seq_off[s + 1]; ++k) {
-                    const int v = o->seq_path_nodes[k];
-                    base[(int64_t)row * ncol + cols[b][v]] = dec[o->node_code[n0 + v]];
-                }
-            if (h->want_consensus)
-                for (int64_t k = o->cons_off[b]; k < o->cons_off[b + 1]; ++k) {
-                    const int v = o->cons_nodes[k];
-                    base[(int64_t)row * ncol + cols[b][v]] = dec[o->node_code[n0 + v]];
-                }
-        }
-        out->msa_off = o->msa_off.data(); out->msa_cols = o->msa_cols.data(); out->msa = o->msa.data();
+    laps.lap("download: paths");   // (and the small per-block and per-sequence arrays)
+    if (h->want_msa && h->want_msa != SXG_MSA_TRIMMED && out->seq_path_nodes) {
+        const sxg::BatchShape S{nb, h->h_blk_off.data(), h->h_seq_off.data()};
+        if (!sxg::format_full_msa(S, h->want_consensus != 0, [o](size_t bytes) { return o->alloc(bytes); }, out))
+            return bail(fail(SXG_E_NOMEM, "host allocation of the MSA failed"));
+        laps.lap("download: full MSA");
     }
     return SXG_OK;
 }
@@ -1910,280 +1878,104 @@ void build_local(const sxg_poa_batch_in* in, const std::vector<int32_t>& part, L
         L.in.bg_trim = L.trims.data();
     }
 }
-// blob of one rank: eight counts, then the arrays, every section 16-byte aligned
+// The blob of one rank is its result, serialised in the order of the result table: for every array the rank's run produced
+// (bit of BC_PRESENT: 4 * family + 0 for the offsets, + 1 .. 3 for the payloads; 4 * families + f for flat array f) one
+// 16-byte-aligned section.  The count words travel ahead of it (the size all-gather) and say everything the root needs to find
+// the sections: blob_views, the one function both ends use.
 enum { BC_NB = 0, BC_NS, BC_NBASES, BC_NODES, BC_EDGES, BC_CONS, BC_BYTES, BC_PAD /* error code of the rank (0 = fine) */,
        // block graphs of the rank's blocks (want_block_graph): the owning rank builds them, the root only laces
        BC_BG /* 0 = none, 1 = with, 2 = instead of the per-base paths */, BC_BG_NODES, BC_BG_EDGES, BC_BG_SEQ, BC_BG_STEPS, BC_BG_CONS,
-       BC_RES0, BC_RES1, BC_N };
+       BC_MSA /* 0: the sharded entries refuse the trimmed MSA */, BC_PRESENT, BC_N };
 static_assert(BC_N == BC_N_WORDS, "count words");
-struct BlobLayout { size_t status, nn, ne, nc, score, cells, code, rank, group, et, eh, ew, paths, cons,
-                    bg_counts, bg_nsteps, bg_len, bg_od, bg_id, bg_seq, bg_eto, bg_steps, bg_cons, total; };
-BlobLayout blob_layout(const int64_t* c) {
-    BlobLayout B;
+const int FAMILY_TOTAL[] = {BC_NODES, BC_EDGES, BC_CONS, BC_MSA, BC_BG_NODES, BC_BG_SEQ, BC_BG_EDGES, BC_BG_STEPS, BC_BG_CONS};   // (the total of every family, by sxg::RF_*)
+static_assert(sizeof(FAMILY_TOTAL) / sizeof(FAMILY_TOTAL[0]) == sxg::N_RESULT_FAMILIES, "one total per family");
+constexpr int family_bit(int a, int slot) { return 4 * a + slot; }
+constexpr int flat_bit(int f) { return 4 * sxg::N_RESULT_FAMILIES + f; }
+// the sections of the blob that the counts c describe, as the arrays of *v (when given) at base; returns the blob's size
+size_t blob_views(const int64_t* c, uint8_t* base, sxg_poa_batch_out* v) {
     size_t cur = 0;
-    auto sec = [&](size_t bytes) { size_t o = cur; cur += (bytes + 15) & ~(size_t)15; return o; };
-    B.status = sec(4 * (size_t)c[BC_NB]); B.nn = sec(4 * (size_t)c[BC_NB]); B.ne = sec(4 * (size_t)c[BC_NB]); B.nc = sec(4 * (size_t)c[BC_NB]);
-    B.score = sec(4 * (size_t)c[BC_NS]); B.cells = sec(8 * (size_t)c[BC_NS]);
-    B.code = sec((size_t)c[BC_NODES]); B.rank = sec(4 * (size_t)c[BC_NODES]); B.group = sec(4 * (size_t)c[BC_NODES]);
-    B.et = sec(4 * (size_t)c[BC_EDGES]); B.eh = sec(4 * (size_t)c[BC_EDGES]); B.ew = sec(4 * (size_t)c[BC_EDGES]);
-    B.paths = sec(c[BC_BG] == 2 ? 0 : 4 * (size_t)c[BC_NBASES]); B.cons = sec(4 * (size_t)c[BC_CONS]);
-    const bool bg = c[BC_BG] != 0;
-    B.bg_counts = sec(bg ? 4 * (size_t)BGC_N * (size_t)c[BC_NB] : 0); B.bg_nsteps = sec(bg ? 4 * (size_t)c[BC_NS] : 0);
-    B.bg_len = sec(bg ? 4 * (size_t)c[BC_BG_NODES] : 0); B.bg_od = sec(bg ? 4 * (size_t)c[BC_BG_NODES] : 0); B.bg_id = sec(bg ? (size_t)c[BC_BG_NODES] : 0);
-    B.bg_seq = sec(bg ? (size_t)c[BC_BG_SEQ] : 0); B.bg_eto = sec(bg ? 4 * (size_t)c[BC_BG_EDGES] : 0);
-    B.bg_steps = sec(bg ? 4 * (size_t)c[BC_BG_STEPS] : 0); B.bg_cons = sec(bg ? 4 * (size_t)c[BC_BG_CONS] : 0);
-    B.total = cur;
-    return B;
+    auto sec = [&](int bit, size_t field, size_t bytes) {
+        if (!((c[BC_PRESENT] >> bit) & 1)) return;
+        if (v) sxg::set_field(*v, field, base + cur);
+        cur += (bytes + 15) & ~(size_t)15;
+    };
+    const size_t n[3] = {(size_t)c[BC_NB], (size_t)c[BC_NS], (size_t)c[BC_NBASES]};
+    for (int a = 0; a < sxg::N_RESULT_FAMILIES; ++a) {
+        const sxg::ResultFamily& A = sxg::RESULT_FAMILIES[a];
+        sec(family_bit(a, 0), A.off_field, 8 * (n[A.per_seq ? 1 : 0] + 1));
+        for (int p = 0; p < 3; ++p)
+            if (A.pay[p].elem) sec(family_bit(a, p + 1), A.pay[p].field, A.pay[p].elem * (size_t)c[FAMILY_TOTAL[a]]);
+    }
+    for (int f = 0; f < sxg::N_RESULT_FLAT; ++f) sec(flat_bit(f), sxg::RESULT_FLAT[f].field, sxg::RESULT_FLAT[f].elem * n[sxg::RESULT_FLAT[f].index]);
+    return cur;
 }
 // dense results of the handle's executed batch, packed into h->d_blob on the device
 int pack_blob(sxg_poa_handle* h, int64_t* counts) {
-    const int nb = h->n_blocks;
-    std::vector<int32_t> nn(std::max(nb, 1)), ne(std::max(nb, 1)), nc(std::max(nb, 1));
-    if (nb) {
-        HIPCHK(hipMemcpy(nn.data(), h->d_nn.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(ne.data(), h->d_ne.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(nc.data(), h->d_nc.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-    }
-    std::vector<int64_t> noff(nb + 1, 0), eoff(nb + 1, 0), coff(nb + 1, 0), soff(nb + 1, 0);
-    for (int b = 0; b < nb; ++b) {
-        noff[b + 1] = noff[b] + nn[b]; eoff[b + 1] = eoff[b] + ne[b]; coff[b + 1] = coff[b] + (h->want_consensus ? nc[b] : 0);
-        soff[b] = h->h_seq_off[h->h_blk_off[b]];
-    }
+    DenseLayout D;
+    int rc = dense_layout(h, D);
+    if (rc) return rc;
     memset(counts, 0, sizeof(int64_t) * BC_N);
-    counts[BC_NB] = nb; counts[BC_NS] = h->n_seqs; counts[BC_NBASES] = h->n_bases;
-    counts[BC_NODES] = noff[nb]; counts[BC_EDGES] = eoff[nb]; counts[BC_CONS] = coff[nb];
-    // block graphs: dense offsets from the block-graph kernel's counts (as sxg_poa_batch_download computes them)
-    const bool bg = h->want_block_graph && h->bg_done;
-    std::vector<int64_t> gno(nb + 1, 0), gso(nb + 1, 0), geo(nb + 1, 0), gco(nb + 1, 0), gpo(nb + 1, 0), src_no(nb + 1, 0), src_eo(nb + 1, 0);
-    if (bg) {
-        std::vector<int32_t> st(std::max(nb, 1)), nsteps((size_t)std::max<int64_t>(h->n_seqs, 1), 0);
-        if (nb) HIPCHK(hipMemcpy(st.data(), h->d_status.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        if (h->n_seqs) HIPCHK(hipMemcpy(nsteps.data(), h->d_bg_nsteps.p, 4 * (size_t)h->n_seqs, hipMemcpyDeviceToHost));
-        for (int b = 0; b < nb; ++b) {
-            const int32_t* c = h->bg_counts.data() + (size_t)BGC_N * b;
-            const bool ok = st[b] == ST_OK;
-            gno[b + 1] = gno[b] + (ok ? c[BGC_NODES] : 0); gso[b + 1] = gso[b] + (ok ? c[BGC_SEQ] : 0);
-            geo[b + 1] = geo[b] + (ok ? c[BGC_EDGES] : 0); gco[b + 1] = gco[b] + (ok && h->want_consensus ? c[BGC_CONS] : 0);
-            int64_t stp = 0;
-            for (int sq = h->h_blk_off[b]; sq < h->h_blk_off[b + 1]; ++sq) stp += nsteps[(size_t)sq];
-            gpo[b + 1] = gpo[b] + (ok ? stp : 0);
-            src_no[b] = h->bg_node_o[(size_t)b]; src_eo[b] = h->bg_edge_o[(size_t)b];
+    counts[BC_NB] = h->n_blocks; counts[BC_NS] = h->n_seqs; counts[BC_NBASES] = h->n_bases;
+    counts[BC_BG] = present(h, WHEN_BG) ? h->want_block_graph : 0;
+    // what travels: everything the run produced but the two arrays the root does not reassemble (the trimmed MSA, block_cycles)
+    for (int a = 0; a < sxg::N_RESULT_FAMILIES; ++a) {
+        if (a == sxg::RF_MSA || !present(h, FAMILY_SRC[a].when)) continue;
+        counts[BC_PRESENT] |= (int64_t)1 << family_bit(a, 0);
+        counts[FAMILY_TOTAL[a]] = D.off[a].back();
+        for (int p = 0; p < 3; ++p)
+            if (sxg::RESULT_FAMILIES[a].pay[p].elem && present(h, FAMILY_SRC[a].pay[p].when)) counts[BC_PRESENT] |= (int64_t)1 << family_bit(a, p + 1);
+    }
+    for (int f = 0; f < sxg::N_RESULT_FLAT; ++f)
+        if (FLAT_SRC[f].buf && sxg::RESULT_FLAT[f].field != offsetof(sxg_poa_batch_out, block_cycles) && present(h, FLAT_SRC[f].when))
+            counts[BC_PRESENT] |= (int64_t)1 << flat_bit(f);
+    const size_t total = blob_views(counts, nullptr, nullptr);
+    counts[BC_BYTES] = (int64_t)total;
+    if ((rc = h->d_blob.ensure(total + 16))) return rc;
+    sxg_poa_batch_out v;
+    memset(&v, 0, sizeof(v));
+    blob_views(counts, h->d_blob.as<uint8_t>(), &v);
+    for (int a = 0; a < sxg::N_RESULT_FAMILIES; ++a) {
+        const sxg::ResultFamily& A = sxg::RESULT_FAMILIES[a];
+        if (void* off = sxg::get_field(v, A.off_field)) HIPCHK(hipMemcpy(off, D.off[a].data(), 8 * D.off[a].size(), hipMemcpyHostToDevice));
+        for (int p = 0; p < 3; ++p) {
+            void* dst = A.pay[p].elem ? sxg::get_field(v, A.pay[p].field) : nullptr;
+            const size_t bytes = A.pay[p].elem * (size_t)counts[FAMILY_TOTAL[a]];
+            if (!dst || !bytes) continue;
+            const DevSource& S = FAMILY_SRC[a].pay[p];
+            if (S.src == SRC_DENSE) { HIPCHK(hipMemcpyAsync(dst, (h->*S.buf).p, bytes, hipMemcpyDeviceToDevice, h->stream)); continue; }
+            if ((rc = gather(h, D, S.src, a, h->*S.buf, A.pay[p].elem, dst, bytes))) return rc;
+            HIPCHK(hipStreamSynchronize(h->stream));   // (the offset vectors on the device are reused by the next array)
         }
-        counts[BC_BG] = h->want_block_graph; counts[BC_BG_NODES] = gno[nb]; counts[BC_BG_EDGES] = geo[nb]; counts[BC_BG_SEQ] = gso[nb];
-        counts[BC_BG_STEPS] = gpo[nb]; counts[BC_BG_CONS] = gco[nb];
     }
-    const BlobLayout B = blob_layout(counts);
-    counts[BC_BYTES] = (int64_t)B.total;
-    int rc;
-    if ((rc = h->d_blob.ensure(B.total + 16))) return rc;
-    if ((rc = h->d_tmp_a.ensure(8 * (size_t)(nb + 1))) || (rc = h->d_tmp_b.ensure(8 * (size_t)(nb + 1)))) return rc;
-    uint8_t* blob = h->d_blob.as<uint8_t>();
-    if (nb) {
-        HIPCHK(hipMemcpyAsync(blob + B.status, h->d_status.p, 4 * (size_t)nb, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(blob + B.nn, h->d_nn.p, 4 * (size_t)nb, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(blob + B.ne, h->d_ne.p, 4 * (size_t)nb, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(blob + B.nc, h->d_nc.p, 4 * (size_t)nb, hipMemcpyDeviceToDevice, h->stream));
-    }
-    if (h->n_seqs) {
-        HIPCHK(hipMemcpyAsync(blob + B.score, h->d_score.p, 4 * (size_t)h->n_seqs, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(blob + B.cells, h->d_cells.p, 8 * (size_t)h->n_seqs, hipMemcpyDeviceToDevice, h->stream));
-    }
-    if (h->n_bases && counts[BC_BG] != 2) HIPCHK(hipMemcpyAsync(blob + B.paths, h->d_paths.p, 4 * (size_t)h->n_bases, hipMemcpyDeviceToDevice, h->stream));
-    if (bg && nb) HIPCHK(hipMemcpyAsync(blob + B.bg_counts, h->d_bg_counts.p, 4 * (size_t)BGC_N * (size_t)nb, hipMemcpyDeviceToDevice, h->stream));
-    if (bg && h->n_seqs) HIPCHK(hipMemcpyAsync(blob + B.bg_nsteps, h->d_bg_nsteps.p, 4 * (size_t)h->n_seqs, hipMemcpyDeviceToDevice, h->stream));
-    const std::vector<int64_t>* cur_src = &soff;
-    auto gather = [&](auto tag, const DevBuf& src, const std::vector<int64_t>& off, size_t at) -> int {
-        typedef decltype(tag) Tv;
-        if (off[nb] == 0) return SXG_OK;
-        HIPCHK(hipMemcpyAsync(h->d_tmp_a.p, cur_src->data(), 8 * (size_t)(nb + 1), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_tmp_b.p, off.data(), 8 * (size_t)(nb + 1), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL((gather_kernel<Tv>), dim3((unsigned)std::min(nb, 4096)), dim3(256), 0, h->stream, src.as<Tv>(), (Tv*)(blob + at),
-                           h->d_tmp_a.as<int64_t>(), h->d_tmp_b.as<int64_t>(), nb);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));   // (d_tmp_b is reused by the next array)
-        return SXG_OK;
-    };
-    if ((rc = gather(uint8_t(), h->d_node_code, noff, B.code)) || (rc = gather(int32_t(), h->d_node_rank, noff, B.rank)) ||
-        (rc = gather(int32_t(), h->d_node_group, noff, B.group)) || (rc = gather(int32_t(), h->d_edge_tail, eoff, B.et)) ||
-        (rc = gather(int32_t(), h->d_edge_head, eoff, B.eh)) || (rc = gather(uint32_t(), h->d_edge_w, eoff, B.ew)))
-        return rc;
-    if (h->want_consensus && (rc = gather(int32_t(), h->d_cons, coff, B.cons))) return rc;
-    if (bg) {
-        cur_src = &src_no;
-        if ((rc = gather(int32_t(), h->d_bg_len, gno, B.bg_len)) || (rc = gather(int32_t(), h->d_bg_od, gno, B.bg_od)) ||
-            (rc = gather(uint8_t(), h->d_bg_id, gno, B.bg_id)) || (rc = gather(uint8_t(), h->d_bg_seq, gso, B.bg_seq)))
-            return rc;
-        if (h->want_consensus && (rc = gather(int32_t(), h->d_bg_cons, gco, B.bg_cons))) return rc;
-        cur_src = &src_eo;
-        if ((rc = gather(int32_t(), h->d_bg_eto, geo, B.bg_eto))) return rc;
-        cur_src = &soff;
-        if ((rc = gather(int32_t(), h->d_bg_steps, gpo, B.bg_steps))) return rc;
+    for (int f = 0; f < sxg::N_RESULT_FLAT; ++f) {
+        void* dst = sxg::get_field(v, sxg::RESULT_FLAT[f].field);
+        const size_t bytes = sxg::RESULT_FLAT[f].elem * (size_t)counts[sxg::RESULT_FLAT[f].index == 0 ? BC_NB : sxg::RESULT_FLAT[f].index == 1 ? BC_NS : BC_NBASES];
+        if (dst && bytes) HIPCHK(hipMemcpyAsync(dst, (h->*FLAT_SRC[f].buf).p, bytes, hipMemcpyDeviceToDevice, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     return SXG_OK;
 }
-void format_msa(OutOwner* o, const sxg_poa_batch_in* in, bool want_consensus);
 // root: results of all ranks (host copies of their blobs) -> one result set in the batch's block order
 int assemble(const sxg_poa_batch_in* in, const std::vector<std::vector<int32_t>>& parts, const std::vector<std::vector<uint8_t>>& blobs,
              const std::vector<int64_t>& counts, sxg_poa_batch_out* out) {
-    const int nb = in->n_blocks, nranks = (int)parts.size();
-    const int64_t ns = nb ? in->blk_off[nb] : 0, nbases = ns ? in->seq_off[ns] : 0;
     OutOwner* o = new OutOwner();
     out->_owner = o;
-    out->n_blocks = nb; out->n_seqs = ns;
-    o->status.assign(std::max(nb, 1), 0); o->score.assign((size_t)std::max<int64_t>(ns, 1), 0); o->cells.assign((size_t)std::max<int64_t>(ns, 1), 0);
-    o->node_off.assign(nb + 1, 0); o->edge_off.assign(nb + 1, 0); o->cons_off.assign(nb + 1, 0);
-    int bg_mode = 0;   // what the ranks sent (the same on all of them: every rank was handed the same request)
-    for (int r = 0; r < nranks; ++r) if (counts[(size_t)r * BC_N + BC_NB] > 0) bg_mode = std::max(bg_mode, (int)counts[(size_t)r * BC_N + BC_BG]);
-    const bool with_paths = bg_mode != 2;
-    const bool with_graphs = true;   // (a sharded run always carries the raw POA graphs to the root)
-    if (with_paths) {
-        o->seq_path_nodes = (int32_t*)host_big_alloc(4 * (size_t)std::max<int64_t>(nbases, 1));
-        if (!o->seq_path_nodes) return fail(SXG_E_NOMEM, "host allocation of the path array failed");
+    std::vector<sxg_poa_batch_out> views(parts.size());
+    for (size_t r = 0; r < parts.size(); ++r) {
+        memset(&views[r], 0, sizeof(views[r]));
+        const int64_t* c = counts.data() + r * BC_N;
+        if (c[BC_NB] != (int64_t)parts[r].size() || (size_t)c[BC_BYTES] > blobs[r].size() || blob_views(c, nullptr, nullptr) != (size_t)c[BC_BYTES])
+            return fail(SXG_E_INVALID, "rank " + std::to_string(r) + " sent a blob that does not match the deal");
+        blob_views(counts.data() + r * BC_N, const_cast<uint8_t*>(blobs[r].data()), &views[r]);
     }
-    // where every block sits: (rank, index in the rank's shard, offsets inside that rank's arrays)
-    struct Where { int rank, idx; int64_t n0, e0, c0, s0, b0, gn0, gs0, ge0, gc0, gp0; };
-    std::vector<Where> where(std::max(nb, 1));
-    for (int r = 0; r < nranks; ++r) {
-        const int64_t* c = counts.data() + (size_t)r * BC_N;
-        const BlobLayout B = blob_layout(c);
-        const uint8_t* blob = blobs[r].data();
-        const int32_t *nn = (const int32_t*)(blob + B.nn), *ne = (const int32_t*)(blob + B.ne), *nc = (const int32_t*)(blob + B.nc);
-        int64_t n0 = 0, e0 = 0, c0 = 0, s0 = 0, b0 = 0, gn0 = 0, gs0 = 0, ge0 = 0, gc0 = 0, gp0 = 0;
-        const int32_t* gcnt = (const int32_t*)(blob + B.bg_counts);
-        const int32_t* gnst = (const int32_t*)(blob + B.bg_nsteps);
-        const int32_t* rst = (const int32_t*)(blob + B.status);
-        for (size_t k = 0; k < parts[r].size(); ++k) {
-            const int b = parts[r][k];
-            where[b] = Where{r, (int)k, n0, e0, c0, s0, b0, gn0, gs0, ge0, gc0, gp0};
-            if (c[BC_BG] && rst[k] == ST_OK) {
-                const int32_t* q = gcnt + (size_t)BGC_N * k;
-                gn0 += q[BGC_NODES]; gs0 += q[BGC_SEQ]; ge0 += q[BGC_EDGES]; gc0 += in->want_consensus ? q[BGC_CONS] : 0;
-                for (int64_t sq = s0; sq < s0 + (in->blk_off[b + 1] - in->blk_off[b]); ++sq) gp0 += gnst[sq];
-            }
-            o->node_off[b + 1] = nn[k]; o->edge_off[b + 1] = ne[k]; o->cons_off[b + 1] = in->want_consensus ? nc[k] : 0;
-            n0 += nn[k]; e0 += ne[k]; c0 += in->want_consensus ? nc[k] : 0;
-            s0 += in->blk_off[b + 1] - in->blk_off[b];
-            b0 += in->seq_off[in->blk_off[b + 1]] - in->seq_off[in->blk_off[b]];
-        }
-    }
-    for (int b = 0; b < nb; ++b) { o->node_off[b + 1] += o->node_off[b]; o->edge_off[b + 1] += o->edge_off[b]; o->cons_off[b + 1] += o->cons_off[b]; }
-    o->node_code.resize((size_t)std::max<int64_t>(o->node_off[nb], 1)); o->node_rank.resize(o->node_code.size()); o->node_group.resize(o->node_code.size());
-    o->edge_tail.resize((size_t)std::max<int64_t>(o->edge_off[nb], 1)); o->edge_head.resize(o->edge_tail.size()); o->edge_weight.resize(o->edge_tail.size());
-    o->cons_nodes.resize((size_t)std::max<int64_t>(o->cons_off[nb], 1));
-    for (int b = 0; b < nb; ++b) {
-        const Where& wv = where[b];
-        const BlobLayout B = blob_layout(counts.data() + (size_t)wv.rank * BC_N);
-        const uint8_t* blob = blobs[wv.rank].data();
-        o->status[b] = ((const int32_t*)(blob + B.status))[wv.idx];
-        const int64_t nn = o->node_off[b + 1] - o->node_off[b], ne = o->edge_off[b + 1] - o->edge_off[b], nc = o->cons_off[b + 1] - o->cons_off[b];
-        memcpy(o->node_code.data() + o->node_off[b], blob + B.code + wv.n0, (size_t)nn);
-        memcpy(o->node_rank.data() + o->node_off[b], blob + B.rank + 4 * wv.n0, 4 * (size_t)nn);
-        memcpy(o->node_group.data() + o->node_off[b], blob + B.group + 4 * wv.n0, 4 * (size_t)nn);
-        memcpy(o->edge_tail.data() + o->edge_off[b], blob + B.et + 4 * wv.e0, 4 * (size_t)ne);
-        memcpy(o->edge_head.data() + o->edge_off[b], blob + B.eh + 4 * wv.e0, 4 * (size_t)ne);
-        memcpy(o->edge_weight.data() + o->edge_off[b], blob + B.ew + 4 * wv.e0, 4 * (size_t)ne);
-        if (nc) memcpy(o->cons_nodes.data() + o->cons_off[b], blob + B.cons + 4 * wv.c0, 4 * (size_t)nc);
-        const int64_t nsq = in->blk_off[b + 1] - in->blk_off[b], nbs = in->seq_off[in->blk_off[b + 1]] - in->seq_off[in->blk_off[b]];
-        memcpy(o->score.data() + in->blk_off[b], blob + B.score + 4 * wv.s0, 4 * (size_t)nsq);
-        memcpy(o->cells.data() + in->blk_off[b], blob + B.cells + 8 * wv.s0, 8 * (size_t)nsq);
-        if (with_paths) memcpy(o->seq_path_nodes + in->seq_off[in->blk_off[b]], blob + B.paths + 4 * wv.b0, 4 * (size_t)nbs);
-    }
-    if (bg_mode) {
-        // block graphs in the batch's block order: offsets first, then every block's pieces from its rank's blob
-        o->bg_node_off.assign(nb + 1, 0); o->bg_seq_off.assign(nb + 1, 0); o->bg_edge_off.assign(nb + 1, 0); o->bg_cons_off.assign(nb + 1, 0);
-        o->bg_step_off.assign((size_t)ns + 1, 0);
-        for (int b = 0; b < nb; ++b) {
-            const Where& wv = where[b];
-            const int64_t* c = counts.data() + (size_t)wv.rank * BC_N;
-            const BlobLayout B = blob_layout(c);
-            const uint8_t* blob = blobs[wv.rank].data();
-            const bool ok = c[BC_BG] && o->status[b] == ST_OK;
-            const int32_t* q = (const int32_t*)(blob + B.bg_counts) + (size_t)BGC_N * wv.idx;
-            o->bg_node_off[b + 1] = o->bg_node_off[b] + (ok ? q[BGC_NODES] : 0);
-            o->bg_seq_off[b + 1] = o->bg_seq_off[b] + (ok ? q[BGC_SEQ] : 0);
-            o->bg_edge_off[b + 1] = o->bg_edge_off[b] + (ok ? q[BGC_EDGES] : 0);
-            o->bg_cons_off[b + 1] = o->bg_cons_off[b] + (ok && in->want_consensus ? q[BGC_CONS] : 0);
-            const int32_t* gnst = (const int32_t*)(blob + B.bg_nsteps) + wv.s0;
-            for (int sq = in->blk_off[b]; sq < in->blk_off[b + 1]; ++sq)
-                o->bg_step_off[(size_t)sq + 1] = o->bg_step_off[(size_t)sq] + (ok ? gnst[sq - in->blk_off[b]] : 0);
-        }
-        o->bg_node_len.resize((size_t)std::max<int64_t>(o->bg_node_off[nb], 1)); o->bg_node_outdeg.resize(o->bg_node_len.size());
-        o->bg_node_indeg.resize(o->bg_node_len.size()); o->bg_seq.resize((size_t)std::max<int64_t>(o->bg_seq_off[nb], 1));
-        o->bg_edge_to.resize((size_t)std::max<int64_t>(o->bg_edge_off[nb], 1)); o->bg_steps.resize((size_t)std::max<int64_t>(o->bg_step_off[(size_t)ns], 1));
-        o->bg_cons_steps.resize((size_t)std::max<int64_t>(o->bg_cons_off[nb], 1));
-        for (int b = 0; b < nb; ++b) {
-            const Where& wv = where[b];
-            const BlobLayout B = blob_layout(counts.data() + (size_t)wv.rank * BC_N);
-            const uint8_t* blob = blobs[wv.rank].data();
-            const int64_t n = o->bg_node_off[b + 1] - o->bg_node_off[b], sb = o->bg_seq_off[b + 1] - o->bg_seq_off[b], ne = o->bg_edge_off[b + 1] - o->bg_edge_off[b];
-            const int64_t nc = o->bg_cons_off[b + 1] - o->bg_cons_off[b];
-            const int64_t p0 = o->bg_step_off[(size_t)in->blk_off[b]], np = o->bg_step_off[(size_t)in->blk_off[b + 1]] - p0;
-            if (n) {
-                memcpy(o->bg_node_len.data() + o->bg_node_off[b], blob + B.bg_len + 4 * wv.gn0, 4 * (size_t)n);
-                memcpy(o->bg_node_outdeg.data() + o->bg_node_off[b], blob + B.bg_od + 4 * wv.gn0, 4 * (size_t)n);
-                memcpy(o->bg_node_indeg.data() + o->bg_node_off[b], blob + B.bg_id + wv.gn0, (size_t)n);
-            }
-            if (sb) memcpy(o->bg_seq.data() + o->bg_seq_off[b], blob + B.bg_seq + wv.gs0, (size_t)sb);
-            if (ne) memcpy(o->bg_edge_to.data() + o->bg_edge_off[b], blob + B.bg_eto + 4 * wv.ge0, 4 * (size_t)ne);
-            if (nc) memcpy(o->bg_cons_steps.data() + o->bg_cons_off[b], blob + B.bg_cons + 4 * wv.gc0, 4 * (size_t)nc);
-            if (np) memcpy(o->bg_steps.data() + p0, blob + B.bg_steps + 4 * wv.gp0, 4 * (size_t)np);
-        }
-        out->bg_node_off = o->bg_node_off.data(); out->bg_node_len = o->bg_node_len.data(); out->bg_node_outdeg = o->bg_node_outdeg.data();
-        out->bg_node_indeg = o->bg_node_indeg.data(); out->bg_seq_off = o->bg_seq_off.data(); out->bg_seq = (char*)o->bg_seq.data();
-        out->bg_edge_off = o->bg_edge_off.data(); out->bg_edge_to = o->bg_edge_to.data(); out->bg_step_off = o->bg_step_off.data();
-        out->bg_steps = o->bg_steps.data();
-        if (in->want_consensus) { out->bg_cons_off = o->bg_cons_off.data(); out->bg_cons_steps = o->bg_cons_steps.data(); }
-    }
-    out->status = o->status.data();
-    out->node_off = o->node_off.data(); out->edge_off = o->edge_off.data();
-    if (with_graphs) {
-        out->node_code = o->node_code.data(); out->node_rank = o->node_rank.data(); out->node_group = o->node_group.data();
-        out->edge_tail = o->edge_tail.data(); out->edge_head = o->edge_head.data(); out->edge_weight = o->edge_weight.data();
-    }
-    out->seq_path_nodes = o->seq_path_nodes; out->score = o->score.data(); out->cells = o->cells.data();
-    if (in->want_consensus) { out->cons_off = o->cons_off.data(); out->cons_nodes = o->cons_nodes.data(); }
-    if (in->want_msa && o->seq_path_nodes) {
-        format_msa(o, in, in->want_consensus != 0);
-        out->msa_off = o->msa_off.data(); out->msa_cols = o->msa_cols.data(); out->msa = o->msa.data();
-    }
-    for (int b = 0; b < nb; ++b)
-        if (o->status[b] != ST_OK) return fail(SXG_E_BLOCK, "block " + std::to_string(b) + " failed with status " + std::to_string(o->status[b]));
+    const sxg::BatchShape S{in->n_blocks, in->blk_off, in->seq_off};
+    auto alloc = [o](size_t bytes) { return o->alloc(bytes); };
+    if (!sxg::reassemble_results(S, parts, views, alloc, out)) return fail(SXG_E_NOMEM, "host allocation of the reassembled result failed");
+    if (in->want_msa && out->seq_path_nodes && !sxg::format_full_msa(S, in->want_consensus != 0, alloc, out))
+        return fail(SXG_E_NOMEM, "host allocation of the MSA failed");
+    for (int b = 0; b < in->n_blocks; ++b)
+        if (out->status[b] != ST_OK) return fail(SXG_E_BLOCK, "block " + std::to_string(b) + " failed with status " + std::to_string(out->status[b]));
     return SXG_OK;
-}
-// S8: MSA column = aligned group in rank order; pure formatting of the results (same rule as sxg_poa_batch_download)
-void format_msa(OutOwner* o, const sxg_poa_batch_in* in, bool want_consensus) {
-    static const char dec[5] = {'A', 'C', 'G', 'T', 'N'};
-    const int nb = in->n_blocks;
-    o->msa_off.assign(nb + 1, 0); o->msa_cols.assign(std::max(nb, 1), 0);
-    std::vector<std::vector<int32_t>> cols(nb);
-    for (int b = 0; b < nb; ++b) {
-        const int64_t n0 = o->node_off[b];
-        const int n = (int)(o->node_off[b + 1] - n0);
-        std::vector<int32_t> by_rank(n);
-        for (int v = 0; v < n; ++v) by_rank[o->node_rank[n0 + v]] = v;
-        cols[b].assign(n, 0);
-        int ncol = 0;
-        for (int r = 0; r < n; ++r) {
-            const int v = by_rank[r];
-            if (r > 0 && o->node_group[n0 + by_rank[r - 1]] == o->node_group[n0 + v]) cols[b][v] = ncol - 1; else cols[b][v] = ncol++;
-        }
-        o->msa_cols[b] = ncol;
-        const int rows = (in->blk_off[b + 1] - in->blk_off[b]) + (want_consensus ? 1 : 0);
-        o->msa_off[b + 1] = o->msa_off[b] + (o->status[b] == ST_OK ? (int64_t)rows * ncol : 0);
-    }
-    o->msa.assign((size_t)std::max<int64_t>(o->msa_off[nb], 1), '-');
-    for (int b = 0; b < nb; ++b) {
-        if (o->status[b] != ST_OK) continue;
-        const int64_t n0 = o->node_off[b];
-        const int ncol = o->msa_cols[b];
-        char* base = o->msa.data() + o->msa_off[b];
-        int row = 0;
-        for (int sq = in->blk_off[b]; sq < in->blk_off[b + 1]; ++sq, ++row)
-            for (int64_t k = in->seq_off[sq]; k < in->seq_off[sq + 1]; ++k) base[(int64_t)row * ncol + cols[b][o->seq_path_nodes[k]]] = dec[o->node_code[n0 + o->seq_path_nodes[k]]];
-        if (want_consensus)
-            for (int64_t k = o->cons_off[b]; k < o->cons_off[b + 1]; ++k) base[(int64_t)row * ncol + cols[b][o->cons_nodes[k]]] = dec[o->node_code[n0 + o->cons_nodes[k]]];
-    }
 }
 int run_shard(sxg_poa_handle* h, const sxg_poa_batch_in* in, const std::vector<int32_t>& part, int64_t* counts) {
     LocalBatch L;
@@ -2262,7 +2054,6 @@ extern "C" int sxg_poa_batch_execute_sharded(sxg_poa_handle* h) {
     const auto t_pack = std::chrono::steady_clock::now();
     { const RoctxRange range_("sxg_poa sharded: pack"); if (!rc || rc == SXG_E_BLOCK) rc = pack_blob(h, mine); }   // (per-block failures travel in the status array)
     const auto t_xch = std::chrono::steady_clock::now();
-    const RoctxRange range_("sxg_poa sharded: exchange");
     h->sh_pack_ms = std::chrono::duration<double, std::milli>(t_xch - t_pack).count();
     h->sh_exchange_ms = 0;
     if (!h->comm) {
@@ -2271,6 +2062,7 @@ extern "C" int sxg_poa_batch_execute_sharded(sxg_poa_handle* h) {
         return SXG_OK;
     }
     {   // (a communicator of ONE rank takes the same way: the collectives run, nothing is sent)
+        const RoctxRange range_("sxg_poa sharded: exchange");
         // A rank-local failure (allocation, HIP error) must not leave the peers blocked in a collective: the failing rank
         // still takes part in the size exchange, with its error code in BC_PAD and nothing to send, and EVERY rank then
         // returns that failure -- the ranks fail together.  (d_counts is allocated by sxg_poa_comm_init / _attach.)
@@ -2411,16 +2203,18 @@ extern "C" int sxg_poa_batch_run_sharded_local(sxg_poa_handle* h, const sxg_poa_
 // of its device list; a batch is dealt over the members in contiguous slices of equal cost (poa_deal.h), every member runs
 // the single-handle upload / execute / download on its slice from a host thread of its own -- on its own device, streams and
 // arenas, at the same time as the others --, and the results, being slices of the batch's dense arrays, are put back with one
-// copy per array and member.  No communicator, no rank, no collective, and no blob: what a member downloads IS its part of
-// the result (trimmed MSA rows, block graphs and block cycles included), only the offsets are rebased.
+// copy per array and member (sxg::reassemble_results of poa_results.h, over the table of the result arrays).  No communicator,
+// no rank, no collective, and no blob: what a member downloads IS its part of the result (trimmed MSA rows, block graphs and
+// block cycles included), only the offsets are rebased.
 struct sxg_poa_group {
     std::vector<sxg_poa_handle*> members;
-    // the uploaded batch: its deal (member m runs blocks cut[m] .. cut[m + 1] - 1), where the slices start, who has work
+    // the uploaded batch: its shape, its deal (member m runs blocks cut[m] .. cut[m + 1] - 1, listed in parts[m]), who has work
     bool have_batch = false, executed = false;
     int n_blocks = 0;
     int64_t n_seqs = 0;
-    std::vector<int32_t> cut, seq0;
-    std::vector<int64_t> base0;
+    std::vector<int32_t> cut, blk_off;
+    std::vector<int64_t> seq_off;
+    std::vector<std::vector<int32_t>> parts;
     std::vector<char> active;
     // last execute + download: wall milliseconds per member, the longest download, the reassembly on the host
     std::vector<double> exec_ms, down_ms;
@@ -2469,31 +2263,6 @@ int group_for_each(sxg_poa_group* g, const char* what, F fn) {
 double ms_since(const std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
-// The result struct's arrays by the index their offsets run over: the reassembly treats them alike.  Fields are addressed by
-// their place in the (standard-layout) struct; every one of them is a data pointer.
-struct GroupPayload { size_t field, elem; };
-struct GroupRagged { size_t off_field; int per_seq; GroupPayload pay[3]; };   // offsets [blocks + 1] (per_seq: [sequences + 1]) and what they index
-struct GroupFlat { size_t field, elem; int index; };                         // one entry per block (0), sequence (1) or base (2)
-#define SXG_GF(f) offsetof(sxg_poa_batch_out, f)
-const GroupRagged GROUP_RAGGED[] = {
-    {SXG_GF(node_off), 0, {{SXG_GF(node_code), 1}, {SXG_GF(node_rank), 4}, {SXG_GF(node_group), 4}}},
-    {SXG_GF(edge_off), 0, {{SXG_GF(edge_tail), 4}, {SXG_GF(edge_head), 4}, {SXG_GF(edge_weight), 4}}},
-    {SXG_GF(cons_off), 0, {{SXG_GF(cons_nodes), 4}, {0, 0}, {0, 0}}},
-    {SXG_GF(msa_off), 0, {{SXG_GF(msa), 1}, {0, 0}, {0, 0}}},
-    {SXG_GF(bg_node_off), 0, {{SXG_GF(bg_node_len), 4}, {SXG_GF(bg_node_outdeg), 4}, {SXG_GF(bg_node_indeg), 1}}},
-    {SXG_GF(bg_seq_off), 0, {{SXG_GF(bg_seq), 1}, {0, 0}, {0, 0}}},
-    {SXG_GF(bg_edge_off), 0, {{SXG_GF(bg_edge_to), 4}, {0, 0}, {0, 0}}},
-    {SXG_GF(bg_step_off), 1, {{SXG_GF(bg_steps), 4}, {0, 0}, {0, 0}}},
-    {SXG_GF(bg_cons_off), 0, {{SXG_GF(bg_cons_steps), 4}, {0, 0}, {0, 0}}},
-};
-const GroupFlat GROUP_FLAT[] = {
-    {SXG_GF(status), 4, 0}, {SXG_GF(msa_cols), 4, 0}, {SXG_GF(block_cycles), 8, 0},
-    {SXG_GF(score), 4, 1}, {SXG_GF(cells), 8, 1}, {SXG_GF(seq_path_nodes), 4, 2},
-};
-#undef SXG_GF
-constexpr int GROUP_N_RAGGED = (int)(sizeof(GROUP_RAGGED) / sizeof(GROUP_RAGGED[0])), GROUP_N_FLAT = (int)(sizeof(GROUP_FLAT) / sizeof(GROUP_FLAT[0]));
-void* get_field(const sxg_poa_batch_out& o, size_t at) { void* q; memcpy(&q, (const char*)&o + at, sizeof(q)); return q; }
-void set_field(sxg_poa_batch_out& o, size_t at, void* q) { memcpy((char*)&o + at, &q, sizeof(q)); }
 }  // namespace
 
 extern "C" int sxg_poa_group_create(const int32_t* devices, int32_t n, sxg_poa_group** out) {
@@ -2561,14 +2330,15 @@ extern "C" int sxg_poa_group_batch_upload(sxg_poa_group* g, const sxg_poa_batch_
     if (ns > 0 && in->seq_off[ns] > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
     sxg::deal_batch(nb, in->blk_off, in->seq_off, n, g->cut);
     g->n_blocks = nb; g->n_seqs = ns;
-    g->seq0.assign((size_t)n + 1, 0); g->base0.assign((size_t)n + 1, 0);
+    g->blk_off.assign(in->blk_off, in->blk_off + (nb ? nb + 1 : 0)); g->seq_off.assign(in->seq_off, in->seq_off + (nb ? ns + 1 : 0));
+    g->parts.assign((size_t)n, {});
     struct Slice { std::vector<int32_t> blk_off; std::vector<int64_t> seq_off; sxg_poa_batch_in in; };
     std::vector<Slice> slices((size_t)n);
     for (int m = 0; m < n; ++m) {
         const int b0 = g->cut[(size_t)m], b1 = g->cut[(size_t)m + 1];
         const int32_t s0 = nb ? in->blk_off[b0] : 0, s1 = nb ? in->blk_off[b1] : 0;
         const int64_t x0 = ns ? in->seq_off[s0] : 0;
-        g->seq0[(size_t)m] = s0; g->base0[(size_t)m] = x0;
+        for (int b = b0; b < b1; ++b) g->parts[(size_t)m].push_back(b);
         g->active[(size_t)m] = b1 > b0 || (nb == 0 && m == 0);   // (a batch without blocks is member 0's: it answers as one handle does)
         if (!g->active[(size_t)m]) continue;
         Slice& S = slices[(size_t)m];
@@ -2584,7 +2354,6 @@ extern "C" int sxg_poa_group_batch_upload(sxg_poa_group* g, const sxg_poa_batch_
         S.in.params = in->per_block_params ? in->params + b0 : in->params;
         S.in.bg_trim = in->bg_trim ? in->bg_trim + b0 : nullptr;
     }
-    g->seq0[(size_t)n] = (int32_t)ns; g->base0[(size_t)n] = ns ? in->seq_off[ns] : 0;
     const int rc = group_for_each(g, "upload", [&](int m) { return sxg_poa_batch_upload(g->members[(size_t)m], &slices[(size_t)m].in); });
     if (rc) return rc;
     g->have_batch = true;
@@ -2626,8 +2395,7 @@ extern "C" int sxg_poa_group_batch_download(sxg_poa_group* g, sxg_poa_batch_out*
     if (!g || !out) return fail(SXG_E_INVALID, "NULL argument");
     memset(out, 0, sizeof(*out));
     if (!g->have_batch || !g->executed) return fail(SXG_E_INVALID, "no executed batch to download");
-    const int n = (int)g->members.size(), nb = g->n_blocks;
-    const int64_t ns = g->n_seqs;
+    const int n = (int)g->members.size();
     std::vector<sxg_poa_batch_out> outs((size_t)n);
     for (auto& o : outs) memset(&o, 0, sizeof(o));
     auto drop = [&] { for (auto& o : outs) sxg_poa_batch_free(&o); };
@@ -2646,61 +2414,16 @@ extern "C" int sxg_poa_group_batch_download(sxg_poa_group* g, sxg_poa_batch_out*
         *out = outs[(size_t)first];   // one slice is the whole batch: the member's result is the group's
         memset(&outs[(size_t)first], 0, sizeof(sxg_poa_batch_out));
     } else {
-        // Several slices: offsets first (each member's start at 0: rebased by what the members before it hold), then every
-        // member's arrays into their places, one thread per member.
+        // Several slices: the batch's offsets and room for every array first, then every member's arrays into their places,
+        // one thread per member.
         OutOwner* o = new OutOwner();
-        out->_owner = o; out->n_blocks = nb; out->n_seqs = ns;
-        bool oom = false;
-        auto alloc = [&](size_t bytes) -> void* {
-            void* q = host_big_alloc(std::max<size_t>(bytes, 8));
-            if (q) o->raw.push_back(q); else oom = true;
-            return q;
-        };
-        const sxg_poa_batch_out& T = outs[(size_t)first];   // (every member was handed the same request: the same arrays are present)
-        std::vector<int64_t> start((size_t)GROUP_N_RAGGED * (size_t)n, 0), total((size_t)GROUP_N_RAGGED * (size_t)n, 0);
-        for (int a = 0; a < GROUP_N_RAGGED && !oom; ++a) {
-            const GroupRagged& A = GROUP_RAGGED[a];
-            if (!get_field(T, A.off_field)) continue;
-            int64_t* off = (int64_t*)alloc(8 * (size_t)((A.per_seq ? ns : (int64_t)nb) + 1));
-            if (!off) break;
-            int64_t running = 0;
-            off[0] = 0;
-            for (int m = 0; m < n; ++m) {
-                if (!g->active[(size_t)m]) continue;
-                const int64_t* src = (const int64_t*)get_field(outs[(size_t)m], A.off_field);
-                const int64_t i0 = A.per_seq ? g->seq0[(size_t)m] : g->cut[(size_t)m];
-                const int64_t cnt = A.per_seq ? g->seq0[(size_t)m + 1] - g->seq0[(size_t)m] : g->cut[(size_t)m + 1] - g->cut[(size_t)m];
-                for (int64_t k = 0; k <= cnt; ++k) off[i0 + k] = running + src[k];
-                start[(size_t)a * n + m] = running; total[(size_t)a * n + m] = src[cnt];
-                running += src[cnt];
-            }
-            set_field(*out, A.off_field, off);
-            for (const GroupPayload& P : A.pay)
-                if (P.elem && get_field(T, P.field)) set_field(*out, P.field, alloc((size_t)running * P.elem));
+        out->_owner = o;
+        const sxg::BatchShape S{g->n_blocks, g->blk_off.data(), g->seq_off.data()};
+        if (!sxg::reassemble_layout(S, g->parts, outs, [o](size_t bytes) { return o->alloc(bytes); }, out)) {
+            drop(); sxg_poa_batch_free(out);
+            return fail(SXG_E_NOMEM, "host allocation of the group's result failed");
         }
-        for (int f = 0; f < GROUP_N_FLAT && !oom; ++f) {
-            const GroupFlat& F = GROUP_FLAT[f];
-            if (!get_field(T, F.field)) continue;
-            const int64_t cnt = F.index == 0 ? nb : F.index == 1 ? ns : g->base0[(size_t)n];
-            set_field(*out, F.field, alloc((size_t)cnt * F.elem));
-        }
-        if (oom) { drop(); sxg_poa_batch_free(out); return fail(SXG_E_NOMEM, "host allocation of the group's result failed"); }
-        rc = group_for_each(g, "reassembly", [&](int m) {
-            const sxg_poa_batch_out& M = outs[(size_t)m];
-            for (int a = 0; a < GROUP_N_RAGGED; ++a)
-                for (const GroupPayload& P : GROUP_RAGGED[a].pay) {
-                    uint8_t* dst = P.elem ? (uint8_t*)get_field(*out, P.field) : nullptr;
-                    const size_t bytes = (size_t)total[(size_t)a * n + m] * P.elem;
-                    if (dst && bytes) memcpy(dst + (size_t)start[(size_t)a * n + m] * P.elem, get_field(M, P.field), bytes);
-                }
-            for (const GroupFlat& F : GROUP_FLAT) {
-                uint8_t* dst = (uint8_t*)get_field(*out, F.field);
-                const int64_t i0 = F.index == 0 ? g->cut[(size_t)m] : F.index == 1 ? g->seq0[(size_t)m] : g->base0[(size_t)m];
-                const int64_t i1 = F.index == 0 ? g->cut[(size_t)m + 1] : F.index == 1 ? g->seq0[(size_t)m + 1] : g->base0[(size_t)m + 1];
-                if (dst && i1 > i0) memcpy(dst + (size_t)i0 * F.elem, get_field(M, F.field), (size_t)(i1 - i0) * F.elem);
-            }
-            return SXG_OK;
-        });
+        rc = group_for_each(g, "reassembly", [&](int m) { sxg::reassemble_part(S, g->parts[(size_t)m], outs[(size_t)m], out); return SXG_OK; });
         if (rc) { const std::string keep = g_err; drop(); sxg_poa_batch_free(out); return fail(rc, keep); }
     }
     drop();

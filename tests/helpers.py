@@ -127,6 +127,36 @@ def heaviest_bundle_independent(code, rank, edge_tail, edge_head, edge_weight):
     return np.asarray(path[::-1], np.int32)
 
 
+def same_array(a, b, what):
+    assert (a is None) == (b is None), what
+    if a is not None:
+        assert a.dtype == b.dtype and a.shape == b.shape and (a == b).all(), what
+
+
+def assert_same(got, want, label="", refused=()):
+    """Two result lists, field for field (device_cycles is a timing and is not compared).  refused: blocks that were refused
+    before they ran -- their status is compared, their scores and cells are whatever the result buffers held before."""
+    assert len(got) == len(want), label
+    for b, (x, y) in enumerate(zip(got, want)):
+        w = "%s block %d" % (label, b)
+        assert x.status == y.status, w
+        if b in refused:
+            assert len(x.node_code) == len(y.node_code) == 0 and x.msa is None and y.msa is None, w
+            continue
+        for f in ("node_code", "node_rank", "node_group", "edge_tail", "edge_head", "edge_weight", "scores", "cells", "consensus"):
+            same_array(getattr(x, f), getattr(y, f), w + " " + f)
+        assert (x.paths is None) == (y.paths is None), w
+        if x.paths is not None:
+            assert len(x.paths) == len(y.paths) and all((p == q).all() for p, q in zip(x.paths, y.paths)), w + " paths"
+        assert x.msa == y.msa, w + " msa"
+        assert (x.bg is None) == (y.bg is None), w
+        if x.bg is not None:
+            assert x.bg.node_seq == y.bg.node_seq and x.bg.edges == y.bg.edges, w + " block graph"
+            same_array(x.bg.node_indeg, y.bg.node_indeg, w + " in-degrees")
+            same_array(x.bg.consensus, y.bg.consensus, w + " consensus path")
+            assert len(x.bg.paths) == len(y.bg.paths) and all((p == q).all() for p, q in zip(x.bg.paths, y.bg.paths)), w + " steps"
+
+
 def rerun_in_own_process(request):
     """Tests that create a real RCCL communicator run in a pytest process of their own: a long-lived process that has
     loaded librccl.so (rccl 2.27.7 of ROCm 7.2) and goes on allocating and freeing HIP memory afterwards aborts in the

@@ -18,7 +18,7 @@ from smoothxg_amd import smooth as SM
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from helpers import random_block  # noqa: E402
+from helpers import assert_same, random_block  # noqa: E402
 from test_identity_host import smooth_gfa_with  # noqa: E402
 from test_maf_device_rows_host import HEADER  # noqa: E402
 from test_smooth_host import DRB1, synthetic_gfa  # noqa: E402
@@ -73,36 +73,6 @@ def base(base_blocks):
 def trims(base_blocks):
     """bg_trim as the iteration sets it: the block's padding, here 1/50 of its longest sequence (1, 6, 14 and 30 letters)."""
     return np.asarray([max((len(s) for s in blk), default=0) // 50 for blk in base_blocks], np.int32)
-
-
-def same_array(a, b, what):
-    assert (a is None) == (b is None), what
-    if a is not None:
-        assert a.dtype == b.dtype and a.shape == b.shape and (a == b).all(), what
-
-
-def assert_same(got, want, label="", refused=()):
-    """Two result lists, field for field (device_cycles is a timing and is not compared).  refused: blocks that were refused
-    before they ran -- their status is compared, their scores and cells are whatever the result buffers held before."""
-    assert len(got) == len(want), label
-    for b, (x, y) in enumerate(zip(got, want)):
-        w = "%s block %d" % (label, b)
-        assert x.status == y.status, w
-        if b in refused:
-            assert len(x.node_code) == len(y.node_code) == 0 and x.msa is None and y.msa is None, w
-            continue
-        for f in ("node_code", "node_rank", "node_group", "edge_tail", "edge_head", "edge_weight", "scores", "cells", "consensus"):
-            same_array(getattr(x, f), getattr(y, f), w + " " + f)
-        assert (x.paths is None) == (y.paths is None), w
-        if x.paths is not None:
-            assert len(x.paths) == len(y.paths) and all((p == q).all() for p, q in zip(x.paths, y.paths)), w + " paths"
-        assert x.msa == y.msa, w + " msa"
-        assert (x.bg is None) == (y.bg is None), w
-        if x.bg is not None:
-            assert x.bg.node_seq == y.bg.node_seq and x.bg.edges == y.bg.edges, w + " block graph"
-            same_array(x.bg.node_indeg, y.bg.node_indeg, w + " in-degrees")
-            same_array(x.bg.consensus, y.bg.consensus, w + " consensus path")
-            assert len(x.bg.paths) == len(y.bg.paths) and all((p == q).all() for p, q in zip(x.bg.paths, y.bg.paths)), w + " steps"
 
 
 RAW = dict(want_consensus=True, want_msa=P.MSA_FULL)
