@@ -35,6 +35,10 @@
     // instruction (pk_max3): the fields stay inside the patterns whose binary16 order is the integer order (poa_fields.h)
     constexpr bool MAX3 = SW && DS && CVX;
     static_assert(!MAX3 || p16_fields_are_f16_ordered(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, W), "biased fields leave the ordered binary16 patterns");
+    // the classes compiled for the default scores read the long gap piece inside a strip off the strip's carry: opened inside
+    // the strip it never beats the short piece there (p16_strip_q_dominated, poa_fields.h), so pass 2 keeps no Q state
+    constexpr bool QDOM = CVX && DS;
+    static_assert(!QDOM || p16_strip_q_dominated(P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, W), "the long piece may win inside a strip of this width");
     const int NEG2 = pk2(FLOORV, FLOORV), B2 = pk2(BIAS, BIAS), NWF2 = pk2(P16_NWFLOOR, P16_NWFLOOR);
     const unsigned Gm = (unsigned)(-g) * 0x10001u, Em = (unsigned)(-e) * 0x10001u, Qm = (unsigned)(-q) * 0x10001u, Cm = (unsigned)(-c) * 0x10001u;
 #define P16_DEC(x, Km, K2) (SW ? (int)((unsigned)(x) - (Km)) : pk_add((x), (K2)))   /* x + K */

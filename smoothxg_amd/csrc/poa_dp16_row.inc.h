@@ -81,11 +81,22 @@
         RP_MARK(2);  // waiting for the left neighbour
         xa = max(sxg_wave_shr1(xa, NEG * 2), in_e);   // max over every strip left of my lo strip, the mailbox's included
         xb = max(sxg_wave_shr1(xb, NEG * 2), in_q);
-        const int Ein_lo = max(xa + 2 * tWe - We, FLOORV);
-        const int Ein_hi = max(max(xa, ya_lo) + 2 * tWe, FLOORV);
+        // (MAX3, round 18: E enters a strip no lower than the bias and stays there -- E is neither stored nor returned, and an E
+        //  raised to the bias proposes nothing the clamp of H at the bias would not have produced: the clamp rides in E's update)
+        constexpr int EFLOOR = MAX3 ? BIAS : FLOORV;
+        const int Ein_lo = max(xa + 2 * tWe - We, EFLOOR);
+        const int Ein_hi = max(max(xa, ya_lo) + 2 * tWe, EFLOOR);
         const int Qin_lo = !CVX ? FLOORV : max(xb + 2 * tWc - Wc, FLOORV);
         const int Qin_hi = !CVX ? FLOORV : max(max(xb, yb_lo) + 2 * tWc, FLOORV);
         int E = pk2(Ein_lo, Ein_hi), Q = pk2(Qin_lo, Qin_hi);
+        // (QDOM: Q stays the carry that entered the strips.  What the long piece is after my hi strip's last column -- the word
+        //  the next wave reads -- is that carry run over the strip, or an opening inside the strip: b, which is built for the scan
+        //  from H before the in-row gaps exactly as the carries of the strips in between are)
+        int mbq = 0;
+        if constexpr (QDOM) {
+            static_assert(p16_strip_q_dominated(P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, W), "pass 2 without Q needs the short piece to dominate inside a strip");
+            mbq = max(Qin_hi + Wc, pk_hi(b));
+        }
 
         // ---- pass 2: final H
         int rowmax = SW ? 0 : NEG2;
@@ -93,21 +104,33 @@
         for (int k = 0; k < W; ++k) {
             if (EXP & 64) { rowmax = pk_max(rowmax, Hc[k] ^ E ^ Q); continue; }
             int h;
-            if constexpr (MAX3) h = pk_max3(Hc[k], E, Q);
-            else {
-                h = pk_max(Hc[k], E);
-                if (CVX) h = pk_max(h, Q);
+            if constexpr (QDOM) {
+                // the long piece at column k of the strip: the carry, k extensions on (each from Q itself: no chain)
+                const int Qr = k ? P16_DEC(Q, (unsigned)k * Cm, pk2(k * c, k * c)) : Q;
+                if constexpr (MAX3) h = pk_max3(Hc[k], E, Qr);   // (>= the bias: E is)
+                else h = pk_max(pk_max(pk_max(Hc[k], E), Qr), NWF2);
+            } else {
+                if constexpr (MAX3) h = pk_max3(Hc[k], E, Q);
+                else {
+                    h = pk_max(Hc[k], E);
+                    if (CVX) h = pk_max(h, Q);
+                }
+                h = pk_max(h, SW ? B2 : NWF2);   // (local: 0; global: P16_NWFLOOR)
             }
-            h = pk_max(h, SW ? B2 : NWF2);   // (local: 0; global: P16_NWFLOOR)
             Hc[k] = h;
             if constexpr (W >= 12 || !SW) rowmax = pk_max(rowmax, h);
-            E = pk_max(P16_DEC(h, Gm, G2), P16_DEC(E, Em, E2));
-            if (CVX) Q = pk_max(P16_DEC(h, Qm, Q2), P16_DEC(Q, Cm, C2));
+            if constexpr (MAX3) E = pk_max3(P16_DEC(h, Gm, G2), P16_DEC(E, Em, E2), B2);
+            else E = pk_max(P16_DEC(h, Gm, G2), P16_DEC(E, Em, E2));
+            if constexpr (!QDOM) { if (CVX) Q = pk_max(P16_DEC(h, Qm, Q2), P16_DEC(Q, Cm, C2)); }
             // (round 6: no register pin behind a column below W = 12.  The empty asm made the hazard recogniser pad every column
             //  with three s_nop and kept the compiler from reusing h + g and h + q -- computed here for E and Q -- as the opening
             //  halves of the row's outgoing candidates: 15 + 21 VALU instructions and 18 s_nop per row of the W = 11 headline
             //  class, 124 VGPRs instead of 120, no scratch.  The 16-wave classes W = 12, 13 spill without it.)
-            if constexpr (W >= 12) SXG_PIN("+v"(Hc[k]), "+v"(E), "+v"(Q), "+v"(rowmax));
+            // (round 18, QDOM: there is no Q update to share h + q with; the outgoing candidates below form it themselves)
+            if constexpr (W >= 12) {
+                if constexpr (QDOM) SXG_PIN("+v"(Hc[k]), "+v"(E), "+v"(rowmax));
+                else SXG_PIN("+v"(Hc[k]), "+v"(E), "+v"(Q), "+v"(rowmax));
+            }
         }
         if constexpr (W < 12 && SW) {
             // (round 6) the row's greatest H as a TREE over the columns: accumulated column by column the compiler sank the chain of
@@ -137,14 +160,14 @@
         // hand my last column to the right neighbour: my hi strip begins where my own lo strip ends, my lo strip where the hi
         // strip of the lane before me ends (lane 0: what came in through the mailbox) -- a lane shift and one v_alignbit;
         // lane 63's hi strip is the wave's right edge -- E, Q after its last column and its H go into the next wave's mailbox
-        // of this row
+        // of this row (QDOM: Q after the last column is mbq, formed in front of pass 2)
         const int xh = Hc[W - 1];
         const int lh = (int)__builtin_amdgcn_alignbit((unsigned)xh, (unsigned)sxg_wave_shr1(xh, in_h << 16), 16);
         RP_MARK(3);  // carry combine + pass 2
         if (wv + 1 < NW && !(EXP & 16)) {
             if ((i & (P16_MBOX / 2 - 1)) == 0)   // the slots of the next P16_MBOX / 2 rows: has my reader freed them?
                 while (__builtin_amdgcn_readfirstlane(prog[wv + 1]) < i - P16_MBOX / 2) __builtin_amdgcn_s_sleep(2);
-            if (lane == 63) mb_out[i & (P16_MBOX - 1)] = i32x4{pk_hi(E), pk_hi(Q), pk_hi(xh), i};
+            if (lane == 63) mb_out[i & (P16_MBOX - 1)] = i32x4{pk_hi(E), QDOM ? mbq : pk_hi(Q), pk_hi(xh), i};
         }
         RP_MARK(4);  // waiting for the right neighbour's progress
 

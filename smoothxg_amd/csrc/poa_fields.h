@@ -1,6 +1,7 @@
 // poa_fields.h -- the 16-bit fields of the packed sweep's LOCAL classes: the bias, what the host admits, and the range the
 // fields therefore stay in.  Plain C++17, constexpr, no HIP: included by the sweep (poa_dp16.hip.h), by the host's admission
-// test (sxg_poa.hip: p16_safe) and by the host-only check of the range (tests/csrc/field_range_check.cpp).
+// test (sxg_poa.hip: p16_safe) and by the host-only checks of the range (tests/csrc/field_range_check.cpp) and of the strip
+// form of the long gap piece (tests/csrc/strip_gap_check.cpp).
 //
 // Nothing here is checked at run time: the static_asserts below ARE the argument.
 #pragma once
@@ -40,12 +41,16 @@ constexpr int p16_abs(int v) { return v < 0 ? -v : v; }
 constexpr int p16_top_field(int e, int c, int W) {
     return P16_BIAS + P16_LOCAL_LIMIT - 1 + (W - 1) * (p16_abs(e) > p16_abs(c) ? p16_abs(e) : p16_abs(c));
 }
-// The least: "minus infinity" plus one mismatch or one opening (the diagonal / a gap state out of a floor cell).
-constexpr int p16_bottom_field(int n, int g, int q) {
-    return P16_FLOOR - (p16_abs(n) > p16_abs(g) ? (p16_abs(n) > p16_abs(q) ? p16_abs(n) : p16_abs(q)) : (p16_abs(g) > p16_abs(q) ? p16_abs(g) : p16_abs(q)));
+// The least: "minus infinity" plus one mismatch or one opening (the diagonal / a gap state out of a floor cell) -- or, in the
+// classes that read the long piece inside a strip straight off its carry (p16_strip_q_dominated below), a carry at the floor
+// run to the strip's last column: Qin - (W - 1) |c| >= P16_FLOOR - (W - 1) |c|.
+constexpr int p16_bottom_field(int n, int g, int q, int c = 0, int W = 1) {
+    const int open_ = p16_abs(n) > p16_abs(g) ? (p16_abs(n) > p16_abs(q) ? p16_abs(n) : p16_abs(q)) : (p16_abs(g) > p16_abs(q) ? p16_abs(g) : p16_abs(q));
+    const int run_ = (W - 1) * p16_abs(c);
+    return P16_FLOOR - (open_ > run_ ? open_ : run_);
 }
 constexpr bool p16_fields_are_f16_ordered(int n, int g, int e, int q, int c, int W) {
-    return p16_bottom_field(n, g, q) >= 0 && p16_top_field(e, c, W) <= P16_F16_TOP;
+    return p16_bottom_field(n, g, q, c, W) >= 0 && p16_top_field(e, c, W) <= P16_F16_TOP;
 }
 // The default scores, every strip width up to the widest: the classes compiled for them (DS) may take three-input maxima.
 static_assert(p16_top_field(P16_DEF_E, P16_DEF_C, P16_W_MAX) == 31047, "1024 + 29 999 + 12 * 2");
@@ -53,5 +58,24 @@ static_assert(p16_fields_are_f16_ordered(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DE
 // Not so for every score set the generic local classes admit (|g|, |q| <= 120, |e| <= |g|): (W - 1) * |e| may exceed the
 // 0x7BFF - 31 023 = 720 of headroom there -- they keep the two-input integer maxima.
 static_assert(!p16_fields_are_f16_ordered(-4, -120, -120, -120, -120, P16_W_MAX), "generic score sets are not covered");
+static_assert(p16_bottom_field(P16_DEF_N, P16_DEF_G, P16_DEF_Q, P16_DEF_C, P16_W_MAX) == P16_FLOOR - 26, "the opening (26) is still the deepest: a floor carry run over a strip is 512 - 12");
+
+// ---- the long gap piece inside a strip ------------------------------------------------------------------------------
+// Two-piece gap cost: a gap opened at column j' and read at column j, d = j - j' - 1 columns between them, scores
+// H[j'] + g + d e by the first piece and H[j'] + q + d c by the second.  The first is at least the second while
+// g - q >= d (c - e); inside a strip of W columns d <= W - 2.  Where that holds for every such d, the second piece opened
+// INSIDE a strip never decides a cell of that strip: H[j] = max(Hc[j], E[j], Qin - (j - j_s) |c|) with Qin the carry that
+// entered the strip at its first column j_s, and the per-column update Q = max(h + q, Q + c) is dead inside the strip.
+// What leaves a strip does not come from that update either: the strips' carries are scanned from pass 1's b (H before the
+// in-row gaps), and the word for the next wave is max(Qin - W |c|, b) of the wave's last strip.
+constexpr bool p16_strip_q_dominated(int g, int e, int q, int c, int W) {
+    for (int d = 0; d <= W - 2; ++d)
+        if (g + d * e < q + d * c) return false;
+    return true;
+}
+static_assert(p16_strip_q_dominated(P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, P16_W_MAX), "default scores: 20 >= d for d <= 11");
+static_assert(!p16_strip_q_dominated(P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, 23), "... and no further than d = 20");
+// Not so for every score set the generic classes admit (g = q: the second piece wins from d = 1 on) -- they keep the update.
+static_assert(!p16_strip_q_dominated(-6, -2, -6, -1, 4), "generic score sets are not covered");
 
 }  // namespace sxg
