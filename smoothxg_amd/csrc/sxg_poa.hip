@@ -224,25 +224,7 @@ struct HostLaps {
     }
 };
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return SXG_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            want = bytes;
-            e = hipMalloc(&p, want);
-        }
-        if (e != hipSuccess) { p = nullptr; return fail(SXG_E_NOMEM, "hipMalloc failed for " + std::to_string(bytes) + " bytes"); }
-        cap = want;
-        return SXG_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class Tp> Tp* as() const { return (Tp*)p; }
-};
+#include "poa_devres.h"            // DevBuf, DevEvent, DevStream, OutGuard: every device resource here frees itself (uses fail above)
 
 struct BlockMeta {
     int maxlen = 0, nseq = 0, rm = 0; bool fits = false; Variant variant{16, 1, 256, 0};
@@ -267,10 +249,10 @@ static void classify_block(BlockMeta& m, int at_least, bool clamp_ok) {
     m.variant.DS = m.rm == 2 && cb == 2 && p16_default_scores(m.S) && !getenv("SXG_POA_NO_DEFAULT_CLASS");
 }
 
-struct PlanRes {
+struct PlanRes {   // (members die in reverse order: the buffers before the stream that used them)
+    DevStream stream;
+    DevEvent e0, e1;
     DevBuf arena, work, queue, est;
-    hipStream_t stream = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
 // Pinned host memory for the one big array of a download (the block graphs' step lists: 1.3 GB on the headline batch).  A
@@ -301,10 +283,12 @@ struct PinPool {
     ~PinPool() { for (auto& b : bufs) (void)hipHostFree(b.p); }
 };
 struct sxg_poa_handle {
-    std::vector<PlanRes*> planres;
+    // Every device resource of the handle is a member that frees itself (poa_devres.h): `delete h`, with h->device current, is the
+    // whole teardown.  The stream and the events stand first: members die in reverse order, the buffers before their stream.
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DevStream stream;
+    DevEvent ev0, ev1;
+    std::vector<std::unique_ptr<PlanRes>> planres;   // per launch of a round: stream, events, arena (kept between executes)
     int num_cu = 256;
     uint64_t mem_budget = 0;
     int budget_share = 1;   // members of a device group on this handle's device: the default arena cap is divided among them
@@ -412,20 +396,20 @@ extern "C" int sxg_poa_measure_copy(sxg_poa_handle* h, uint64_t bytes, int reps,
     if (int rc = a.ensure(n16 * 16)) return rc;
     if (int rc = b.ensure(n16 * 16)) return rc;
     HIPCHK(hipMemsetAsync(a.p, 1, n16 * 16, h->stream));
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    DevEvent e0, e1;
+    HIPCHK(e0.create()); HIPCHK(e1.create());
     const int grid = std::max(h->num_cu, 1) * 16;
     reps = std::max(reps, 1);
     hipLaunchKernelGGL(sxg_copy_kernel, dim3((unsigned)grid), dim3(256), 0, h->stream, a.as<u32x4>(), b.as<u32x4>(), n16);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e0, h->stream));
     for (int r = 0; r < reps; ++r)
         hipLaunchKernelGGL(sxg_copy_kernel, dim3((unsigned)grid), dim3(256), 0, h->stream, a.as<u32x4>(), b.as<u32x4>(), n16);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(e1, h->stream));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    a.release(); b.release();
     if (ms > 0) *gbps = 2.0 * (double)(n16 * 16) * reps / ((double)ms * 1e-3) / 1e9;
     return SXG_OK;
 }
@@ -455,48 +439,25 @@ extern "C" int sxg_poa_create(int device, sxg_poa_handle** out) {
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail(SXG_E_NODEVICE, "no HIP device available");
     if (device < 0 || device >= n) return fail(SXG_E_INVALID, "device index out of range");
     HIPCHK(hipSetDevice(device));
-    sxg_poa_handle* h = new sxg_poa_handle();
+    auto h = std::make_unique<sxg_poa_handle>();   // (freed on every early return below)
     h->device = device;
     h->pins = std::make_shared<PinPool>();
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     h->num_cu = prop.multiProcessorCount;
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&h->ev0));
-    HIPCHK(hipEventCreate(&h->ev1));
-    *out = h;
+    HIPCHK(h->stream.create(hipStreamNonBlocking));
+    HIPCHK(h->ev0.create());
+    HIPCHK(h->ev1.create());
+    *out = h.release();
     return SXG_OK;
-}
-
-static void release_all(sxg_poa_handle* h) {
-    DevBuf* bufs[] = {&h->d_blk_off, &h->d_seq_off, &h->d_bases, &h->d_weights, &h->d_params, &h->d_status, &h->d_nn,
-                      &h->d_ne, &h->d_nc, &h->d_node_code, &h->d_node_rank, &h->d_node_group, &h->d_edge_tail,
-                      &h->d_edge_head, &h->d_edge_w, &h->d_paths, &h->d_score, &h->d_cells, &h->d_cons, &h->d_work,
-                      &h->d_queue, &h->d_arena, &h->d_blk_cycles, &h->d_tmp_a, &h->d_tmp_b, &h->d_tmp_c, &h->d_tmp_d, &h->d_board, &h->d_est_done, &h->d_trim, &h->d_bg_no, &h->d_bg_eo,
-                      &h->d_bg_len, &h->d_bg_od, &h->d_bg_id, &h->d_bg_seq, &h->d_bg_eto, &h->d_bg_steps, &h->d_bg_nsteps, &h->d_bg_cons,
-                      &h->d_bg_counts, &h->d_bg_work, &h->d_bg_queue, &h->d_bg_arena,
-                      &h->d_msa_no, &h->d_msa_tmp, &h->d_msa_col, &h->d_msa_be, &h->d_msa_off, &h->d_msa_items, &h->d_msa_work, &h->d_msa_queue, &h->d_msa};
-    for (DevBuf* b : bufs) b->release();
 }
 
 extern "C" void sxg_poa_comm_destroy(sxg_poa_handle* h);
 extern "C" void sxg_poa_destroy(sxg_poa_handle* h) {
     if (!h) return;
     if (h->pin_thread.joinable()) h->pin_thread.join();
-    (void)hipSetDevice(h->device);
+    (void)hipSetDevice(h->device);   // (a group holds handles of several devices: the members below free on this one)
     sxg_poa_comm_destroy(h);
-    h->d_blob.release(); h->d_recv.release(); h->d_counts.release();
-    release_all(h);
-    for (PlanRes* r : h->planres) {
-        r->arena.release(); r->work.release(); r->queue.release(); r->est.release();
-        if (r->e0) (void)hipEventDestroy(r->e0);
-        if (r->e1) (void)hipEventDestroy(r->e1);
-        if (r->stream) (void)hipStreamDestroy(r->stream);
-        delete r;
-    }
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -534,7 +495,7 @@ static uint64_t arena_budget(sxg_poa_handle* h) {
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) return 8ull << 30;
     uint64_t avail = (uint64_t)fr + h->d_arena.cap;  // the arenas we already hold can be reused
-    for (PlanRes* r : h->planres) avail += r->arena.cap;
+    for (const auto& r : h->planres) avail += r->arena.cap;
     uint64_t b = avail / 4 * 3 / (uint64_t)std::max(h->budget_share, 1);
     if (h->mem_budget && h->mem_budget < b) b = h->mem_budget;
     return b;
@@ -1250,11 +1211,11 @@ static void size_slots(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, const 
 // launches the round, waits for it, and collects its times and statistics
 static int launch_round(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, const int attempt, const bool dbg, float& ms_total) {
     while (h->planres.size() < plans.size()) {
-        PlanRes* r = new PlanRes();
-        HIPCHK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreate(&r->e0));
-        HIPCHK(hipEventCreate(&r->e1));
-        h->planres.push_back(r);
+        auto r = std::make_unique<PlanRes>();
+        HIPCHK(r->stream.create(hipStreamNonBlocking));
+        HIPCHK(r->e0.create());
+        HIPCHK(r->e1.create());
+        h->planres.push_back(std::move(r));
     }
     {
         const size_t board_bytes = (size_t)PRIO_BOARD_CUS * PRIO_BOARD_SLOTS * 4;
@@ -1613,18 +1574,18 @@ extern "C" int sxg_poa_batch_download(sxg_poa_handle* h, sxg_poa_batch_out* out)
     OutOwner* o = new OutOwner();
     out->_owner = o;
     out->n_blocks = nb; out->n_seqs = h->n_seqs;
-    auto bail = [&](int code) { sxg_poa_batch_free(out); return code; };
+    OutGuard<sxg_poa_batch_out, sxg_poa_batch_free> guard(out);   // (every return below but the last frees the result)
     auto hip = [&](hipError_t e, const char* what) { return e == hipSuccess ? SXG_OK : fail(SXG_E_NODEVICE, std::string(what) + ": " + hipGetErrorString(e)); };
     DenseLayout D;
     int rc = dense_layout(h, D);
-    if (rc) return bail(rc);
+    if (rc) return rc;
     for (int a = 0; a < sxg::N_RESULT_FAMILIES; ++a) {
         const sxg::ResultFamily& A = sxg::RESULT_FAMILIES[a];
         if (a == sxg::RF_MSA) laps.lap("download: POA graphs");
         if (a == sxg::RF_BG_NODE) laps.lap("download: MSA rows");
         if (!present(h, FAMILY_SRC[a].when)) continue;
         int64_t* off = (int64_t*)o->alloc(8 * D.off[a].size());
-        if (!off) return bail(fail(SXG_E_NOMEM, "host allocation of the result failed"));
+        if (!off) return fail(SXG_E_NOMEM, "host allocation of the result failed");
         memcpy(off, D.off[a].data(), 8 * D.off[a].size());
         sxg::set_field(*out, A.off_field, off);
         const size_t total = (size_t)D.off[a].back();
@@ -1637,18 +1598,18 @@ extern "C" int sxg_poa_batch_download(sxg_poa_handle* h, sxg_poa_batch_out* out)
                 if (h->pin_thread.joinable()) h->pin_thread.join();
                 if (total >= ((size_t)16 << 20) && h->pins && !getenv("SXG_POA_NO_PINNED") && (dst = h->pins->acquire(elem * total))) { o->pin_pool = h->pins; o->pinned = dst; }
             }
-            if (!dst && !(dst = o->alloc(elem * total))) return bail(fail(SXG_E_NOMEM, "host allocation of the result failed"));
+            if (!dst && !(dst = o->alloc(elem * total))) return fail(SXG_E_NOMEM, "host allocation of the result failed");
             sxg::set_field(*out, A.pay[p].field, dst);
             if (!total) continue;
             const DevBuf& src = h->*S.buf;
             if (S.src == SRC_DENSE) {   // (the rows of the trimmed MSA, as the device wrote them)
-                if ((rc = hip(hipMemcpy(dst, src.p, elem * total, hipMemcpyDeviceToHost), "download of the MSA rows"))) return bail(rc);
+                if ((rc = hip(hipMemcpy(dst, src.p, elem * total, hipMemcpyDeviceToHost), "download of the MSA rows"))) return rc;
                 continue;
             }
             if ((rc = h->d_tmp_c.ensure(elem * total)) || (rc = gather(h, D, S.src, a, src, elem, h->d_tmp_c.p, h->d_tmp_c.cap)) ||
                 (rc = hip(hipMemcpyAsync(dst, h->d_tmp_c.p, elem * total, hipMemcpyDeviceToHost, h->stream), "download of a gathered array")) ||
                 (rc = hip(hipStreamSynchronize(h->stream), "download of a gathered array")))
-                return bail(rc);
+                return rc;
         }
     }
     laps.lap("download: block graphs");
@@ -1657,19 +1618,20 @@ extern "C" int sxg_poa_batch_download(sxg_poa_handle* h, sxg_poa_batch_out* out)
         if (!present(h, FLAT_SRC[f].when)) continue;
         const size_t bytes = F.elem * (size_t)(F.index == 0 ? nb : F.index == 1 ? h->n_seqs : h->n_bases);
         void* dst = o->alloc(bytes);   // (seq_path_nodes, one node id per base, is the big one: 1.3 GB on the headline batch, one straight copy)
-        if (!dst) return bail(fail(SXG_E_NOMEM, "host allocation of the result failed"));
+        if (!dst) return fail(SXG_E_NOMEM, "host allocation of the result failed");
         sxg::set_field(*out, F.field, dst);
         if (!bytes) continue;
         if (!FLAT_SRC[f].buf) memcpy(dst, h->msa_cols_h.data(), std::min(bytes, 4 * h->msa_cols_h.size()));
-        else if ((rc = hip(hipMemcpy(dst, (h->*FLAT_SRC[f].buf).p, bytes, hipMemcpyDeviceToHost), "download of a flat array"))) return bail(rc);
+        else if ((rc = hip(hipMemcpy(dst, (h->*FLAT_SRC[f].buf).p, bytes, hipMemcpyDeviceToHost), "download of a flat array"))) return rc;
     }
     laps.lap("download: paths");   // (and the small per-block and per-sequence arrays)
     if (h->want_msa && h->want_msa != SXG_MSA_TRIMMED && out->seq_path_nodes) {
         const sxg::BatchShape S{nb, h->h_blk_off.data(), h->h_seq_off.data()};
         if (!sxg::format_full_msa(S, h->want_consensus != 0, [o](size_t bytes) { return o->alloc(bytes); }, out))
-            return bail(fail(SXG_E_NOMEM, "host allocation of the MSA failed"));
+            return fail(SXG_E_NOMEM, "host allocation of the MSA failed");
         laps.lap("download: full MSA");
     }
+    guard.dismiss();
     return SXG_OK;
 }
 
@@ -2499,39 +2461,34 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
     AlignOwner* o = new AlignOwner();
     out->_owner = o; out->n = n;
     o->status.assign(std::max(n, 1), 0); o->score.assign(std::max(n, 1), 0); o->pair_off.assign(n + 1, 0);
+    OutGuard<sxg_poa_align_out, sxg_poa_align_free> guard(out);   // (every return below but those after dismiss() frees the result)
     DevBuf d_row_off, d_code, d_sink, d_pred_off, d_preds, d_seq_off, d_bases, d_params, d_status, d_score, d_np, d_pr, d_pp, d_work,
         d_queue, d_arena;
-    auto cleanup = [&]() {
-        DevBuf* bs[] = {&d_row_off, &d_code, &d_sink, &d_pred_off, &d_preds, &d_seq_off, &d_bases, &d_params, &d_status, &d_score,
-                        &d_np, &d_pr, &d_pp, &d_work, &d_queue, &d_arena};
-        for (DevBuf* b : bs) b->release();
-    };
-#define CK(x) do { int _rc = (x); if (_rc) { cleanup(); sxg_poa_align_free(out); return _rc; } } while (0)
-#define HCK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { cleanup(); sxg_poa_align_free(out); return fail(SXG_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); } } while (0)
+    int rc;
     const int np = in->per_problem_params ? n : 1;
     std::vector<uint8_t> stage((size_t)std::max<int64_t>(nbases, 1));
     for (int64_t i = 0; i < nbases; ++i) stage[i] = in->bases[i] > 4 ? 4 : in->bases[i];
     std::vector<uint8_t> codes((size_t)std::max<int64_t>(rows, 1));
     for (int64_t i = 0; i < rows; ++i) codes[i] = in->row_code[i] > 4 ? 4 : in->row_code[i];
     const size_t outcap = (size_t)(rows + nbases + 1);
-    CK(d_row_off.ensure(8 * (size_t)(n + 1))); CK(d_code.ensure((size_t)rows + 16)); CK(d_sink.ensure((size_t)rows + 16));
-    CK(d_pred_off.ensure(8 * (size_t)(rows + 1))); CK(d_preds.ensure(4 * (size_t)(ne + 1))); CK(d_seq_off.ensure(8 * (size_t)(n + 1)));
-    CK(d_bases.ensure((size_t)nbases + 16)); CK(d_params.ensure(sizeof(sxg_poa_params) * (size_t)std::max(np, 1)));
-    CK(d_status.ensure(4 * (size_t)std::max(n, 1))); CK(d_score.ensure(4 * (size_t)std::max(n, 1))); CK(d_np.ensure(4 * (size_t)std::max(n, 1)));
-    CK(d_pr.ensure(4 * outcap)); CK(d_pp.ensure(4 * outcap)); CK(d_work.ensure(4 * (size_t)std::max(n, 1))); CK(d_queue.ensure(256));
+    if ((rc = d_row_off.ensure(8 * (size_t)(n + 1))) || (rc = d_code.ensure((size_t)rows + 16)) || (rc = d_sink.ensure((size_t)rows + 16)) ||
+        (rc = d_pred_off.ensure(8 * (size_t)(rows + 1))) || (rc = d_preds.ensure(4 * (size_t)(ne + 1))) || (rc = d_seq_off.ensure(8 * (size_t)(n + 1))) ||
+        (rc = d_bases.ensure((size_t)nbases + 16)) || (rc = d_params.ensure(sizeof(sxg_poa_params) * (size_t)std::max(np, 1))) ||
+        (rc = d_status.ensure(4 * (size_t)std::max(n, 1))) || (rc = d_score.ensure(4 * (size_t)std::max(n, 1))) || (rc = d_np.ensure(4 * (size_t)std::max(n, 1))) ||
+        (rc = d_pr.ensure(4 * outcap)) || (rc = d_pp.ensure(4 * outcap)) || (rc = d_work.ensure(4 * (size_t)std::max(n, 1))) || (rc = d_queue.ensure(256)))
+        return rc;
     if (n) {
-        HCK(hipMemcpy(d_row_off.p, in->row_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice));
-        HCK(hipMemcpy(d_seq_off.p, in->seq_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice));
-        HCK(hipMemcpy(d_pred_off.p, in->pred_off, 8 * (size_t)(rows + 1), hipMemcpyHostToDevice));
-        HCK(hipMemcpy(d_params.p, in->params, sizeof(sxg_poa_params) * (size_t)np, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_row_off.p, in->row_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_seq_off.p, in->seq_off, 8 * (size_t)(n + 1), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_pred_off.p, in->pred_off, 8 * (size_t)(rows + 1), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_params.p, in->params, sizeof(sxg_poa_params) * (size_t)np, hipMemcpyHostToDevice));
         if (rows) {
-            HCK(hipMemcpy(d_code.p, codes.data(), (size_t)rows, hipMemcpyHostToDevice));
-            HCK(hipMemcpy(d_sink.p, in->row_sink, (size_t)rows, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_code.p, codes.data(), (size_t)rows, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_sink.p, in->row_sink, (size_t)rows, hipMemcpyHostToDevice));
         }
-        if (ne) HCK(hipMemcpy(d_preds.p, in->preds, 4 * (size_t)ne, hipMemcpyHostToDevice));
-        if (nbases) HCK(hipMemcpy(d_bases.p, stage.data(), (size_t)nbases, hipMemcpyHostToDevice));
-        HCK(hipMemset(d_status.p, 0, 4 * (size_t)n)); HCK(hipMemset(d_score.p, 0, 4 * (size_t)n)); HCK(hipMemset(d_np.p, 0, 4 * (size_t)n));
-
+        if (ne) HIPCHK(hipMemcpy(d_preds.p, in->preds, 4 * (size_t)ne, hipMemcpyHostToDevice));
+        if (nbases) HIPCHK(hipMemcpy(d_bases.p, stage.data(), (size_t)nbases, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_status.p, 0, 4 * (size_t)n)); HIPCHK(hipMemset(d_score.p, 0, 4 * (size_t)n)); HIPCHK(hipMemset(d_np.p, 0, 4 * (size_t)n));
     }
     // plans (the statistics of an align batch: launches, kernel time and the geometry of the plan with the most work)
     h->stats = sxg_poa_stats{};
@@ -2555,7 +2512,7 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         pl->work.push_back(p);
         pl->rows_cap = std::max(pl->rows_cap, N);
     }
-    if (n) HCK(hipMemcpy(d_status.p, o->status.data(), 4 * (size_t)n, hipMemcpyHostToDevice));
+    if (n) HIPCHK(hipMemcpy(d_status.p, o->status.data(), 4 * (size_t)n, hipMemcpyHostToDevice));
     for (auto& pl : plans) {
         const Variant V = pl.variant;
         const int rows_cap = pl.rows_cap + 1;
@@ -2568,7 +2525,7 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         if (V.RM == 2) lay2.lds_rows = p16_lds_rows(V.T(), V.W, 4);   // (the align-only kernel runs the 4-byte cells)
         auto kern = align_kernel(pl.variant, pl.cvx, pl.sw);
         const int tfix = class_traits(V.TMAX, V.W, V.RM, V.CB).tfix;
-        if (!kern || (tfix && tfix != V.T())) { cleanup(); sxg_poa_align_free(out); return fail(SXG_E_INVALID, kern ? "kernel class compiled for another thread count" : "no kernel class built for this geometry"); }
+        if (!kern || (tfix && tfix != V.T())) return fail(SXG_E_INVALID, kern ? "kernel class compiled for another thread count" : "no kernel class built for this geometry");
         int per_cu = 1;
         int smem = V.RM == 2 ? dp16_lds_bytes(V.T(), V.W, lay2.lds_rows, 4) : dp_lds_launch_bytes(V.Lpad(), wb);
         const int pf_off = (V.RM != 2 && getenv("SXG_POA_PREFETCH")) ? dp_pf_offset(V.Lpad(), wb, V.T()) : -1;
@@ -2578,10 +2535,10 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         const uint64_t budget = arena_budget(h);
         int64_t n_slots = std::min<int64_t>((int64_t)pl.work.size(), (int64_t)h->num_cu * per_cu);
         n_slots = std::min<int64_t>(n_slots, (int64_t)(budget / lay2.total));
-        if (n_slots < 1) { cleanup(); sxg_poa_align_free(out); return fail(SXG_E_NOMEM, "memory budget too small for one alignment arena"); }
-        CK(d_arena.ensure((size_t)n_slots * lay2.total));
-        HCK(hipMemcpy(d_work.p, pl.work.data(), 4 * pl.work.size(), hipMemcpyHostToDevice));
-        HCK(hipMemset(d_queue.p, 0, 4));
+        if (n_slots < 1) return fail(SXG_E_NOMEM, "memory budget too small for one alignment arena");
+        if ((rc = d_arena.ensure((size_t)n_slots * lay2.total))) return rc;
+        HIPCHK(hipMemcpy(d_work.p, pl.work.data(), 4 * pl.work.size(), hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_queue.p, 0, 4));
         AlignArgs A;
         A.row_off = d_row_off.as<int64_t>(); A.row_code = d_code.as<uint8_t>(); A.row_sink = d_sink.as<uint8_t>();
         A.pred_off = d_pred_off.as<int64_t>(); A.preds = d_preds.as<int32_t>(); A.seq_off = d_seq_off.as<int64_t>();
@@ -2593,13 +2550,13 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         A.park_in_lds = (V.RM == 2 || dp_park_in_lds(V.Lpad(), wb)) ? 1 : 0;
         A.pf_off = pf_off;
         A.num_cu = std::max(h->num_cu, 1);
-        HCK(hipEventRecord(h->ev0, h->stream));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
         hipLaunchKernelGGL(kern, dim3((unsigned)n_slots), dim3(V.T()), (size_t)smem, h->stream, A);
-        HCK(hipGetLastError());
-        HCK(hipEventRecord(h->ev1, h->stream));
-        HCK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
         float ms = 0;
-        HCK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
         double work = 0;   // rows x letters of the plan's problems
         for (int p : pl.work) work += (double)(in->row_off[p + 1] - in->row_off[p]) * (double)(in->seq_off[p + 1] - in->seq_off[p]);
         h->stats.dp_launches += 1;
@@ -2617,11 +2574,11 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
     }
     std::vector<int32_t> npairs(std::max(n, 1), 0), pr(outcap), pp(outcap);
     if (n) {
-        HCK(hipMemcpy(o->status.data(), d_status.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
-        HCK(hipMemcpy(o->score.data(), d_score.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
-        HCK(hipMemcpy(npairs.data(), d_np.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
-        HCK(hipMemcpy(pr.data(), d_pr.p, 4 * outcap, hipMemcpyDeviceToHost));
-        HCK(hipMemcpy(pp.data(), d_pp.p, 4 * outcap, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o->status.data(), d_status.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o->score.data(), d_score.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(npairs.data(), d_np.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pr.data(), d_pr.p, 4 * outcap, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pp.data(), d_pp.p, 4 * outcap, hipMemcpyDeviceToHost));
     }
     for (int p = 0; p < n; ++p) o->pair_off[p + 1] = o->pair_off[p] + npairs[p];
     o->pair_row.resize((size_t)std::max<int64_t>(o->pair_off[n], 1)); o->pair_pos.resize(o->pair_row.size());
@@ -2630,9 +2587,7 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
         std::copy(pr.begin() + s0, pr.begin() + s0 + npairs[p], o->pair_row.begin() + o->pair_off[p]);
         std::copy(pp.begin() + s0, pp.begin() + s0 + npairs[p], o->pair_pos.begin() + o->pair_off[p]);
     }
-    cleanup();
-#undef CK
-#undef HCK
+    guard.dismiss();   // (the caller keeps the result, also when a problem failed: SXG_E_BLOCK below)
     out->status = o->status.data(); out->score = o->score.data(); out->pair_off = o->pair_off.data();
     out->pair_row = o->pair_row.data(); out->pair_pos = o->pair_pos.data();
     for (int p = 0; p < n; ++p)
@@ -2646,26 +2601,23 @@ extern "C" int sxg_poa_align_batch(sxg_poa_handle* h, const sxg_poa_align_in* in
 static_assert(SXG_POA_SPLIT_PANEL == SXG_SPLIT_PANEL, "panel width of the header");
 static_assert(SXG_POA_MASH_SORT_TILE == SXG_MASH_SORT_TILE, "sort tile of the header");
 namespace {
-struct SplitBufs {
-    DevBuf seq_off, bases, a, b, c, d, e, f, g, hh, work, queue, bound, lists;
-    DevBuf sets, set_size, sort_scratch, sketch_work, sketch_queue, min_len, mash_f, mash_jmin, n_mash;   // the mash-based branch
-    ~SplitBufs() {
-        DevBuf* bs[] = {&seq_off, &bases, &a, &b, &c, &d, &e, &f, &g, &hh, &work, &queue, &bound, &lists,
-                        &sets, &set_size, &sort_scratch, &sketch_work, &sketch_queue, &min_len, &mash_f, &mash_jmin, &n_mash};
-        for (DevBuf* x : bs) x->release();
-    }
-};
+struct MashSets { DevBuf seq_off, bases, sets, set_size, sort_scratch, sketch_work, sketch_queue; };   // a call's uploaded sequences and, where it sketches them (mash_sketch), their k-mer sets
+// kernel time of a call: the launches between the two on the handle's stream, by the handle's two events (timer_stop waits for them)
+int timer_start(sxg_poa_handle* h) { HIPCHK(hipEventRecord(h->ev0, h->stream)); return SXG_OK; }
+int timer_stop(sxg_poa_handle* h, float* ms) {
+    HIPCHK(hipEventRecord(h->ev1, h->stream)); HIPCHK(hipEventSynchronize(h->ev1));
+    HIPCHK(hipEventElapsedTime(ms, h->ev0, h->ev1));
+    return SXG_OK;
+}
 // slots of a split launch: what fits the chip, the work and the budget (one slot = one wavefront with its boundary column)
-int split_slots(sxg_poa_handle* h, int which, int64_t n_work, size_t slot_bytes, int64_t* n_slots) {
-    int per_cu = 1;
-    sxg_split_occupancy(which, &per_cu);
+int split_slots(sxg_poa_handle* h, int per_cu, int64_t n_work, size_t slot_bytes, int64_t* n_slots) {
     int64_t n = std::min<int64_t>(n_work, (int64_t)std::max(h->num_cu, 1) * per_cu);
     n = std::min<int64_t>(n, (int64_t)(arena_budget(h) / std::max<size_t>(slot_bytes, 1)));
     if (n < 1) return fail(SXG_E_NOMEM, "memory budget too small for one split slot");
     *n_slots = n;
     return SXG_OK;
 }
-int split_upload_seqs(sxg_poa_handle* h, SplitBufs& B, int64_t n_seqs, const int64_t* seq_off, const uint8_t* bases) {
+int split_upload_seqs(sxg_poa_handle* h, MashSets& B, int64_t n_seqs, const int64_t* seq_off, const uint8_t* bases) {
     const int64_t nbases = seq_off[n_seqs];
     std::vector<uint8_t> stage((size_t)std::max<int64_t>(nbases, 1));
     for (int64_t i = 0; i < nbases; ++i) stage[(size_t)i] = bases[i] > 4 ? 4 : bases[i];
@@ -2683,7 +2635,7 @@ template <class Tp> int split_up(sxg_poa_handle* h, DevBuf& d, const Tp* src, si
 }
 // M1 on the device: the sets of the sequences in `work` (made longest first here) into B.sets / B.set_size, every other sequence
 // with size 0.  B.seq_off / B.bases are uploaded; the launch goes on the handle's stream; *dev_bytes: sets and sort scratch.
-int mash_sketch(sxg_poa_handle* h, SplitBufs& B, int64_t ns, const int64_t* seq_off, std::vector<int32_t>& work, int k, bool clear_sets, size_t* dev_bytes) {
+int mash_sketch(sxg_poa_handle* h, MashSets& B, int64_t ns, const int64_t* seq_off, std::vector<int32_t>& work, int k, bool clear_sets, size_t* dev_bytes) {
     const int64_t nbases = seq_off[ns];
     if (int rc = B.sets.ensure(8 * (size_t)std::max<int64_t>(nbases, 1))) return rc;
     if (int rc = B.set_size.ensure(4 * (size_t)std::max<int64_t>(ns, 1))) return rc;
@@ -2753,39 +2705,35 @@ extern "C" int sxg_poa_pair_identity_batch(sxg_poa_handle* h, int64_t n_seqs, co
     for (int64_t k = 0; k < n_pairs; ++k) work[(size_t)k] = cost[(size_t)k].second;
     std::vector<uint8_t> rev((size_t)n_pairs, 0);
     if (b_rev) for (int64_t k = 0; k < n_pairs; ++k) rev[(size_t)k] = b_rev[k] ? 1 : 0;
-    SplitBufs B;
-    if (int rc = split_upload_seqs(h, B, n_seqs, seq_off, bases)) return rc;
-    if (int rc = split_up(h, B.a, pair_a, (size_t)n_pairs)) return rc;
-    if (int rc = split_up(h, B.b, pair_b, (size_t)n_pairs)) return rc;
-    if (int rc = split_up(h, B.c, rev.data(), (size_t)n_pairs)) return rc;
-    if (int rc = split_up(h, B.d, cap, (size_t)n_pairs)) return rc;
-    if (int rc = split_up(h, B.work, work.data(), (size_t)n_pairs)) return rc;
-    if (int rc = B.e.ensure(4 * (size_t)n_pairs)) return rc;
-    if (int rc = B.f.ensure(4 * (size_t)n_pairs)) return rc;
-    if (int rc = B.g.ensure(4 * (size_t)n_pairs)) return rc;
-    if (int rc = B.queue.ensure(256)) return rc;
+    MashSets seqs;   // (the sequences only: this call sketches nothing)
+    DevBuf d_pair_a, d_pair_b, d_rev, d_cap, d_work, d_queue, d_bound, d_penalty, d_cols, d_matches;
+    int rc;
+    if ((rc = split_upload_seqs(h, seqs, n_seqs, seq_off, bases)) || (rc = split_up(h, d_pair_a, pair_a, (size_t)n_pairs)) ||
+        (rc = split_up(h, d_pair_b, pair_b, (size_t)n_pairs)) || (rc = split_up(h, d_rev, rev.data(), (size_t)n_pairs)) ||
+        (rc = split_up(h, d_cap, cap, (size_t)n_pairs)) || (rc = split_up(h, d_work, work.data(), (size_t)n_pairs)) ||
+        (rc = d_penalty.ensure(4 * (size_t)n_pairs)) || (rc = d_cols.ensure(4 * (size_t)n_pairs)) || (rc = d_matches.ensure(4 * (size_t)n_pairs)) || (rc = d_queue.ensure(256)))
+        return rc;
     const int64_t bound_rows = max_la + 1;
     const size_t slot_bytes = 3 * sizeof(sxg_key_t) * (size_t)bound_rows;
     int64_t n_slots = 0;
-    if (int rc = split_slots(h, 0, n_pairs, slot_bytes, &n_slots)) return rc;
-    if (int rc = B.bound.ensure(slot_bytes * (size_t)n_slots)) return rc;
-    HIPCHK(hipMemsetAsync(B.queue.p, 0, 4, h->stream));
+    int per_cu = 1;
+    sxg_split_occupancy(0, &per_cu);
+    if ((rc = split_slots(h, per_cu, n_pairs, slot_bytes, &n_slots)) || (rc = d_bound.ensure(slot_bytes * (size_t)n_slots))) return rc;
+    HIPCHK(hipMemsetAsync(d_queue.p, 0, 4, h->stream));
     SplitPairArgs A;
-    A.seq_off = B.seq_off.as<int64_t>(); A.bases = B.bases.as<uint8_t>(); A.pair_a = B.a.as<int32_t>(); A.pair_b = B.b.as<int32_t>();
-    A.b_rev = B.c.as<uint8_t>(); A.cap = B.d.as<int32_t>(); A.work = B.work.as<int32_t>(); A.n_work = (int32_t)n_pairs;
-    A.queue = B.queue.as<int32_t>(); A.bound = B.bound.as<sxg_key_t>(); A.bound_rows = bound_rows;
-    A.penalty = B.e.as<int32_t>(); A.cols = B.f.as<int32_t>(); A.matches = B.g.as<int32_t>();
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    A.seq_off = seqs.seq_off.as<int64_t>(); A.bases = seqs.bases.as<uint8_t>(); A.pair_a = d_pair_a.as<int32_t>(); A.pair_b = d_pair_b.as<int32_t>();
+    A.b_rev = d_rev.as<uint8_t>(); A.cap = d_cap.as<int32_t>(); A.work = d_work.as<int32_t>(); A.n_work = (int32_t)n_pairs;
+    A.queue = d_queue.as<int32_t>(); A.bound = d_bound.as<sxg_key_t>(); A.bound_rows = bound_rows;
+    A.penalty = d_penalty.as<int32_t>(); A.cols = d_cols.as<int32_t>(); A.matches = d_matches.as<int32_t>();
+    float ms = 0;
+    if ((rc = timer_start(h))) return rc;
     sxg_split_launch_pairs(A, (int)n_slots, h->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    HIPCHK(hipMemcpy(penalty, B.e.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cols, B.f.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(matches, B.g.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
-    split_stats(h, ms, cells, n_slots, B.bound.cap);
+    if ((rc = timer_stop(h, &ms))) return rc;
+    HIPCHK(hipMemcpy(penalty, d_penalty.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cols, d_cols.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(matches, d_matches.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    split_stats(h, ms, cells, n_slots, d_bound.cap);
     return SXG_OK;
 }
 
@@ -2837,6 +2785,7 @@ static int split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, const sxg_
     h->stats = sxg_poa_stats{};
     SplitOwner* o = new SplitOwner();
     out->_owner = o; out->n_blocks = nb; out->n_seqs = ns;
+    OutGuard<sxg_poa_split_out, sxg_poa_split_free> guard(out);   // (every return below but those after dismiss() frees the result)
     o->group.assign((size_t)std::max<int64_t>(ns, 1), 0); o->n_groups.assign((size_t)std::max(nb, 1), 0);
     o->status.assign((size_t)std::max(nb, 1), 0); o->n_pairs.assign((size_t)std::max(nb, 1), 0);
     out->group = o->group.data(); out->n_groups = o->n_groups.data(); out->status = o->status.data(); out->n_pairs = o->n_pairs.data();
@@ -2859,44 +2808,39 @@ static int split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, const sxg_
         max_len = std::max(max_len, longest);
         max_depth = std::max(max_depth, s1 - s0);
     }
-#define SPLIT_CK(x) do { int _rc = (x); if (_rc) { sxg_poa_split_free(out); return _rc; } } while (0)
-#define SPLIT_HCK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { sxg_poa_split_free(out); return fail(SXG_E_NODEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); } } while (0)
     if (!cost.empty()) {
         std::stable_sort(cost.begin(), cost.end(), [](const std::pair<uint64_t, int32_t>& x, const std::pair<uint64_t, int32_t>& y) { return x.first > y.first; });
         std::vector<int32_t> work(cost.size());
         for (size_t k = 0; k < cost.size(); ++k) work[k] = cost[k].second;
-        SplitBufs B;
-        SPLIT_CK(split_upload_seqs(h, B, ns, in->seq_off, in->bases));
-        SPLIT_CK(split_up(h, B.a, in->blk_off, (size_t)nb + 1));
-        SPLIT_CK(split_up(h, B.b, in->identity, (size_t)nb));
-        SPLIT_CK(split_up(h, B.c, in->length_ratio_min, (size_t)nb));
-        SPLIT_CK(split_up(h, B.work, work.data(), work.size()));
-        SPLIT_CK(B.d.ensure(4 * (size_t)ns)); SPLIT_CK(B.e.ensure(4 * (size_t)nb)); SPLIT_CK(B.f.ensure(8 * (size_t)nb)); SPLIT_CK(B.g.ensure(8 * (size_t)nb));
-        SPLIT_CK(B.queue.ensure(256));
+        MashSets seqs;
+        DevBuf d_blk_off, d_identity, d_ratio_min, d_work, d_queue, d_bound, d_lists, d_group, d_n_groups, d_n_pairs, d_cells,
+            d_min_len, d_mash_f, d_mash_jmin, d_n_mash;   // (the last four: the mash-based branch)
+        int rc;
+        if ((rc = split_upload_seqs(h, seqs, ns, in->seq_off, in->bases)) || (rc = split_up(h, d_blk_off, in->blk_off, (size_t)nb + 1)) ||
+            (rc = split_up(h, d_identity, in->identity, (size_t)nb)) || (rc = split_up(h, d_ratio_min, in->length_ratio_min, (size_t)nb)) ||
+            (rc = split_up(h, d_work, work.data(), work.size())) ||
+            (rc = d_group.ensure(4 * (size_t)ns)) || (rc = d_n_groups.ensure(4 * (size_t)nb)) || (rc = d_n_pairs.ensure(8 * (size_t)nb)) ||
+            (rc = d_cells.ensure(8 * (size_t)nb)) || (rc = d_queue.ensure(256)))
+            return rc;
         const int64_t bound_rows = max_len + 1;
         const size_t slot_bytes = 3 * sizeof(sxg_key_t) * (size_t)bound_rows + 2 * sizeof(int32_t) * (size_t)max_depth;
         int64_t n_slots = 0;
-        if (!mash) SPLIT_CK(split_slots(h, 1, (int64_t)work.size(), slot_bytes, &n_slots));
-        else {
-            int per_cu = 1;
-            sxg_mash_occupancy(2, &per_cu);
-            n_slots = std::min<int64_t>((int64_t)work.size(), (int64_t)std::max(h->num_cu, 1) * per_cu);
-            n_slots = std::min<int64_t>(n_slots, (int64_t)(arena_budget(h) / std::max<size_t>(slot_bytes, 1)));
-            if (n_slots < 1) { sxg_poa_split_free(out); return fail(SXG_E_NOMEM, "memory budget too small for one split slot"); }
-        }
-        SPLIT_CK(B.bound.ensure(3 * sizeof(sxg_key_t) * (size_t)bound_rows * (size_t)n_slots));
-        SPLIT_CK(B.lists.ensure(2 * sizeof(int32_t) * (size_t)max_depth * (size_t)n_slots));
-        SPLIT_HCK(hipMemsetAsync(B.queue.p, 0, 4, h->stream));
-        SPLIT_HCK(hipMemsetAsync(B.d.p, 0, 4 * (size_t)ns, h->stream));
-        SPLIT_HCK(hipMemsetAsync(B.e.p, 0, 4 * (size_t)nb, h->stream));
-        SPLIT_HCK(hipMemsetAsync(B.f.p, 0, 8 * (size_t)nb, h->stream));
-        SPLIT_HCK(hipMemsetAsync(B.g.p, 0, 8 * (size_t)nb, h->stream));
+        int per_cu = 1;
+        if (mash) sxg_mash_occupancy(2, &per_cu); else sxg_split_occupancy(1, &per_cu);
+        if ((rc = split_slots(h, per_cu, (int64_t)work.size(), slot_bytes, &n_slots))) return rc;
+        if ((rc = d_bound.ensure(3 * sizeof(sxg_key_t) * (size_t)bound_rows * (size_t)n_slots))) return rc;
+        if ((rc = d_lists.ensure(2 * sizeof(int32_t) * (size_t)max_depth * (size_t)n_slots))) return rc;
+        HIPCHK(hipMemsetAsync(d_queue.p, 0, 4, h->stream));
+        HIPCHK(hipMemsetAsync(d_group.p, 0, 4 * (size_t)ns, h->stream));
+        HIPCHK(hipMemsetAsync(d_n_groups.p, 0, 4 * (size_t)nb, h->stream));
+        HIPCHK(hipMemsetAsync(d_n_pairs.p, 0, 8 * (size_t)nb, h->stream));
+        HIPCHK(hipMemsetAsync(d_cells.p, 0, 8 * (size_t)nb, h->stream));
         SplitBlockArgs A;
-        A.blk_off = B.a.as<int32_t>(); A.seq_off = B.seq_off.as<int64_t>(); A.bases = B.bases.as<uint8_t>();
-        A.identity = B.b.as<double>(); A.ratio_min = B.c.as<double>(); A.work = B.work.as<int32_t>(); A.n_work = (int32_t)work.size();
-        A.queue = B.queue.as<int32_t>(); A.bound = B.bound.as<sxg_key_t>(); A.bound_rows = bound_rows;
-        A.lists = B.lists.as<int32_t>(); A.list_cap = max_depth;
-        A.group = B.d.as<int32_t>(); A.n_groups = B.e.as<int32_t>(); A.n_pairs = B.f.as<int64_t>(); A.cells = B.g.as<uint64_t>();
+        A.blk_off = d_blk_off.as<int32_t>(); A.seq_off = seqs.seq_off.as<int64_t>(); A.bases = seqs.bases.as<uint8_t>();
+        A.identity = d_identity.as<double>(); A.ratio_min = d_ratio_min.as<double>(); A.work = d_work.as<int32_t>(); A.n_work = (int32_t)work.size();
+        A.queue = d_queue.as<int32_t>(); A.bound = d_bound.as<sxg_key_t>(); A.bound_rows = bound_rows;
+        A.lists = d_lists.as<int32_t>(); A.list_cap = max_depth;
+        A.group = d_group.as<int32_t>(); A.n_groups = d_n_groups.as<int32_t>(); A.n_pairs = d_n_pairs.as<int64_t>(); A.cells = d_cells.as<uint64_t>();
         size_t mash_bytes = 0;
         MashBlockArgs M;
         std::vector<int32_t> sketch_work;
@@ -2907,37 +2851,33 @@ static int split_batch(sxg_poa_handle* h, const sxg_poa_split_in* in, const sxg_
                 for (int64_t s = in->blk_off[b]; s < in->blk_off[b + 1]; ++s)
                     if (in->seq_off[s + 1] - in->seq_off[s] >= mash->min_len[b]) sketch_work.push_back((int32_t)s);
             }
-            SPLIT_CK(split_up(h, B.min_len, mash->min_len, (size_t)nb));
-            SPLIT_CK(split_up(h, B.mash_f, mash_f.data(), (size_t)nb));
-            SPLIT_CK(split_up(h, B.mash_jmin, mash_jmin.data(), (size_t)nb));
-            SPLIT_CK(B.n_mash.ensure(8 * (size_t)nb));
-            SPLIT_HCK(hipMemsetAsync(B.n_mash.p, 0, 8 * (size_t)nb, h->stream));
+            if ((rc = split_up(h, d_min_len, mash->min_len, (size_t)nb)) || (rc = split_up(h, d_mash_f, mash_f.data(), (size_t)nb)) ||
+                (rc = split_up(h, d_mash_jmin, mash_jmin.data(), (size_t)nb)) || (rc = d_n_mash.ensure(8 * (size_t)nb)))
+                return rc;
+            HIPCHK(hipMemsetAsync(d_n_mash.p, 0, 8 * (size_t)nb, h->stream));
         }
-        SPLIT_HCK(hipEventRecord(h->ev0, h->stream));
+        float ms = 0;
+        if ((rc = timer_start(h))) return rc;
         if (mash) {
-            SPLIT_CK(mash_sketch(h, B, ns, in->seq_off, sketch_work, mash->kmer_size, false, &mash_bytes));
-            M.S = A; M.min_len = B.min_len.as<int32_t>(); M.f = B.mash_f.as<double>(); M.jmin = B.mash_jmin.as<double>();
-            M.sets = B.sets.as<unsigned long long>(); M.set_size = B.set_size.as<int32_t>(); M.n_mash = B.n_mash.as<int64_t>();
+            if ((rc = mash_sketch(h, seqs, ns, in->seq_off, sketch_work, mash->kmer_size, false, &mash_bytes))) return rc;
+            M.S = A; M.min_len = d_min_len.as<int32_t>(); M.f = d_mash_f.as<double>(); M.jmin = d_mash_jmin.as<double>();
+            M.sets = seqs.sets.as<unsigned long long>(); M.set_size = seqs.set_size.as<int32_t>(); M.n_mash = d_n_mash.as<int64_t>();
             sxg_mash_launch_blocks(M, (int)n_slots, h->stream);
         } else sxg_split_launch_blocks(A, (int)n_slots, h->stream);
-        SPLIT_HCK(hipGetLastError());
-        SPLIT_HCK(hipEventRecord(h->ev1, h->stream));
-        SPLIT_HCK(hipEventSynchronize(h->ev1));
-        float ms = 0;
-        SPLIT_HCK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        HIPCHK(hipGetLastError());
+        if ((rc = timer_stop(h, &ms))) return rc;
         std::vector<uint64_t> cells((size_t)nb);
-        SPLIT_HCK(hipMemcpy(o->group.data(), B.d.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
-        SPLIT_HCK(hipMemcpy(o->n_groups.data(), B.e.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        SPLIT_HCK(hipMemcpy(o->n_pairs.data(), B.f.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
-        SPLIT_HCK(hipMemcpy(cells.data(), B.g.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
-        if (mash && n_mash) SPLIT_HCK(hipMemcpy(n_mash, B.n_mash.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o->group.data(), d_group.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o->n_groups.data(), d_n_groups.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o->n_pairs.data(), d_n_pairs.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cells.data(), d_cells.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
+        if (mash && n_mash) HIPCHK(hipMemcpy(n_mash, d_n_mash.p, 8 * (size_t)nb, hipMemcpyDeviceToHost));
         uint64_t total = 0;
         for (uint64_t c : cells) total += c;
-        split_stats(h, ms, total, n_slots, B.bound.cap + B.lists.cap + mash_bytes);
+        split_stats(h, ms, total, n_slots, d_bound.cap + d_lists.cap + mash_bytes);
         if (mash && !sketch_work.empty()) h->stats.dp_launches = 2;
     }
-#undef SPLIT_CK
-#undef SPLIT_HCK
+    guard.dismiss();   // (the caller keeps the result, also when a block failed: SXG_E_BLOCK below)
     if (any_failed) return fail(SXG_E_BLOCK, "a block holds a sequence longer than SXG_POA_MAX_SEQ_LEN");
     return SXG_OK;
 }
@@ -2974,37 +2914,36 @@ extern "C" int sxg_poa_kmer_jaccard_batch(sxg_poa_handle* h, int64_t n_seqs, con
     HIPCHK(hipSetDevice(h->device));
     h->stats = sxg_poa_stats{};
     if (n_seqs == 0) return SXG_OK;
-    SplitBufs B;
-    if (int rc = split_upload_seqs(h, B, n_seqs, seq_off, bases)) return rc;
+    MashSets seqs;
+    DevBuf d_pair_a, d_pair_b, d_inter, d_queue;
+    if (int rc = split_upload_seqs(h, seqs, n_seqs, seq_off, bases)) return rc;
     size_t dev_bytes = 0;
     int64_t n_slots = 0;
     if (n_pairs) {
-        if (int rc = split_up(h, B.a, pair_a, (size_t)n_pairs)) return rc;
-        if (int rc = split_up(h, B.b, pair_b, (size_t)n_pairs)) return rc;
-        if (int rc = B.c.ensure(4 * (size_t)n_pairs)) return rc;
-        if (int rc = B.queue.ensure(256)) return rc;
-        HIPCHK(hipMemsetAsync(B.queue.p, 0, 4, h->stream));
+        int rc;
+        if ((rc = split_up(h, d_pair_a, pair_a, (size_t)n_pairs)) || (rc = split_up(h, d_pair_b, pair_b, (size_t)n_pairs)) ||
+            (rc = d_inter.ensure(4 * (size_t)n_pairs)) || (rc = d_queue.ensure(256)))
+            return rc;
+        HIPCHK(hipMemsetAsync(d_queue.p, 0, 4, h->stream));
     }
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    if (int rc = mash_sketch(h, B, n_seqs, seq_off, work, kmer_size, kmers != nullptr, &dev_bytes)) return rc;
+    float ms = 0;
+    if (int rc = timer_start(h)) return rc;
+    if (int rc = mash_sketch(h, seqs, n_seqs, seq_off, work, kmer_size, kmers != nullptr, &dev_bytes)) return rc;
     if (n_pairs) {
         int per_cu = 1;
         sxg_mash_occupancy(1, &per_cu);
         n_slots = std::min<int64_t>(n_pairs, (int64_t)std::max(h->num_cu, 1) * per_cu);
         MashPairArgs A;
-        A.seq_off = B.seq_off.as<int64_t>(); A.sets = B.sets.as<unsigned long long>(); A.set_size = B.set_size.as<int32_t>();
-        A.pair_a = B.a.as<int32_t>(); A.pair_b = B.b.as<int32_t>(); A.n_pairs = (int32_t)n_pairs; A.queue = B.queue.as<int32_t>();
-        A.inter = B.c.as<int32_t>();
+        A.seq_off = seqs.seq_off.as<int64_t>(); A.sets = seqs.sets.as<unsigned long long>(); A.set_size = seqs.set_size.as<int32_t>();
+        A.pair_a = d_pair_a.as<int32_t>(); A.pair_b = d_pair_b.as<int32_t>(); A.n_pairs = (int32_t)n_pairs; A.queue = d_queue.as<int32_t>();
+        A.inter = d_inter.as<int32_t>();
         sxg_mash_launch_pairs(A, (int)n_slots, h->stream);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    HIPCHK(hipMemcpy(set_size, B.set_size.p, 4 * (size_t)n_seqs, hipMemcpyDeviceToHost));
-    if (n_pairs) HIPCHK(hipMemcpy(inter, B.c.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
-    if (kmers && seq_off[n_seqs] > 0) HIPCHK(hipMemcpy(kmers, B.sets.p, 8 * (size_t)seq_off[n_seqs], hipMemcpyDeviceToHost));
+    if (int rc = timer_stop(h, &ms)) return rc;
+    HIPCHK(hipMemcpy(set_size, seqs.set_size.p, 4 * (size_t)n_seqs, hipMemcpyDeviceToHost));
+    if (n_pairs) HIPCHK(hipMemcpy(inter, d_inter.p, 4 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+    if (kmers && seq_off[n_seqs] > 0) HIPCHK(hipMemcpy(kmers, seqs.sets.p, 8 * (size_t)seq_off[n_seqs], hipMemcpyDeviceToHost));
     split_stats(h, ms, 0, n_slots, dev_bytes);
     h->stats.dp_launches = n_pairs ? 2 : 1;
     return SXG_OK;
@@ -3090,22 +3029,20 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
         }
         int64_t round_pairs = 0;
         for (size_t r = 0, b0 = 0; r < round_end.size(); b0 = (size_t)round_end[r++]) round_pairs = std::max(round_pairs, pair_off[(size_t)round_end[r]] - pair_off[b0]);
-        SplitBufs B;
-        if (int rc = B.seq_off.ensure(8 * (size_t)(ns + 1))) return rc;
-        if (int rc = B.bases.ensure((size_t)nbases + 16)) return rc;
-        HIPCHK(hipMemcpyAsync(B.seq_off.p, seq_off.data(), 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(B.bases.p, bases.data(), (size_t)nbases, hipMemcpyHostToDevice, h->stream));
+        MashSets seqs;
+        DevBuf d_blk_off, d_pair_off, d_idx, d_inter, d_uni, d_words, d_queue;
+        int rc;
+        if ((rc = seqs.seq_off.ensure(8 * (size_t)(ns + 1))) || (rc = seqs.bases.ensure((size_t)nbases + 16))) return rc;
+        HIPCHK(hipMemcpyAsync(seqs.seq_off.p, seq_off.data(), 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(seqs.bases.p, bases.data(), (size_t)nbases, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (int rc = split_up(h, B.a, blk_off.data(), (size_t)nb + 1)) return rc;
-        if (int rc = split_up(h, B.b, pair_off.data(), (size_t)nb + 1)) return rc;
-        if (int rc = split_up(h, B.c, idx.data(), (size_t)nb)) return rc;
-        if (int rc = B.d.ensure(4 * (size_t)nb)) return rc;
-        if (int rc = B.e.ensure(4 * (size_t)nb)) return rc;
-        if (int rc = B.f.ensure(8 * (size_t)std::max<int64_t>(round_pairs, 1))) return rc;
-        if (int rc = B.queue.ensure(4 * round_end.size() + 256)) return rc;
-        HIPCHK(hipMemsetAsync(B.d.p, 0, 4 * (size_t)nb, h->stream));
-        HIPCHK(hipMemsetAsync(B.e.p, 0, 4 * (size_t)nb, h->stream));
-        HIPCHK(hipMemsetAsync(B.queue.p, 0, 4 * round_end.size(), h->stream));
+        if ((rc = split_up(h, d_blk_off, blk_off.data(), (size_t)nb + 1)) || (rc = split_up(h, d_pair_off, pair_off.data(), (size_t)nb + 1)) ||
+            (rc = split_up(h, d_idx, idx.data(), (size_t)nb)) || (rc = d_inter.ensure(4 * (size_t)nb)) || (rc = d_uni.ensure(4 * (size_t)nb)) ||
+            (rc = d_words.ensure(8 * (size_t)std::max<int64_t>(round_pairs, 1))) || (rc = d_queue.ensure(4 * round_end.size() + 256)))
+            return rc;
+        HIPCHK(hipMemsetAsync(d_inter.p, 0, 4 * (size_t)nb, h->stream));
+        HIPCHK(hipMemsetAsync(d_uni.p, 0, 4 * (size_t)nb, h->stream));
+        HIPCHK(hipMemsetAsync(d_queue.p, 0, 4 * round_end.size(), h->stream));
         std::vector<int32_t> work((size_t)ns);   // (min_len >= k: every sequence here has a window)
         for (int64_t s = 0; s < ns; ++s) work[(size_t)s] = (int32_t)s;
         size_t dev_bytes = 0;
@@ -3113,8 +3050,9 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
         sxg_identity_occupancy(&per_cu);
         int64_t pair_slots = 0;
         uint64_t launches = 1;
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
-        if (int rc = mash_sketch(h, B, ns, seq_off.data(), work, k, false, &dev_bytes)) return rc;   // Q1: M1's sets, one launch
+        float ms = 0;
+        if (int rc = timer_start(h)) return rc;
+        if (int rc = mash_sketch(h, seqs, ns, seq_off.data(), work, k, false, &dev_bytes)) return rc;   // Q1: M1's sets, one launch
         for (size_t r = 0, b0 = 0; r < round_end.size(); b0 = (size_t)round_end[r++]) {
             const int32_t b1 = round_end[r];
             const int64_t n_pairs = pair_off[(size_t)b1] - pair_off[b0];
@@ -3122,25 +3060,22 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
             const int64_t n_slots = std::min<int64_t>(n_pairs, (int64_t)std::max(h->num_cu, 1) * per_cu);
             pair_slots = std::max(pair_slots, n_slots);
             IdentityPairArgs A;
-            A.blk_off = B.a.as<int32_t>(); A.seq_off = B.seq_off.as<int64_t>(); A.sets = B.sets.as<unsigned long long>(); A.set_size = B.set_size.as<int32_t>();
-            A.pair_off = B.b.as<int64_t>(); A.b0 = (int32_t)b0; A.b1 = b1; A.n_pairs = (int32_t)n_pairs; A.queue = B.queue.as<int32_t>() + r;
-            A.words = B.f.as<unsigned long long>();
+            A.blk_off = d_blk_off.as<int32_t>(); A.seq_off = seqs.seq_off.as<int64_t>(); A.sets = seqs.sets.as<unsigned long long>(); A.set_size = seqs.set_size.as<int32_t>();
+            A.pair_off = d_pair_off.as<int64_t>(); A.b0 = (int32_t)b0; A.b1 = b1; A.n_pairs = (int32_t)n_pairs; A.queue = d_queue.as<int32_t>() + r;
+            A.words = d_words.as<unsigned long long>();
             sxg_identity_launch_pairs(A, (int)n_slots, h->stream);
             HIPCHK(hipGetLastError());
             IdentitySelectArgs S;
-            S.pair_off = B.b.as<int64_t>(); S.idx = B.c.as<int64_t>(); S.b0 = (int32_t)b0; S.words = B.f.as<unsigned long long>();
-            S.inter = B.d.as<int32_t>(); S.uni = B.e.as<int32_t>();
+            S.pair_off = d_pair_off.as<int64_t>(); S.idx = d_idx.as<int64_t>(); S.b0 = (int32_t)b0; S.words = d_words.as<unsigned long long>();
+            S.inter = d_inter.as<int32_t>(); S.uni = d_uni.as<int32_t>();
             sxg_identity_launch_select(S, b1 - (int32_t)b0, h->stream);
             HIPCHK(hipGetLastError());
             launches += 2;
         }
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        HIPCHK(hipEventSynchronize(h->ev1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        HIPCHK(hipMemcpy(inter, B.d.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(uni, B.e.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        split_stats(h, ms, 0, pair_slots, dev_bytes + B.f.cap);
+        if (int rc = timer_stop(h, &ms)) return rc;
+        HIPCHK(hipMemcpy(inter, d_inter.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(uni, d_uni.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
+        split_stats(h, ms, 0, pair_slots, dev_bytes + d_words.cap);
         h->stats.dp_launches = launches;   // the sketch + (pairs, select) of every round
     }
     if (any_failed) return fail(SXG_E_BLOCK, "a block holds a sequence longer than SXG_POA_MAX_SEQ_LEN");
@@ -3208,25 +3143,24 @@ extern "C" int sxg_poa_path_sgd_order(sxg_poa_handle* h, const sxg_poa_sgd_in* i
         if (!lds && batches > (1ull << 40) / (uint64_t)in->iter_max) return fail(SXG_E_INVALID, "path_sgd_order: too many batches");
         const size_t dev_bytes = 16 * (size_t)N + 4 * (size_t)N + 8 * (size_t)(P + 1) + 12 * (size_t)S + 8 * (size_t)in->iter_max;
         if ((uint64_t)dev_bytes > arena_budget(h)) return fail(SXG_E_NOMEM, "memory budget too small for the node coordinates and the path steps");
-        SplitBufs Bf;
-        if (int rc = split_up(h, Bf.a, in->node_len, (size_t)N)) return rc;
-        if (int rc = split_up(h, Bf.b, in->path_off, (size_t)(P + 1))) return rc;
-        if (int rc = split_up(h, Bf.c, in->step_node, (size_t)S)) return rc;
-        if (int rc = split_up(h, Bf.d, in->step_pos, (size_t)S)) return rc;
-        if (int rc = split_up(h, Bf.e, in->eta, (size_t)in->iter_max)) return rc;
-        if (int rc = split_up(h, Bf.f, X.data(), (size_t)N)) return rc;
-        if (int rc = Bf.g.ensure(8 * (size_t)N)) return rc;
-        HIPCHK(hipMemsetAsync(Bf.g.p, 0, 8 * (size_t)N, h->stream));
+        DevBuf d_node_len, d_path_off, d_step_node, d_step_pos, d_eta, d_X, d_D;
+        int rc;
+        if ((rc = split_up(h, d_node_len, in->node_len, (size_t)N)) || (rc = split_up(h, d_path_off, in->path_off, (size_t)(P + 1))) ||
+            (rc = split_up(h, d_step_node, in->step_node, (size_t)S)) || (rc = split_up(h, d_step_pos, in->step_pos, (size_t)S)) ||
+            (rc = split_up(h, d_eta, in->eta, (size_t)in->iter_max)) || (rc = split_up(h, d_X, X.data(), (size_t)N)) || (rc = d_D.ensure(8 * (size_t)N)))
+            return rc;
+        HIPCHK(hipMemsetAsync(d_D.p, 0, 8 * (size_t)N, h->stream));
         SgdArgs A;
-        A.node_len = Bf.a.as<int32_t>(); A.path_off = Bf.b.as<int64_t>(); A.step_node = Bf.c.as<int32_t>(); A.step_pos = Bf.d.as<int64_t>();
-        A.eta = Bf.e.as<double>(); A.X = Bf.f.as<unsigned long long>(); A.D = Bf.g.as<unsigned long long>();
+        A.node_len = d_node_len.as<int32_t>(); A.path_off = d_path_off.as<int64_t>(); A.step_node = d_step_node.as<int32_t>(); A.step_pos = d_step_pos.as<int64_t>();
+        A.eta = d_eta.as<double>(); A.X = d_X.as<unsigned long long>(); A.D = d_D.as<unsigned long long>();
         A.n_nodes = (int32_t)N; A.n_paths = (int32_t)P; A.S = (uint64_t)S; A.iter_max = in->iter_max; A.cooling_start = in->cooling_start;
         int nb = 0;
         for (uint64_t v = (uint64_t)(maxsteps - 1); v; v >>= 1) ++nb;                   // Y4: bitlength(maxsteps - 1)
         A.nb = std::max(nb, 1);
         A.terms_per_iter = terms; A.seed = in->seed; A.B = B;
         const int threads = lds ? (int)std::min<uint64_t>(1024, (std::min<uint64_t>(B, terms) + 63) / 64 * 64) : SXG_SGD_TERM_THREADS;
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        float ms = 0;
+        if (int rc = timer_start(h)) return rc;
         if (lds) {
             sxg_sgd_launch_lds(A, threads, 16 * (size_t)N, h->stream);
             launches = 1;
@@ -3239,11 +3173,8 @@ extern "C" int sxg_poa_path_sgd_order(sxg_poa_handle* h, const sxg_poa_sgd_in* i
                 }
         }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        HIPCHK(hipEventSynchronize(h->ev1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        HIPCHK(hipMemcpy(X.data(), Bf.f.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
+        if (int rc = timer_stop(h, &ms)) return rc;
+        HIPCHK(hipMemcpy(X.data(), d_X.p, 8 * (size_t)N, hipMemcpyDeviceToHost));
         h->stats.kernel_ms = ms; h->stats.dom_kernel_ms = ms; h->stats.dp_launches = launches; h->stats.n_slots = (int32_t)std::min<uint64_t>(launches, 0x7fffffff);
         h->stats.device_bytes = dev_bytes; h->stats.dom_threads = threads;
     }
