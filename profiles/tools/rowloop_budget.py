@@ -14,7 +14,12 @@ import sys
 
 W = sys.argv[1] if len(sys.argv) > 1 else "11"
 TM = sys.argv[2] if len(sys.argv) > 2 else "256"
-KSUB = sys.argv[3] if len(sys.argv) > 3 and sys.argv[3] else "dp_fill_p16ILi%sELb1ELb1ELi2ELi%sELi%sELb1E" % (W, "2" if TM == "64" and int(W) <= 11 else ("1" if int(TM) <= 128 else "0"), TM)
+# the default: the class as class_traits() (poa_classes.h) compiles it -- template arguments <W, CVX, SW, CB, RP, TFIX, DS>; the
+# classes of three waves and more (twin: stored rows never read back from the plane) are dp_fill_p16_twin, and only the classes up
+# to 512 threads other than the two-wave one are compiled for a fixed thread count
+RP = "2" if TM == "64" and int(W) <= 11 else ("1" if int(TM) <= 128 else "0")
+TFIX = TM if int(TM) <= 512 and int(TM) != 128 else "0"
+KSUB = sys.argv[3] if len(sys.argv) > 3 and sys.argv[3] else "%sILi%sELb1ELb1ELi2ELi%sELi%sELb1E" % ("dp_fill_p16_twin" if RP == "0" else "dp_fill_p16", W, RP, TFIX)
 out = "/tmp/rowloop_budget_%s_%s.s" % (W, TM)
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-DSXG_DEV_ONLY_W=" + W,
                        "-DSXG_DEV_ONLY_TMAX=" + TM, "-S", "--cuda-device-only", "-o", out, "smoothxg_amd/csrc/sxg_poa.hip"] + sys.argv[4:],

@@ -35,6 +35,11 @@
     // instruction (pk_max3): the fields stay inside the patterns whose binary16 order is the integer order (poa_fields.h)
     constexpr bool MAX3 = SW && DS && CVX;
     static_assert(!MAX3 || p16_fields_are_f16_ordered(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, W), "biased fields leave the ordered binary16 patterns");
+    // ... and build pass 1's strip carries as trees of such maxima over the strip's columns, each run down to the strip's last
+    // column by one plain 32-bit subtraction (p16_carry_leaf_bottom, poa_fields.h: no half borrows, every leaf stays ordered).
+    // (every width: W = 12 and 13, which spill without their pins, keep their registers and scratch with it -- profiles/r22)
+    constexpr bool CTREE = MAX3;
+    static_assert(!CTREE || p16_carry_leaf_bottom(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, W) >= 0, "a leaf of the carry trees borrows");
     // the classes compiled for the default scores read the long gap piece inside a strip off the strip's carry: opened inside
     // the strip it never beats the short piece there (p16_strip_q_dominated, poa_fields.h), so pass 2 keeps no Q state
     constexpr bool QDOM = CVX && DS;
@@ -378,7 +383,8 @@
                 const unsigned t0_2 = SC_N4 ^ (cd2 < 4 ? SC_MX << (8 * cd2) : 0u), t1_2 = SC_N4 ^ (cd2 == 4 ? SC_MX : 0u);
                 int Hc2[W], a2, b2, HLB;
                 // The fragment poa_dp16_row.inc.h speaks of the row under FIXED names, which every inclusion below binds on purpose:
-                //   part 1 reads  SC_T0, SC_T1 (the row's score table), Hp, Fp, Op, Hleft;  writes Hc[], declares a, b;
+                //   part 1 reads  SC_T0, SC_T1 (the row's score table), Hp, Fp, Op, Hleft;  writes Hc[], declares a, b
+                //                 (and sc4; the leaves of its carry trees, ta_ / tb_, live in a block of their own);
                 //   part 2 reads  i, flags, myslot, hint, Hc[], a, b;  modes 1 / 2 also HLB, HB[], twin_joined (see its header).
                 // A rename inside the fragment has to be followed here, or a shadowed name silently binds to the outer row's.
                 // (1) first row, pass 1: every name is the loop's own (row i); declares a, b for (3)

@@ -35,6 +35,7 @@
                 if (CVX) h = pk_max(h, Op[k]);
             }
             Hc[k] = h;
+            if constexpr (CTREE) { SXG_PIN("+v"(Hc[k])); continue; }   // (the carries: a tree over the finished columns, below)
             // a = max_k' (h_k' - (k'-k) e) over the columns k' >= k done so far: "the gap is e longer, or restarts here";
             // shifted by (W-1) e below it is max_k (h_k + (W-1-k) e), the carry the strip hands on.  The opening cost
             // and the local-alignment clamp (whose best term is k = W-1) are applied once per row
@@ -42,9 +43,35 @@
             if (CVX) b = pk_max(P16_INC(b, Cm, C2), h);
             SXG_PIN("+v"(Hc[k]), "+v"(a), "+v"(b));
         }
+        if constexpr (CTREE) {
+            // (round 19) the same two maxima, a = max_k (h_k + (W-1-k) e) and b with c, without the running form's chain of 2 W
+            // dependent instructions per carry: W - 1 independent full-rate subtractions of constants -- on both halves at once,
+            // no half borrows (p16_carry_leaf_bottom, poa_fields.h) --, the clamp at the bias as one more leaf, and a tree of
+            // three-input nodes as the row maximum's below (a node writes ta_[k] after reading ta_[3 k ..])
+            int ta_[W + 1], tb_[W + 1];
+#pragma unroll
+            for (int k = 0; k < W - 1; ++k) {
+                ta_[k] = (int)((unsigned)Hc[k] - (unsigned)(W - 1 - k) * Em);
+                tb_[k] = (int)((unsigned)Hc[k] - (unsigned)(W - 1 - k) * Cm);
+            }
+            ta_[W - 1] = tb_[W - 1] = Hc[W - 1];
+            ta_[W] = tb_[W] = B2;
+#pragma unroll
+            for (int n = W + 1; n > 1; n = n / 3 + (n % 3 ? 1 : 0)) {
+#pragma unroll
+                for (int k = 0; k < n / 3; ++k) {
+                    ta_[k] = pk_max3(ta_[3 * k], ta_[3 * k + 1], ta_[3 * k + 2]);
+                    tb_[k] = pk_max3(tb_[3 * k], tb_[3 * k + 1], tb_[3 * k + 2]);
+                }
+                if (n % 3 == 1) { ta_[n / 3] = ta_[n - 1]; tb_[n / 3] = tb_[n - 1]; }
+                if (n % 3 == 2) { ta_[n / 3] = pk_max(ta_[n - 2], ta_[n - 1]); tb_[n / 3] = pk_max(tb_[n - 2], tb_[n - 1]); }
+            }
+            a = ta_[0]; b = tb_[0];
+        } else {
         a = P16_DEC(a, (unsigned)(W - 1) * Em, pk2((W - 1) * e, (W - 1) * e));
         if (CVX) b = P16_DEC(b, (unsigned)(W - 1) * Cm, pk2((W - 1) * c, (W - 1) * c));
         if (SW) { a = pk_max(a, B2); if (CVX) b = pk_max(b, B2); }
+        }
         a = P16_DEC(a, Gm, G2);
         if (CVX) b = P16_DEC(b, Qm, Q2);
 #endif

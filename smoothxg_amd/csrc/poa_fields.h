@@ -60,6 +60,23 @@ static_assert(p16_fields_are_f16_ordered(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DE
 static_assert(!p16_fields_are_f16_ordered(-4, -120, -120, -120, -120, P16_W_MAX), "generic score sets are not covered");
 static_assert(p16_bottom_field(P16_DEF_N, P16_DEF_G, P16_DEF_Q, P16_DEF_C, P16_W_MAX) == P16_FLOOR - 26, "the opening (26) is still the deepest: a floor carry run over a strip is 512 - 12");
 
+// ---- pass 1's strip carries as maximum trees ------------------------------------------------------------------------
+// The carries a strip hands to the scans are plain maxima over its columns: a = max_k (Hc[k] - (W-1-k) |e|), b the same with
+// |c| (Hc: H before the in-row gaps).  The classes with ordered fields build them as trees of three-input maxima whose leaves
+// are Hc[k] run down to the strip's last column, (W - 1 - k) extensions: the least operand of a node is a pass-1 H at the
+// bottom bound, W - 1 extensions of the dearer piece down.  (Nothing rides ABOVE H in this form; p16_top_field keeps its
+// (W - 1) extensions for the classes that still carry a and b column by column.)
+// The leaf is ONE 32-bit subtraction of (W-1-k) |e| * 0x10001 on both halves: with every half at least this bound before and
+// at least 0 after, the low half never borrows from bit 16 -- the same bound is the range argument and the borrow argument.
+constexpr int p16_carry_leaf_bottom(int n, int g, int e, int q, int c, int W) {
+    return p16_bottom_field(n, g, q, c, W) - (W - 1) * (p16_abs(e) > p16_abs(c) ? p16_abs(e) : p16_abs(c));
+}
+static_assert(p16_carry_leaf_bottom(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, P16_W_MAX) == 462, "512 - 26 - 12 * 2");
+static_assert(p16_carry_leaf_bottom(P16_DEF_N, P16_DEF_G, P16_DEF_E, P16_DEF_Q, P16_DEF_C, P16_W_MAX) >= 0, "default scores: no leaf below 0, no borrow");
+// Not so for every score set the generic local classes admit -- they keep the running form.
+static_assert(p16_carry_leaf_bottom(-4, -120, -120, -120, -120, P16_W_MAX) < 0, "generic score sets are not covered");
+static_assert(p16_carry_leaf_bottom(-4, -120, -60, -120, -1, P16_W_MAX) < 0, "... nor with a cheap long piece: 512 - 120 - 12 * 60");
+
 // ---- the long gap piece inside a strip ------------------------------------------------------------------------------
 // Two-piece gap cost: a gap opened at column j' and read at column j, d = j - j' - 1 columns between them, scores
 // H[j'] + g + d e by the first piece and H[j'] + q + d c by the second.  The first is at least the second while
