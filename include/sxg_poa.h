@@ -43,7 +43,9 @@
 extern "C" {
 #endif
 
-/* 5 (addition, no number change, no struct change): sxg_poa_group_* -- one process, several GPUs: a group of handles, one host
+/* 5 (addition, no number change, no struct change): sxg_poa_set_long_blocks, sxg_poa_group_set_long_blocks, sxg_poa_get_tile_stats
+ *    and SXG_POA_MAX_SEQ_LEN_TILED -- the 32-bit sweep in column tiles: with the switch on, one length limit for every mode.
+ * 5 (addition, no number change, no struct change): sxg_poa_group_* -- one process, several GPUs: a group of handles, one host
  *    thread per member, the results reassembled in the batch's block order (trimmed MSA and block cycles included).
  * 5 (addition, no number change, no struct change): want_msa = SXG_MSA_TRIMMED -- the rows of the MAF built on the device -- and
  *    sxg_poa_get_msa_stats.
@@ -95,7 +97,8 @@ extern "C" {
 #define SXG_ST_POOL_OVERFLOW 2
 #define SXG_ST_TBX_OVERFLOW 3
 #define SXG_ST_NODES_OVERFLOW 4
-#define SXG_ST_TOO_LONG 5 /* a sequence exceeds SXG_POA_MAX_SEQ_LEN (local) / SXG_POA_MAX_SEQ_LEN_WIDE (see below) */
+#define SXG_ST_TOO_LONG 5 /* a sequence exceeds SXG_POA_MAX_SEQ_LEN (local) / SXG_POA_MAX_SEQ_LEN_WIDE, or, with
+                           * sxg_poa_set_long_blocks on, SXG_POA_MAX_SEQ_LEN_TILED in every mode (see below) */
 #define SXG_ST_RANGE_OVERFLOW 6 /* internal: scores left the narrow sweep's range; the engine re-runs the block wider */
 #define SXG_ST_INTERNAL 8       /* an internal invariant failed (e.g. the banded traceback left its band): final, please report */
 #define SXG_ST_BAND_MISS 7      /* internal: the packed sweep's traceback left its band of kept cells; re-run wider */
@@ -108,6 +111,14 @@ extern "C" {
  * 1024 lanes * 12 columns. */
 #define SXG_POA_MAX_SEQ_LEN 26623
 #define SXG_POA_MAX_SEQ_LEN_WIDE 12287
+/* With sxg_poa_set_long_blocks(h, 1) (off by default) a block that no geometry of its sweep covers -- global beyond the packed
+ * sweep, a walk that met a clamped cell, |g| or |q| > 120, local with m * length >= 30000, and local beyond SXG_POA_MAX_SEQ_LEN
+ * whose scores the packed sweep would hold (it then runs the 32-bit sweep) -- is swept by the widest 32-bit
+ * geometry in column tiles, left to right: up to 4 tiles of 12 288 columns, enough for -l 20k cut at 40k plus padding.  Below
+ * this length no mode and no score set answers SXG_ST_TOO_LONG, and a global block's status no longer depends on its data.
+ * The traceback plane of such a block takes rows x padded columns bytes (about 5 GB at the limit); an arena that does not fit
+ * fails that block alone.  The align-only API and the split / identity entry points keep their limits. */
+#define SXG_POA_MAX_SEQ_LEN_TILED 49151
 
 /* The six scores + alignment type that smooth_spoa hands to
  * spoa::AlignmentEngine::Create (src/smooth.cpp:752-755).                                */
@@ -416,6 +427,7 @@ void sxg_poa_group_destroy(sxg_poa_group *g);
 int sxg_poa_group_size(const sxg_poa_group *g);
 sxg_poa_handle *sxg_poa_group_member(sxg_poa_group *g, int32_t i);
 int sxg_poa_group_set_memory_budget(sxg_poa_group *g, uint64_t bytes_per_member);
+int sxg_poa_group_set_long_blocks(sxg_poa_group *g, int on); /* sxg_poa_set_long_blocks on every member */
 int sxg_poa_group_batch_run(sxg_poa_group *g, const sxg_poa_batch_in *in, sxg_poa_batch_out *out);
 int sxg_poa_group_batch_upload(sxg_poa_group *g, const sxg_poa_batch_in *in);
 int sxg_poa_group_batch_execute(sxg_poa_group *g);
@@ -603,6 +615,11 @@ int sxg_poa_path_sgd_order(sxg_poa_handle *h, const sxg_poa_sgd_in *in, int32_t 
 
 int sxg_poa_get_stats(sxg_poa_handle *h, sxg_poa_stats *out);
 int sxg_poa_get_width_stats(sxg_poa_handle *h, sxg_poa_width_stats *out);
+/* The switch of SXG_POA_MAX_SEQ_LEN_TILED (on != 0; read by the next sxg_poa_batch_upload and by the executes of that batch),
+ * and what the last execute ran in column tiles: blocks of its tiled launches, the sweeps (alignments) of those launches and the
+ * tiles they swept -- more tiles than sweeps means some sweep crossed a tile edge.  Any of the three pointers may be NULL. */
+int sxg_poa_set_long_blocks(sxg_poa_handle *h, int on);
+int sxg_poa_get_tile_stats(sxg_poa_handle *h, int64_t *blocks, int64_t *sweeps, int64_t *tiles);
 int sxg_poa_get_twin_stats(sxg_poa_handle *h, sxg_poa_twin_stats *out);
 int sxg_poa_get_msa_stats(sxg_poa_handle *h, double *cols_ms, double *rows_ms, uint64_t *msa_bytes);
 /* The rows kernel's geometry: kept letters of a row one work item places, bytes of a row it builds on chip at once (tests). */

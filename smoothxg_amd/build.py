@@ -14,7 +14,7 @@ SO = os.path.join(CSRC, "libsxgpoa.so")
 KERN_PARTS = range(1, 10)
 SOURCES = [("sxg_poa.hip", "sxg_poa.o", []), ("kern_split.hip", "kern_split.o", []), ("kern_msa.hip", "kern_msa.o", []),
            ("kern_sgd.hip", "kern_sgd.o", ["-ffp-contract=off"])] + [("kern_part.hip", "kern_part%d.o" % k, ["-DSXG_KERN_PART=%d" % k]) for k in KERN_PARTS]
-DEPS = ["sxg_poa.hip", "kern_part.hip", "poa_classes.h", "poa_slot_prof.h", "poa_cost.h", "poa_deal.h", "poa_results.h", "poa_devres.h", "poa_kernels.hip.h", "poa_kern_tables.hip.h", "poa_dp.hip.h", "poa_dp16.hip.h", "poa_dp16_fill.inc.h", "poa_dp16_row.inc.h", "poa_prep_rows.inc.h", "poa_rowcode.h", "poa_fields.h", "poa_band16.hip.h", "poa_graph_dev.h",
+DEPS = ["sxg_poa.hip", "kern_part.hip", "poa_classes.h", "poa_slot_prof.h", "poa_cost.h", "poa_tiles.h", "poa_deal.h", "poa_results.h", "poa_devres.h", "poa_kernels.hip.h", "poa_kern_tables.hip.h", "poa_dp.hip.h", "poa_dp16.hip.h", "poa_dp16_fill.inc.h", "poa_dp16_row.inc.h", "poa_prep_rows.inc.h", "poa_rowcode.h", "poa_fields.h", "poa_band16.hip.h", "poa_graph_dev.h",
                   "poa_bgraph_dev.h", "poa_types.h", "kern_split.hip", "poa_split.hip.h", "poa_mash.hip.h", "poa_identity.hip.h", "poa_identity_key.h", "kern_sgd.hip", "poa_sgd.hip.h", "kern_msa.hip", "poa_msa.hip.h", "poa_msa_cols.h", os.path.join("..", "..", "include", "sxg_poa.h")]
 OBJ_DIR = os.path.join(CSRC, "build")
 

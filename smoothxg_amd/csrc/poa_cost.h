@@ -8,7 +8,8 @@
 // unit of work is rows x swept columns: cost = sum over the alignments k >= 1 of rows_k * cols_k.
 //   rows_k: the graph's rows when sequence k is aligned -- an ESTIMATE, SURVEY 8(e)'s L_0 + 0.05 * sum_{j<k} L_j;
 //   cols_k: EXACT -- the packed sweep's T * 2 * W2 when the class has a second width and the sequence fits it (width_for_len: the
-//           test poa_block_kernel makes per sequence), T * 2 * W otherwise; the 32-bit sweeps' T * W; the banded sweep's band,
+//           test poa_block_kernel makes per sequence), T * 2 * W otherwise; the 32-bit sweeps' T * W, times the tiles of the
+//           sequence when the launch sweeps in column tiles (poa_tiles.h: rows x Lpad_total); the banded sweep's band,
 //           2 * band_half_width(L_k) cells per row.
 // The sweeps report their progress to the priority board in the same unit (rows done x the columns they sweep), and the block
 // kernel takes the part of a block that is done from the prefix sums of the same terms (BlockArgs::est_done).
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "poa_classes.h"
+#include "poa_tiles.h"
 
 namespace sxg {
 
@@ -29,24 +31,24 @@ constexpr int BAND_WMAX = 693;      // decree B1: cap of the half-width -- a ban
 constexpr int band_half_width(int L) { const int w = BAND_WB + (int)(BAND_WF * L); return w < BAND_WMAX ? w : BAND_WMAX; }
 
 // columns (banded: band cells) one row of the alignment of a sequence of `len` letters costs a launch of row mode rm, T threads,
-// strip width W and second width W2 (0 = none; only the packed sweep has one)
-constexpr uint64_t cost_cols(int rm, int T, int W, int W2, int64_t len) {
+// strip width W and second width W2 (0 = none; only the packed sweep has one); tiles > 1: a 32-bit launch in column tiles
+constexpr uint64_t cost_cols(int rm, int T, int W, int W2, int64_t len, int tiles = 1) {
     if (rm == 3) return 2u * (uint64_t)band_half_width((int)len);
     if (rm == 2) return (uint64_t)T * 2u * (uint64_t)width_for_len(W, W2, T, (int)len);
-    return (uint64_t)T * (uint64_t)W;
+    return (uint64_t)T * (uint64_t)W * (uint64_t)(tiles > 1 ? n_tiles((int)len, T, W) : 1);
 }
 
 // Cost of the block whose n sequences have the offsets off[0 .. n] (lengths off[k + 1] - off[k], in alignment order).
 // done[k], k = 0 .. n - 1 (nullptr: not wanted), receives the cost of the alignments BEFORE k: done[0] = done[1] = 0 -- the first
 // sequence founds the graph and is not swept -- and done[n - 1] + the last term is the returned total.
-inline uint64_t block_cost(const int64_t* off, int n, int rm, int T, int W, int W2, uint64_t* done) {
+inline uint64_t block_cost(const int64_t* off, int n, int rm, int T, int W, int W2, uint64_t* done, int tiles = 1) {
     uint64_t total = 0;
     double prev = 0;
     const double l0 = n > 0 ? (double)(off[1] - off[0]) : 0.0;
     for (int k = 0; k < n; ++k) {
         const int64_t len = off[k + 1] - off[k];
         if (done) done[k] = total;
-        if (k > 0) total += (uint64_t)((l0 + 0.05 * prev) * (double)cost_cols(rm, T, W, W2, len));
+        if (k > 0) total += (uint64_t)((l0 + 0.05 * prev) * (double)cost_cols(rm, T, W, W2, len, tiles));
         prev += (double)len;
     }
     return total;

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 
@@ -48,17 +49,23 @@ inline size_t lay(size_t& cur, size_t bytes) {
 // re-sort, ~104 bytes per node of nodes_cap -- left out of every other arena
 // W2, band_strips2: the second strip width of the launch's alignments and its strips per plane row (0: none).  The plane is sized
 // for the larger of the two (strips x dwords per strip); pool, row 0 and park for the geometry's own width, whose rows are the longer.
+// tiles, bnd_off: a 32-bit sweep in column tiles (poa_tiles.h; Lpad is the tile's width).  The traceback plane, the fold-step
+// masks and row 0 are laid out per virtual lane -- `tiles` times as wide --, and *bnd_off receives where the two boundary buffers
+// of rows_cap + 1 records lie (behind the parked row; one tile has none, and the offset is the parked row's: never read).  The offset is no member of the
+// layout: SlotLayout travels inside the kernels' argument block, whose size and offsets every kernel class is compiled against.
 inline SlotLayout make_layout(int nodes_cap, int rows_cap, int pool_slots, int step_cap, int threads, int Lpad,
                               int word_bytes, bool pairs, int band_strips = 0, int cell_bytes = 4, bool spoa_scratch = false,
-                              int W2 = 0, int band_strips2 = 0) {
+                              int W2 = 0, int band_strips2 = 0, int tiles = 1, size_t* bnd_off = nullptr) {
     SlotLayout L;
     memset(&L, 0, sizeof(L));
     L.nodes_cap = nodes_cap; L.rows_cap = rows_cap; L.pool_slots = pool_slots;
     L.step_cap = step_cap; L.threads = threads; L.Lpad = Lpad; L.word_bytes = word_bytes;
     L.band_strips = band_strips;
     const bool packed = band_strips > 0;
+    if (packed || tiles < 1) tiles = 1;
     L.W2 = packed ? W2 : 0; L.band_strips2 = L.W2 ? band_strips2 : 0;
-    const size_t C = (size_t)nodes_cap + 4, S = (size_t)std::max(nodes_cap, Lpad) + 4, Rr = (size_t)rows_cap + 4;
+    const size_t LpadT = (size_t)tiles * (size_t)Lpad;   // padded width of the matrix (poa_tiles.h: tiles_lpad_total)
+    const size_t C = (size_t)nodes_cap + 4, S = std::max((size_t)nodes_cap, LpadT) + 4, Rr = (size_t)rows_cap + 4;
     L.scratch_len = (int)S;
     size_t cur = 0;
     L.hdr = lay(cur, SLOT_HDR_BYTES);
@@ -80,18 +87,22 @@ inline SlotLayout make_layout(int nodes_cap, int rows_cap, int pool_slots, int s
     L.r_preds = lay(cur, 4 * C); L.r_slot = lay(cur, 4 * Rr); L.r_tbx = lay(cur, 4 * Rr);
     L.r_sseq = lay(cur, 4 * Rr); L.r_row_node = lay(cur, 4 * Rr); L.r_meta = lay(cur, 32 * Rr);
     // traceback plane: one byte per cell, or (packed sweep) one dword per cell of the row's band of strips
-    size_t plane_row = packed ? (size_t)band_strips * (size_t)p16_slot_dwords(Lpad / (2 * threads), cell_bytes) * 4 : (size_t)Lpad;
+    size_t plane_row = packed ? (size_t)band_strips * (size_t)p16_slot_dwords(Lpad / (2 * threads), cell_bytes) * 4 : LpadT;
     if (L.W2) plane_row = std::max(plane_row, (size_t)L.band_strips2 * (size_t)p16_slot_dwords(L.W2, cell_bytes) * 4);
     L.tb = lay(cur, ((size_t)rows_cap + 1) * plane_row);
-    L.steps = lay(cur, packed ? 256 : (size_t)std::max(step_cap, 1) * 3 * threads * 4);
+    L.steps = lay(cur, packed ? 256 : (size_t)std::max(step_cap, 1) * 3 * tiles_vlanes(tiles, threads) * 4);
     // (a stored row of the packed sweep ends with one more word per lane: the column left of the lane's strips; its 2-byte
     //  classes store 2 bytes per column, dp16_row_bytes)
     const size_t row_bytes = (size_t)Lpad * (packed && cell_bytes == 2 ? 2 : word_bytes) + (size_t)threads * 4;
     L.pool = lay(cur, (size_t)pool_slots * row_bytes);
-    L.row0 = lay(cur, row_bytes);
+    L.row0 = lay(cur, row_bytes + (LpadT - (size_t)Lpad) * word_bytes);
     L.park = lay(cur, (size_t)Lpad * word_bytes);
+    if (tiles > 1) {
+        const size_t o = lay(cur, 2 * (size_t)tile_bnd_records(rows_cap) * TILE_BND_BYTES);
+        if (bnd_off) *bnd_off = o;
+    } else if (bnd_off) *bnd_off = L.park;   // (never read)
     L.cons_sc = lay(cur, 8 * C); L.cons_pr = lay(cur, 4 * C);
-    if (pairs) { L.pair_row = lay(cur, 4 * (Rr + Lpad)); L.pair_pos = lay(cur, 4 * (Rr + Lpad)); }
+    if (pairs) { L.pair_row = lay(cur, 4 * (Rr + LpadT)); L.pair_pos = lay(cur, 4 * (Rr + LpadT)); }
     L.total = cur;
     return L;
 }
@@ -189,8 +200,12 @@ struct BlockArgs {
     // inputs (device)
     const int32_t* blk_off; const int64_t* seq_off; const uint8_t* bases; const uint32_t* weights;
     const sxg_poa_params* params; int per_block_params;
+    // 32-bit sweep in column tiles (poa_tiles.h): tiles the arenas of this launch are laid out for (1: no tiles) and where a slot's
+    // boundary buffers lie, in units of 256 bytes from the slot's base.  (Both sit where the structure had padding: its size and
+    // the offsets of its other members are what every kernel class was compiled against.)
+    int n_tiles;
     // work list of this launch
-    const int32_t* work; int n_work; int32_t* queue;
+    const int32_t* work; int n_work; unsigned bnd_off256; int32_t* queue;
     // slots
     uint8_t* arena; SlotLayout lay;
     // outputs (device), worst-case layout: block b's nodes/edges start at seq_off[blk_off[b]]
@@ -214,6 +229,14 @@ struct BlockArgs {
     int band_floor, band_margin, band_full;
     int twin;   // packed classes with the twin step: 0 = prep sets neither ROW_TWIN nor ROW_JOIN (SXG_POA_TWIN=0: the rows of round 12)
 };
+// The two tile members fill what was padding: the argument block's size and the offsets of its other members are what the
+// kernel classes that never read them were compiled against, and stay.
+static_assert(offsetof(BlockArgs, n_tiles) == offsetof(BlockArgs, per_block_params) + 4 && offsetof(BlockArgs, work) == offsetof(BlockArgs, n_tiles) + 4,
+              "n_tiles sits in the padding in front of work");
+static_assert(offsetof(BlockArgs, bnd_off256) == offsetof(BlockArgs, n_work) + 4 && offsetof(BlockArgs, queue) == offsetof(BlockArgs, bnd_off256) + 4,
+              "bnd_off256 sits in the padding in front of queue");
+static_assert(offsetof(BlockArgs, arena) == offsetof(BlockArgs, queue) + 8 && offsetof(BlockArgs, lay) == offsetof(BlockArgs, arena) + 8 &&
+              sizeof(BlockArgs) == offsetof(BlockArgs, twin) + 4 && sizeof(BlockArgs) == 728, "the argument block's size, as before the tile members");
 
 // Kernel classes <TMAX, W>: TMAX bounds blockDim.x (the actual T = 64 * strips is a run-time
 // value), W = columns per lane.  The second launch-bound is the number of waves per SIMD the
@@ -282,7 +305,8 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
             __syncthreads();
             const int N = *V.G.n_nodes;
             int score = 0;
-            if (RM != 3 && len + 1 > T * CPL) { status = ST_TOO_LONG; break; }   // (against W, whatever the second width)
+            // (against W, whatever the second width; a 32-bit sweep in column tiles: against all its tiles)
+            if (RM != 3 && len + 1 > T * CPL * (RM < 2 ? A.n_tiles : 1)) { status = ST_TOO_LONG; break; }
             if (N + len > A.lay.nodes_cap || *V.G.n_edges + len > A.lay.nodes_cap) { status = ST_NODES_OVERFLOW; break; }
             // (the packed full-matrix sweep clamps instead and lets the traceback decide: see P16_NWFLOOR)
             if (RM != 1 && RM != 2 && !S.sw &&
@@ -411,10 +435,16 @@ __global__ __launch_bounds__(TMAX, sxg_min_waves(TMAX, W, RM)) void poa_block_ke
                     } else sweep(std::integral_constant<int, W>{});
                     if (status != ST_OK) break;
                 } else {
-                    dp_fill<W, CVX, H16, SW>(S, V.R, N, seq, len, V.B, smem, A.park_in_lds != 0, A.pf_off, res);
+                    DpTiles TL;
+                    TL.cap = A.n_tiles; TL.rows_cap = A.lay.rows_cap;
+                    TL.bnd = A.arena + (size_t)blockIdx.x * A.lay.total + (size_t)A.bnd_off256 * 256;
+                    // (sweeps and tiles of a tiled launch: sxg_poa_get_tile_stats)
+                    if (t == 0 && A.n_tiles > 1) prof[SP_TILES] += 1ull | ((unsigned long long)n_tiles(len, T, W) << 32);
+                    dp_fill<W, CVX, H16, SW>(S, V.R, N, seq, len, V.B, smem, A.park_in_lds != 0, A.pf_off, res, TL);
                     __syncthreads();
                     PROF(SP_DP_FILL);
-                    if (t == 0 && res.bi >= 0) traceback<false>(V.R, V.B, T, W, S.sw, res.bi, res.bj, V.G.posnode, nullptr, nullptr);
+                    // (the walk finds a column's lane and mask word by virtual lane: as in a workgroup of n_tiles * T lanes)
+                    if (t == 0 && res.bi >= 0) traceback<false>(V.R, V.B, tiles_vlanes(A.n_tiles, T), W, S.sw, res.bi, res.bj, V.G.posnode, nullptr, nullptr);
                     __syncthreads();
                     PROF(SP_TRACEBACK);
                 }

@@ -24,7 +24,7 @@ enum : int {
     SP_WALL0 = 8, SP_WALL1 = 9,     // constant 100 MHz clock at the slot's start and end (s_memrealtime)
     SP_WAVE = 10,              // SP_WAVES words: placement of every wave, smid << 32 | raw HW_ID
     SP_WAVES = 16,
-    SP_UNUSED = 26,            // (nothing writes or reads it)
+    SP_TILES = 26,             // 32-bit sweep in column tiles: sweeps | tiles they swept << 32, of the launches laid out for more than one tile
     SP_HINT_REPEATS = 27,      // packed sweep: sweeps repeated after a hint shift
     SP_ROW = 28,               // ROWP_WORDS words: DpBuffers::row_prof (SXG_ROW_PROF builds)
     SP_RESORT = 41,            // RSP_WORDS words: spoa_resort's rprof (SXG_RESORT_PROF builds)
@@ -51,7 +51,7 @@ enum : int {
     RSP_WORDS = 6,
 };
 
-static_assert(SP_WAVE + SP_WAVES == SP_UNUSED && SP_UNUSED + 1 == SP_HINT_REPEATS, "placement words, then the unused one");
+static_assert(SP_WAVE + SP_WAVES == SP_TILES && SP_TILES + 1 == SP_HINT_REPEATS, "placement words, then the tile counters");
 static_assert(SP_ROW + ROWP_WORDS <= SP_RESORT, "the row profile ends in front of the re-sort profile");
 static_assert(SP_RESORT + RSP_WORDS <= SP_BAND_STRIPS, "the re-sort profile ends in front of the band counters");
 static_assert(SP_SWEEPS + 2 == SP_SWEPT_COLS && SP_SWEPT_COLS + 2 == SP_SWEPT_CELLS && SP_SWEPT_CELLS + 2 == SP_TWIN, "one word per width");

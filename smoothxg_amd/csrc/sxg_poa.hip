@@ -229,6 +229,7 @@ struct HostLaps {
 struct BlockMeta {
     int maxlen = 0, nseq = 0, rm = 0; bool fits = false; Variant variant{16, 1, 256, 0};
     int tier = 0;      // arena capacity tier the block runs at next (raised by ROWS/POOL/TBX overflow only)
+    int tiles = 1;     // 32-bit sweep in column tiles (poa_tiles.h): tiles of the block's longest sequence at `variant`; 1 = no tiles
     bool wide_band = false;   // packed sweep re-run with a traceback plane that keeps EVERY strip (after ST_BAND_MISS)
     bool no_wide = false;     // that plane did not fit the arena budget: the block takes the widening ladder instead
     int64_t sumlen = 0;
@@ -239,12 +240,33 @@ struct BlockMeta {
 
 // Row mode (the narrowest >= at_least that holds the block's scores), plane cell format and launch geometry of a block
 // (optimistic: the kernel re-checks -- see score_floor -- and a packed global sweep checks the cells its traceback visits)
-static void classify_block(BlockMeta& m, int at_least, bool clamp_ok) {
+// long_blocks (sxg_poa_set_long_blocks): a block on a 32-bit sweep that no geometry covers runs the widest one, 16 waves of 12
+// columns, in as many column tiles as its longest sequence needs, up to SXG_POA_MAX_SEQ_LEN_TILED.  SXG_POA_TILE_COLS=n (a
+// multiple of 512; honoured with the switch on only -- a test knob, tiles change speed, never results): every 32-bit block takes
+// the geometry of a sequence of n - 1 letters and the tiles its own length needs at it.
+static_assert(SXG_POA_MAX_SEQ_LEN_TILED == TILED_MAX_SEQ_LEN && TILED_MAX_SEQ_LEN + 1 == TILED_MAX_TILES * (SXG_POA_MAX_SEQ_LEN_WIDE + 1), "tiled limit of the header");
+static void classify_block(BlockMeta& m, int at_least, bool clamp_ok, bool long_blocks) {
     m.rm = row_mode(m.S, m.maxlen, m.maxlen, at_least, clamp_ok);
-    const int cb = m.rm == 2 ? plane_cell_bytes(m.S) : 4;
+    int cb = m.rm == 2 ? plane_cell_bytes(m.S) : 4;
     int fw, fnw;
     forced_p16(&fw, &fnw);
     m.fits = variant_for_len(m.maxlen, m.rm, &m.variant, m.S.sw, cb, fw, fnw);
+    m.tiles = 1;
+    // (a block whose scores the packed sweep holds but whose length no packed geometry covers -- local beyond 26 623 letters with
+    //  m L < 30 000 -- takes the 32-bit sweep, tiled, as well: below the tiled limit the switch leaves no length refused)
+    if (long_blocks && m.rm == 2 && !m.fits && m.maxlen <= SXG_POA_MAX_SEQ_LEN_TILED) {
+        m.rm = row_mode(m.S, m.maxlen, m.maxlen, 0, false);
+        cb = 4;
+        m.fits = variant_for_len(m.maxlen, m.rm, &m.variant, m.S.sw, cb, 0, 0);
+    }
+    if (long_blocks && m.rm < 2 && m.maxlen <= SXG_POA_MAX_SEQ_LEN_TILED) {
+        int cols = 0;
+        if (const char* e = getenv("SXG_POA_TILE_COLS")) cols = atoi(e);
+        Variant v = m.variant;
+        if (cols >= 512 && cols % 512 == 0 && variant_for_len(cols - 1, m.rm, &v)) { m.variant = v; m.fits = true; }
+        else if (!m.fits) { m.variant = Variant{12, 16, class_tmax(12, 16, m.rm, 4, true), m.rm, 4}; m.fits = true; }
+        m.tiles = n_tiles(m.maxlen, m.variant.T(), m.variant.W);
+    }
     m.variant.CB = cb;   // (also of a block that does not fit)
     m.variant.DS = m.rm == 2 && cb == 2 && p16_default_scores(m.S) && !getenv("SXG_POA_NO_DEFAULT_CLASS");
 }
@@ -291,6 +313,8 @@ struct sxg_poa_handle {
     std::vector<std::unique_ptr<PlanRes>> planres;   // per launch of a round: stream, events, arena (kept between executes)
     int num_cu = 256;
     uint64_t mem_budget = 0;
+    bool long_blocks = false;   // sxg_poa_set_long_blocks: 32-bit sweeps beyond their widest geometry run in column tiles
+    int64_t tile_blocks = 0, tile_sweeps = 0, tile_tiles = 0;   // tiled launches of the last execute (sxg_poa_get_tile_stats)
     int budget_share = 1;   // members of a device group on this handle's device: the default arena cap is divided among them
     // resident batch
     bool have_batch = false, executed = false;
@@ -467,6 +491,20 @@ extern "C" int sxg_poa_set_memory_budget(sxg_poa_handle* h, uint64_t bytes) {
     return SXG_OK;
 }
 
+extern "C" int sxg_poa_set_long_blocks(sxg_poa_handle* h, int on) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    h->long_blocks = on != 0;   // (read when a batch is uploaded and when a block changes its sweep)
+    return SXG_OK;
+}
+
+extern "C" int sxg_poa_get_tile_stats(sxg_poa_handle* h, int64_t* blocks, int64_t* sweeps, int64_t* tiles) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    if (blocks) *blocks = h->tile_blocks;
+    if (sweeps) *sweeps = h->tile_sweeps;
+    if (tiles) *tiles = h->tile_tiles;
+    return SXG_OK;
+}
+
 extern "C" int sxg_poa_get_stats(sxg_poa_handle* h, sxg_poa_stats* out) {
     if (!h || !out) return fail(SXG_E_INVALID, "NULL argument");
     *out = h->stats;
@@ -556,7 +594,7 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
             if (s > in->blk_off[b]) m.cost += (double)len * (l1 + 0.05 * prev);
             prev += (double)len;
         }
-        classify_block(m, 2, h->h_params[in->per_block_params ? b : 0].banded == 0);
+        classify_block(m, 2, h->h_params[in->per_block_params ? b : 0].banded == 0, h->long_blocks);
         // A11: the reference's abPOA path is banded (wb=311, wf=0.03); local alignments whose scores fit the packed
         // sweep run the one-wave banded kernel, everything else asked to be banded runs the full matrix
         // (global alignment: the adaptive band only -- the band of a row without successors holds the end column by
@@ -621,6 +659,8 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
 
 struct LaunchPlan {
     Variant variant; bool cvx, sw; int tier = 0; bool wide_band = false;
+    int tiles = 1;        // 32-bit sweep in column tiles: the tile count its blocks share (a launch of its own); 1 = no tiles
+    size_t bnd_off = 0;   // where a slot's boundary buffers lie (make_layout)
     std::vector<int32_t> work;  // block ids, largest cost first
     std::vector<unsigned long long> est;  // cost-model cells per work item (priority balancing)
     // filled by prepare_plan
@@ -695,7 +735,7 @@ static void prepare_plan(sxg_poa_handle* h, LaunchPlan& P, int attempt) {
     // strips per plane row at either width, on-chip rows and dynamic LDS of a packed launch: p16_launch_sizes
     const P16LaunchSizes LS = p16_launch_sizes(V.T(), V.W, P.variant.W2, V.CB, P.wide_band);
     P.lay = make_layout(nodes_cap, rows_cap, pool_slots, step_cap, V.T(), Lpad, wb, false, strips1, V.RM >= 2 ? V.CB : 4, any_spoa,
-                        V.RM == 2 ? P.variant.W2 : 0, LS.strips2);
+                        V.RM == 2 ? P.variant.W2 : 0, LS.strips2, P.tiles, &P.bnd_off);
     P.kern = block_kernel(P.variant, P.cvx, P.sw);
     const int tfix = class_traits(P.variant.TMAX, V.W, V.RM, V.CB).tfix;
     if (tfix && tfix != V.T()) { P.kern = nullptr; P.why = "kernel class compiled for " + std::to_string(tfix) + " threads asked to run at " + std::to_string(V.T()); }
@@ -704,7 +744,8 @@ static void prepare_plan(sxg_poa_handle* h, LaunchPlan& P, int attempt) {
     P.park_lds = dp_park_in_lds(Lpad, wb);
     if (V.RM == 2) { P.lay.lds_rows = LS.lds_rows; P.smem = LS.smem; P.park_lds = true; }
     if (V.RM == 3) { P.smem = band_lds_bytes(V.W); P.park_lds = true; }
-    P.pf_off = (V.RM < 2 && getenv("SXG_POA_PREFETCH")) ? dp_pf_offset(Lpad, wb, V.T()) : -1;
+    // (the LDS-DMA prefetch knows one tile: off in sweeps of more)
+    P.pf_off = (V.RM < 2 && P.tiles == 1 && getenv("SXG_POA_PREFETCH")) ? dp_pf_offset(Lpad, wb, V.T()) : -1;
     if (P.pf_off >= 0) P.smem += dp_pf_bytes(Lpad, wb, V.T());
     if (P.smem > 48 * 1024)
         (void)hipFuncSetAttribute((const void*)P.kern, hipFuncAttributeMaxDynamicSharedMemorySize, P.smem);
@@ -755,6 +796,7 @@ static int launch_plan(sxg_poa_handle* h, LaunchPlan& P, PlanRes& R, const int p
     A.blk_off = h->d_blk_off.as<int32_t>(); A.seq_off = h->d_seq_off.as<int64_t>(); A.bases = h->d_bases.as<uint8_t>();
     A.weights = h->has_weights ? h->d_weights.as<uint32_t>() : nullptr;
     A.params = h->d_params.as<sxg_poa_params>(); A.per_block_params = h->per_block_params;
+    A.n_tiles = P.tiles; A.bnd_off256 = (unsigned)(P.bnd_off / 256);   // (make_layout aligns every array to 256 bytes)
     A.work = R.work.as<int32_t>(); A.n_work = (int)P.work.size(); A.queue = R.queue.as<int32_t>();
     A.arena = R.arena.as<uint8_t>(); A.lay = P.lay;
     A.status = h->d_status.as<int32_t>(); A.n_nodes = h->d_nn.as<int32_t>(); A.n_edges = h->d_ne.as<int32_t>();
@@ -1066,8 +1108,8 @@ static void group_pending(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, con
         const BlockMeta& m = h->meta[b];
         LaunchPlan* pl = nullptr;
         for (auto& q : plans)
-            if (q.variant == m.variant && q.cvx == m.cvx && q.sw == m.sw && q.tier == m.tier && q.wide_band == m.wide_band) { pl = &q; break; }
-        if (!pl) { plans.emplace_back(); pl = &plans.back(); pl->variant = m.variant; pl->cvx = m.cvx; pl->sw = m.sw; pl->tier = m.tier; pl->wide_band = m.wide_band; }
+            if (q.variant == m.variant && q.cvx == m.cvx && q.sw == m.sw && q.tier == m.tier && q.wide_band == m.wide_band && q.tiles == m.tiles) { pl = &q; break; }
+        if (!pl) { plans.emplace_back(); pl = &plans.back(); pl->variant = m.variant; pl->cvx = m.cvx; pl->sw = m.sw; pl->tier = m.tier; pl->wide_band = m.wide_band; pl->tiles = m.tiles; }
         pl->work.push_back(b);
     }
     std::sort(plans.begin(), plans.end(), [](const LaunchPlan& a, const LaunchPlan& b) { return a.variant.Lpad() > b.variant.Lpad(); });
@@ -1103,7 +1145,8 @@ static void merge_plans(sxg_poa_handle* h, std::vector<LaunchPlan>& plans) {
             const LaunchPlan &a = plans[i], &b = plans[j];
             // (neighbouring widths: see merge_w2 above)
             const bool join_w2 = merge_w2 && a.variant.NW == b.variant.NW && b.variant.W == class_w2(CLASS_BLOCK, a.variant, a.sw);
-            if (same_kind(a.variant, b.variant) && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
+            // (a launch in column tiles stays on its own: its arenas are laid out for its tile count at its geometry)
+            if (a.tiles == 1 && b.tiles == 1 && same_kind(a.variant, b.variant) && a.variant.RM != 3 && a.cvx == b.cvx && a.sw == b.sw && a.tier == b.tier && a.wide_band == b.wide_band &&
                 (join_w2 || (double)b.variant.Lpad() >= (merge_env > 0 ? merge_env : (a.variant.Lpad() >= 4096 ? 0.92 : 0.75)) * (double)a.variant.Lpad())) {
                 plans[i].work.insert(plans[i].work.end(), b.work.begin(), b.work.end());
                 plans.erase(plans.begin() + (long)j);
@@ -1138,7 +1181,7 @@ static void price_plans(sxg_poa_handle* h, std::vector<LaunchPlan>& plans) {
         const Variant& v = pl.variant;
         for (int b : pl.work)
             h->blk_cost[(size_t)b] = block_cost(h->h_seq_off.data() + h->h_blk_off[b], h->h_blk_off[b + 1] - h->h_blk_off[b], v.RM, v.T(), v.W, v.W2,
-                                                h->seq_done.data() + h->h_blk_off[b]);
+                                                h->seq_done.data() + h->h_blk_off[b], pl.tiles);
         std::stable_sort(pl.work.begin(), pl.work.end(), [&](int a, int b) { return h->blk_cost[(size_t)a] > h->blk_cost[(size_t)b]; });
     }
 }
@@ -1256,6 +1299,15 @@ static int launch_round(sxg_poa_handle* h, std::vector<LaunchPlan>& plans, const
         h->stats.n_slots += (int)plans[i].n_slots;
         h->stats.device_bytes += (uint64_t)plans[i].n_slots * plans[i].lay.total;
         width_stats_of(plans[i], prof, h->wstats, &h->tstats);
+        if (plans[i].tiles > 1) {   // (a tiled launch counts its sweeps and their tiles in SP_TILES)
+            h->tile_blocks += (int64_t)plans[i].work.size();
+            for (int64_t sl = 0; sl < plans[i].n_slots; ++sl) {
+                const unsigned long long w = prof[(size_t)sl * SLOT_PROF_WORDS + SP_TILES];
+                h->tile_sweeps += (int64_t)(w & 0xffffffffull);
+                h->tile_tiles += (int64_t)(w >> 32);
+            }
+            if (dbg) fprintf(stderr, "[sxg]   tiles: %d per row of the arena, %d columns each\n", plans[i].tiles, plans[i].variant.Lpad());
+        }
         if (dbg) debug_plan(plans[i], prof, attempt);
     }
     return SXG_OK;
@@ -1293,7 +1345,7 @@ static int advance_ladders(sxg_poa_handle* h, const std::vector<LaunchPlan>& pla
         } else if (status[b] == ST_RANGE_OVERFLOW || status[b] == ST_BAND_MISS) {
             // one step wider at the same capacity tier: packed -> int16 row words -> int32 row words
             if (m.rm != 1) {
-                classify_block(m, m.rm >= 2 ? 0 : 1, false);
+                classify_block(m, m.rm >= 2 ? 0 : 1, false, h->long_blocks);
                 if (m.fits) again.push_back(b);
                 else status[b] = ST_TOO_LONG;    // (a score range beyond int16 on a sequence beyond SXG_POA_MAX_SEQ_LEN_WIDE)
             } else status[b] = ST_TOO_LONG;      // (unreachable: the int32 sweep reports neither)
@@ -1347,6 +1399,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
     h->stats = sxg_poa_stats{};
     h->wstats = sxg_poa_width_stats{};
     h->tstats = sxg_poa_twin_stats{};
+    h->tile_blocks = h->tile_sweeps = h->tile_tiles = 0;
     const bool dbg = getenv("SXG_POA_DEBUG") != nullptr;
     auto T0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
@@ -2273,6 +2326,12 @@ extern "C" sxg_poa_handle* sxg_poa_group_member(sxg_poa_group* g, int32_t i) {
 extern "C" int sxg_poa_group_set_memory_budget(sxg_poa_group* g, uint64_t bytes_per_member) {
     if (!g) return fail(SXG_E_INVALID, "group is NULL");
     for (sxg_poa_handle* h : g->members) h->mem_budget = bytes_per_member;
+    return SXG_OK;
+}
+
+extern "C" int sxg_poa_group_set_long_blocks(sxg_poa_group* g, int on) {
+    if (!g) return fail(SXG_E_INVALID, "group is NULL");
+    for (sxg_poa_handle* h : g->members) h->long_blocks = on != 0;
     return SXG_OK;
 }
 

@@ -124,6 +124,7 @@ SGD_LDS_NODES = 8192   # SXG_POA_SGD_LDS_NODES: nodes the one-workgroup path of 
 MASH_SORT_TILE = 1024   # SXG_POA_MASH_SORT_TILE: k-mers a workgroup sorts on chip at once
 SPLIT_PANEL = 512   # SXG_POA_SPLIT_PANEL: columns of the second sequence a wavefront sweeps at once
 MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
+MAX_SEQ_LEN_TILED = 49151  # SXG_POA_MAX_SEQ_LEN_TILED: every mode and score set, with set_long_blocks(True)
 ST_TOO_LONG = 5
 MSA_FULL, MSA_TRIMMED = 1, 2   # SXG_MSA_FULL / SXG_MSA_TRIMMED: values of want_msa (True = the full MSA)
 
@@ -136,7 +137,7 @@ EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_km
            "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available", "sxg_poa_get_msa_stats", "sxg_poa_msa_geometry",
            "sxg_poa_group_create", "sxg_poa_group_destroy", "sxg_poa_group_size", "sxg_poa_group_member", "sxg_poa_group_set_memory_budget",
            "sxg_poa_group_batch_run", "sxg_poa_group_batch_upload", "sxg_poa_group_batch_execute", "sxg_poa_group_batch_download",
-           "sxg_poa_group_timing"]
+           "sxg_poa_group_timing", "sxg_poa_set_long_blocks", "sxg_poa_group_set_long_blocks", "sxg_poa_get_tile_stats"]
 COMM_ID_BYTES = 128
 NOT_ROOT = 1
 
@@ -171,6 +172,9 @@ def load_library(build_if_missing=True):
     L.sxg_poa_get_width_stats.argtypes = [vp, C.POINTER(WidthStats)]
     L.sxg_poa_get_twin_stats.argtypes = [vp, C.POINTER(TwinStats)]
     L.sxg_poa_set_memory_budget.argtypes = [vp, C.c_uint64]
+    L.sxg_poa_set_long_blocks.argtypes = [vp, C.c_int]
+    L.sxg_poa_group_set_long_blocks.argtypes = [vp, C.c_int]
+    L.sxg_poa_get_tile_stats.argtypes = [vp, _i64p, _i64p, _i64p]
     L.sxg_poa_get_msa_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.sxg_poa_msa_geometry.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.sxg_poa_msa_geometry.restype = None
@@ -284,6 +288,19 @@ class PoaEngine:
 
     def set_memory_budget(self, nbytes):
         self.lib.sxg_poa_set_memory_budget(self.h, int(nbytes))
+
+    def set_long_blocks(self, on):
+        """sxg_poa_set_long_blocks: with the switch on (default off) a block whose 32-bit sweep no geometry covers runs in column
+        tiles instead of answering ST_TOO_LONG, up to MAX_SEQ_LEN_TILED letters; read by the next upload."""
+        if self.lib.sxg_poa_set_long_blocks(self.h, int(bool(on))):
+            raise self._err("sxg_poa_set_long_blocks")
+
+    def tile_stats(self):
+        """sxg_poa_get_tile_stats of the last execute: blocks of its tiled launches, their sweeps, the tiles those swept."""
+        b, s, t = C.c_int64(), C.c_int64(), C.c_int64()
+        if self.lib.sxg_poa_get_tile_stats(self.h, C.byref(b), C.byref(s), C.byref(t)):
+            raise self._err("sxg_poa_get_tile_stats")
+        return {"blocks": b.value, "sweeps": s.value, "tiles": t.value}
 
     # -- flat batch -----------------------------------------------------------------
     def _mk_in(self, bases, seq_off, blk_off, weights, params, want_consensus, want_msa, block_graph=0, bg_trim=None,
@@ -788,6 +805,19 @@ class PoaGroup:
 
     def set_memory_budget(self, nbytes_per_member):
         self.lib.sxg_poa_group_set_memory_budget(self.h, int(nbytes_per_member))
+
+    def set_long_blocks(self, on):
+        """PoaEngine.set_long_blocks on every member."""
+        if self.lib.sxg_poa_group_set_long_blocks(self.h, int(bool(on))):
+            raise self._err("sxg_poa_group_set_long_blocks")
+
+    def tile_stats(self):
+        """PoaEngine.tile_stats, summed over the members."""
+        tot = {"blocks": 0, "sweeps": 0, "tiles": 0}
+        for i in range(len(self)):
+            for k, v in self.member(i).tile_stats().items():
+                tot[k] += v
+        return tot
 
     def member(self, i):
         """Member i as a PoaEngine (owned by the group): its stats, and the split, identity and SGD calls, which stay
