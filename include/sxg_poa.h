@@ -51,6 +51,8 @@ extern "C" {
  *    sxg_poa_get_msa_stats.
  * 5 (addition, no number change): sxg_poa_path_sgd_order and struct sxg_poa_sgd_in -- the path-guided SGD node order of prep
  *    (src/prep.cpp:11-163) on the device, decree Y.
+ * 5 (addition, no number change: no struct or existing entry point changed): sxg_poa_repeat_scan_batch and struct
+ *    sxg_poa_repeat_in -- the tandem-repeat scan of the cutting half of break_blocks (src/breaks.cpp:224-272), decree R.
  * 5 (addition, no number change): sxg_poa_kmer_jaccard_batch, sxg_poa_split_mash_batch and struct sxg_poa_split_mash -- the
  *    mash-based branch of the identity split (src/breaks.cpp:388-471) on the device, decrees M1-M5.
  * 5 (addition, no number change: no struct or existing entry point changed): sxg_poa_pair_identity_batch, sxg_poa_split_batch,
@@ -564,6 +566,46 @@ typedef struct sxg_poa_identity_in {
 /* caller-allocated [n_blocks] each */
 int sxg_poa_block_identity_batch(sxg_poa_handle *h, const sxg_poa_identity_in *in,
                                  int32_t *n_used, int32_t *inter, int32_t *uni, int32_t *status);
+
+/* The tandem-repeat scan of the cutting half of break_blocks (src/breaks.cpp:224-272) for every sequence of a batch, decree R of
+ * DESIGN.md section 9 (an addition to ABI 5, no struct changed).  The scan itself is include/sxg_smooth.h's (the stand-in for
+ * sautocorr::repeat, itself a decree: match-fraction autocorrelation over sampled positions, z-score across the lags); this call
+ * computes it in exact integers plus one short double-precision pass whose every operation is pinned:
+ *   R1  letters are the bytes as they stand in the graph, compared for equality only: case matters and N == N, as on the host.
+ *   R2  a sequence of n bytes with n >= 2 min_copy has the lags L = min_copy ... hi, hi = min(max_copy, n - min_copy), n_lags =
+ *       hi - min_copy + 1; match(L) = #{ i = 0, stride, 2 stride, ... < n - L : s[i] == s[i + L] }, cnt(L) = ceil((n - L) / stride).
+ *       The device produces match as 32-bit integers; nothing about the counts is approximate or depends on an order.
+ *   R3  a second kernel finishes each sequence in IEEE double, sums in lag order k = 0 ... n_lags - 1, one rounding per operation
+ *       (its translation unit is built without contraction): r[k] = (double)match / (double)cnt; mean = (sum of r[k], from 0.0) /
+ *       n_lags; var = sum of (r[k] - mean) * (r[k] - mean); it returns best = the first k of the greatest r[k], dev = r[best] -
+ *       mean and v = var / n_lags.  The host does the three operations that remain: sd = sqrt(v); sd == 0 means no repeat; a
+ *       repeat of length min_copy + best is reported iff dev / sd >= min_z -- the host scan's own operations on best (one
+ *       function of smoothxg_amd/csrc/poa_repeat.h, sxg_repeat_decide, serves both).
+ *   R4  "first lag of greatest r" is the host scan's "first lag of greatest z", z[k] = (r[k] - mean) / sd: rounding is monotone,
+ *       so z is non-decreasing in r, and the two can differ only if two DIFFERENT r round to one z.  Two different r = m / c
+ *       differ by at least 1 / c_max^2 >= 1 / n^2, less 2^-53 for their own roundings; the subtraction of the mean adds at most
+ *       2^-53 (|r - mean| <= 1), the division by sd <= 1/2 doubles the gap, and its rounding adds at most 2^-53 |z| to either z
+ *       with |z| <= sqrt(n_lags) <= sqrt(n).  So the z differ whenever 1 / n^2 > 2^-52 + sqrt(n) 2^-53, which holds with a factor
+ *       of 8 to spare up to n = SXG_POA_REPEAT_MAX_LEN = 2^20.  A longer sequence gets SXG_ST_TOO_LONG (n_lags = 0) and the call
+ *       returns SXG_E_BLOCK, the other sequences being valid: the host scans it itself.
+ * A work item is (sequence, tile of 256 consecutive lags), one wavefront, the items of a round sorted largest first and dealt
+ * to the workgroups in that order; a lane owns four consecutive lags, reads them as one word per sample and compares it with the
+ * replicated sampled letter; the counts leave as plain stores.  No atomics, no cooperative launch, no grid-wide wait, no captured
+ * graph: two launches per round on the handle's stream.  The letters (as they came, plus 16 bytes per sequence and 8 per item)
+ * and the counts (4 bytes per lag and sequence) come out of the handle's memory budget: sequences run in rounds, in order, as
+ * many as their counts fit; a sequence whose counts alone do not fit is SXG_E_NOMEM.  A sequence shorter than 2 min_copy is
+ * SXG_ST_OK with n_lags = 0.  SXG_E_INVALID: min_copy = 0, stride = 0, max_copy < min_copy.  match: NULL, or the counts of every
+ * scanned sequence, sequence s's n_lags[s] counts at the prefix sum of the n_lags before it (sxg_repeat_match_offsets of
+ * poa_repeat.h); for tests.  The call runs inside a ROCTx range; sxg_poa_stats after it: kernel_ms the sum of the kernels,
+ * dp_launches their number (2 per round), n_slots the workgroups of the widest counting launch, device_bytes the buffers. */
+#define SXG_POA_REPEAT_MAX_LEN (1 << 20)
+typedef struct sxg_poa_repeat_in {
+    int64_t n_seqs; const int64_t *seq_off; const uint8_t *bases;   /* [n_seqs + 1], [seq_off[n_seqs]] the letters as they are */
+    uint64_t min_copy, max_copy, stride;                            /* src/main.cpp:285-286,458: 1000, 20000, 50 */
+} sxg_poa_repeat_in;
+/* caller-allocated [n_seqs] each; match: NULL or [sum of n_lags] */
+int sxg_poa_repeat_scan_batch(sxg_poa_handle *h, const sxg_poa_repeat_in *in, int32_t *n_lags, int32_t *best, double *dev, double *v,
+                              int32_t *status, int32_t *match);
 
 /* The node order of prep (src/prep.cpp:11-163: odgi's path_linear_sgd_order, called from src/main.cpp:423-433 before every
  * iteration unless -n), decree Y of DESIGN.md section 9.  odgi is absent from the snapshot and its hogwild updates are not

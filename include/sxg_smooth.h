@@ -136,6 +136,21 @@ int sxg_blockset_break(const sxg_graph *g, const sxg_blockset *in, uint64_t max_
 int sxg_blockset_break_ex(const sxg_graph *g, const sxg_blockset *in, uint64_t max_poa_length, int break_repeats,
                           uint64_t min_copy_length, uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride,
                           int order_paths_from_longest, sxg_blockset **out);
+/* The same cut with the repeat scan behind a provider, and the two counts the reference prints (an addition to ABI 2, no struct
+ * changed).  Scan provider: exactly sxg_poa_repeat_scan_batch's contract (decree R of include/sxg_poa.h: the match count of every
+ * lag in exact integers, then best / dev / v of a pinned double-precision pass), ctx is its handle.  sxg_blockset_break_scan finds
+ * the blocks that will be cut, collects the range sequences of at least 2 * min_copy_length bases of ALL of them (step
+ * orientation, the letters as they stand), makes ONE provider call on the calling thread, turns every (best, dev, v) into a repeat
+ * length with the host scan's own three operations (sd = sqrt(v); none if sd == 0; min_copy_length + best iff dev / sd >=
+ * min_autocorr_z) and cuts as sxg_blockset_break_ex does.  *n_cut: the blocks cut, *n_repeat: those of them cut at a repeat
+ * (src/breaks.cpp:220,265,596); *n_host: the sequences the provider reported with a status other than SXG_ST_OK, which the host
+ * scanned itself; any of the three may be NULL.  scan == NULL: sxg_blockset_break_ex with break_repeats = 1 and the counts
+ * (*n_host = 0).  A provider that returns anything but SXG_OK / SXG_E_BLOCK, a wrong n_lags, or best out of range fails the call. */
+typedef int (*sxg_repeat_fn)(void *ctx, const sxg_poa_repeat_in *in, int32_t *n_lags, int32_t *best, double *dev, double *v,
+                             int32_t *status, int32_t *match);
+int sxg_blockset_break_scan(const sxg_graph *g, const sxg_blockset *in, uint64_t max_poa_length, uint64_t min_copy_length,
+                            uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest,
+                            sxg_repeat_fn scan, void *ctx, sxg_blockset **out, int64_t *n_cut, int64_t *n_repeat, int64_t *n_host);
 /* The splitting half of break_blocks, src/breaks.cpp:335-586 (-I / --block-id-min, -R / --block-ratio-min and the dedup
  * depth; an addition to ABI 2, no struct changed): a block whose sequences fall into more than one identity group becomes one
  * block per group.  Decree P3 of DESIGN.md section 9, statement by statement as the reference: nothing happens to a block

@@ -30,6 +30,7 @@
 #include "poa_split.hip.h"         // the identity split: argument structs and launchers (kernels in kern_split.hip)
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
 #include "poa_identity.hip.h"      // the identity estimate of -a on those sets: all pairs of a block, the percentile's pair (kern_split.hip)
+#include "poa_repeat.hip.h"        // the tandem-repeat scan of the cutting half of break_blocks: counts per lag, then the double pass (kern_repeat.hip)
 #include "poa_sgd.hip.h"           // the path-guided SGD node order of prep: argument struct and launchers (kernels in kern_sgd.hip)
 #include "poa_msa.hip.h"           // the trimmed MSA (want_msa == SXG_MSA_TRIMMED): argument structs and launchers (kernels in kern_msa.hip)
 
@@ -3138,6 +3139,142 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
         h->stats.dp_launches = launches;   // the sketch + (pairs, select) of every round
     }
     if (any_failed) return fail(SXG_E_BLOCK, "a block holds a sequence longer than SXG_POA_MAX_SEQ_LEN");
+    return SXG_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The tandem-repeat scan of the cutting half of break_blocks (src/breaks.cpp:224-272): decree R (include/sxg_poa.h, DESIGN.md
+// section 9).  Kernels in poa_repeat.hip.h / kern_repeat.hip on the arithmetic of poa_repeat.h; here the validation, the work items
+// (largest first), the rounds and the timing.  Memory: the letters as they came, their offsets and the item list (uploaded once)
+// and the counts of a round (4 bytes per lag and sequence) share the handle's budget; sequences go round after round, in order, as
+// many as their counts fit; a sequence whose counts alone do not fit is SXG_E_NOMEM.  Everything is enqueued on the handle's
+// stream without a host wait in between: the counts' buffer is reused by the next round in stream order.
+static_assert(SXG_POA_REPEAT_MAX_LEN == SXG_REPEAT_MAX_LEN, "length limit of the header");
+extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat_in* in, int32_t* n_lags, int32_t* best, double* dev, double* v,
+                                         int32_t* status, int32_t* match) {
+    if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
+    const int64_t ns = in->n_seqs;
+    if (ns < 0 || ns > 0x7fffffff || (ns > 0 && (!in->seq_off || !n_lags || !best || !dev || !v || !status))) return fail(SXG_E_INVALID, "repeat_scan: bad argument");
+    if (in->min_copy == 0 || in->stride == 0 || in->max_copy < in->min_copy) return fail(SXG_E_INVALID, "repeat_scan: min_copy and stride must be positive and max_copy at least min_copy");
+    if (ns > 0 && in->seq_off[0] != 0) return fail(SXG_E_INVALID, "seq_off[0] must be 0");
+    for (int64_t s = 0; s < ns; ++s)
+        if (in->seq_off[s + 1] < in->seq_off[s]) return fail(SXG_E_INVALID, "seq_off not monotone");
+    const int64_t nbases = ns ? in->seq_off[ns] : 0;
+    if (nbases > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
+    RoctxRange range("sxg_poa_repeat_scan_batch");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    // what the device sees is 32-bit: a stride or a max_copy beyond the length limit, clamped to it, changes no count
+    const int64_t lim = SXG_REPEAT_MAX_LEN;
+    const int64_t min_copy = (int64_t)std::min<uint64_t>(in->min_copy, (uint64_t)lim), max_copy = (int64_t)std::min<uint64_t>(in->max_copy, (uint64_t)lim),
+                  stride = (int64_t)std::min<uint64_t>(in->stride, (uint64_t)lim);
+    std::vector<int64_t> match_off((size_t)ns + 1, 0);   // of the sequences the device scans: a declined one has no counts
+    std::vector<int32_t> work;
+    bool any_failed = false;
+    int64_t max_lags = 0;
+    for (int64_t s = 0; s < ns; ++s) {
+        const int64_t n = in->seq_off[s + 1] - in->seq_off[s];
+        n_lags[s] = best[s] = 0; dev[s] = v[s] = 0.0;
+        status[s] = SXG_ST_OK;
+        int64_t lags = 0;
+        if ((uint64_t)n / 2 >= in->min_copy) {   // (n < 2 min_copy: no lags, SXG_ST_OK)
+            if (n > lim) { status[s] = SXG_ST_TOO_LONG; any_failed = true; }   // R4: the host scans it itself
+            else { lags = sxg_repeat_n_lags(n, min_copy, max_copy); n_lags[s] = (int32_t)lags; work.push_back((int32_t)s); }
+        }
+        match_off[(size_t)s + 1] = match_off[(size_t)s] + lags;   // (= sxg_repeat_match_offsets: the caller's layout of `match`)
+        max_lags = std::max(max_lags, lags);
+    }
+    if (!work.empty()) {
+        // the items of every sequence, and the rounds: consecutive sequences while their counts fit
+        int64_t n_items_all = 0;
+        for (int32_t s : work) n_items_all += sxg_repeat_n_tiles(n_lags[s]);
+        if (n_items_all > 0x3fffffff) return fail(SXG_E_INVALID, "repeat_scan: too many work items for one call");
+        const uint64_t budget = arena_budget(h);
+        const uint64_t fixed_bytes = (uint64_t)nbases + 16ull * (uint64_t)(ns + 1) + 8ull * (uint64_t)n_items_all + 4ull * work.size() + 20ull * (uint64_t)ns;
+        if (fixed_bytes + 4ull * (uint64_t)max_lags > budget)
+            return fail(SXG_E_NOMEM, "memory budget too small for the letters (" + std::to_string(fixed_bytes) + " bytes) and the counts of the longest sequence (" +
+                                         std::to_string(4 * max_lags) + " bytes)");
+        const int64_t counts_cap = (int64_t)((budget - fixed_bytes) / 4);
+        struct round_t { size_t w0, w1; int64_t i0, i1; };
+        std::vector<round_t> rounds;
+        std::vector<int32_t> items;
+        items.reserve(2 * (size_t)n_items_all);
+        int64_t round_counts = 0;
+        for (size_t w0 = 0; w0 < work.size();) {
+            size_t w1 = w0;
+            const int64_t base = match_off[(size_t)work[w0]];
+            while (w1 < work.size() && match_off[(size_t)work[w1] + 1] - base <= counts_cap) ++w1;
+            round_counts = std::max(round_counts, match_off[(size_t)work[w1 - 1] + 1] - base);
+            // largest first: an item's work is the samples of its first lag times its lags
+            std::vector<std::pair<int64_t, std::pair<int32_t, int32_t>>> order;
+            for (size_t w = w0; w < w1; ++w) {
+                const int32_t s = work[w];
+                const int32_t n = (int32_t)(in->seq_off[s + 1] - in->seq_off[s]);
+                for (int32_t t = 0; t < sxg_repeat_n_tiles(n_lags[s]); ++t) {
+                    const int32_t k0 = t * SXG_REPEAT_TILE_LAGS;
+                    order.push_back({-(int64_t)sxg_repeat_cnt(n, (int32_t)min_copy + k0, (int32_t)stride) * std::min<int32_t>(SXG_REPEAT_TILE_LAGS, n_lags[s] - k0), {s, t}});
+                }
+            }
+            std::sort(order.begin(), order.end());
+            const int64_t i0 = (int64_t)items.size() / 2;
+            for (auto& o : order) { items.push_back(o.second.first); items.push_back(o.second.second); }
+            rounds.push_back(round_t{w0, w1, i0, (int64_t)items.size() / 2});
+            w0 = w1;
+        }
+        DevBuf d_bases, d_seq_off, d_match_off, d_items, d_work, d_match, d_best, d_dev, d_v;
+        int rc;
+        if ((rc = d_bases.ensure((size_t)std::max<int64_t>(nbases, 1))) || (rc = d_seq_off.ensure(8 * (size_t)(ns + 1))) || (rc = d_match_off.ensure(8 * (size_t)(ns + 1))) ||
+            (rc = d_items.ensure(4 * items.size())) || (rc = d_work.ensure(4 * work.size())) || (rc = d_match.ensure(4 * (size_t)std::max<int64_t>(round_counts, 1))) ||
+            (rc = d_best.ensure(4 * (size_t)ns)) || (rc = d_dev.ensure(8 * (size_t)ns)) || (rc = d_v.ensure(8 * (size_t)ns)))
+            return rc;
+        if (nbases > 0) HIPCHK(hipMemcpyAsync(d_bases.p, in->bases, (size_t)nbases, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_seq_off.p, in->seq_off, 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_match_off.p, match_off.data(), 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_items.p, items.data(), 4 * items.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_work.p, work.data(), 4 * work.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(d_best.p, 0, 4 * (size_t)ns, h->stream));
+        HIPCHK(hipMemsetAsync(d_dev.p, 0, 8 * (size_t)ns, h->stream));
+        HIPCHK(hipMemsetAsync(d_v.p, 0, 8 * (size_t)ns, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));   // (the uploads read the caller's and this frame's memory; the kernels' time starts after them)
+        int per_cu = 1;
+        sxg_repeat_occupancy(&per_cu);
+        int64_t groups_max = 0;
+        uint64_t launches = 0;
+        float ms = 0;
+        if (int rc = timer_start(h)) return rc;
+        for (const round_t& r : rounds) {
+            RepeatArgs A;
+            A.bases = d_bases.as<uint8_t>(); A.seq_off = d_seq_off.as<int64_t>(); A.match_off = d_match_off.as<int64_t>();
+            A.match_base = match_off[(size_t)work[r.w0]]; A.match = d_match.as<int32_t>();
+            A.items = d_items.as<int32_t>() + 2 * r.i0; A.n_items = (int32_t)(r.i1 - r.i0);
+            A.work = d_work.as<int32_t>() + r.w0; A.n_work = (int32_t)(r.w1 - r.w0);
+            A.min_copy = (int32_t)min_copy; A.max_copy = (int32_t)max_copy; A.stride = (int32_t)stride;
+            A.best = d_best.as<int32_t>(); A.dev = d_dev.as<double>(); A.v = d_v.as<double>();
+            const int64_t groups = std::min<int64_t>(A.n_items, (int64_t)std::max(h->num_cu, 1) * per_cu);
+            groups_max = std::max(groups_max, groups);
+            sxg_repeat_launch_count(A, (int)groups, h->stream);
+            HIPCHK(hipGetLastError());
+            sxg_repeat_launch_stats(A, h->stream);
+            HIPCHK(hipGetLastError());
+            launches += 2;
+            if (match)   // (tests only: the round's counts, sequence by sequence before the next round overwrites them)
+                for (size_t w = r.w0; w < r.w1; ++w) {
+                    const int32_t s = work[w];
+                    HIPCHK(hipMemcpyAsync(match + match_off[(size_t)s], d_match.as<int32_t>() + (match_off[(size_t)s] - A.match_base), 4 * (size_t)n_lags[s], hipMemcpyDeviceToHost, h->stream));
+                }
+        }
+        if (int rc = timer_stop(h, &ms)) return rc;
+        std::vector<int32_t> got_best((size_t)ns);
+        std::vector<double> got_dev((size_t)ns), got_v((size_t)ns);
+        HIPCHK(hipMemcpy(got_best.data(), d_best.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(got_dev.data(), d_dev.p, 8 * (size_t)ns, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(got_v.data(), d_v.p, 8 * (size_t)ns, hipMemcpyDeviceToHost));
+        for (int32_t s : work) { best[s] = got_best[(size_t)s]; dev[s] = got_dev[(size_t)s]; v[s] = got_v[(size_t)s]; }
+        h->stats.kernel_ms = ms; h->stats.dom_kernel_ms = ms; h->stats.dp_launches = launches; h->stats.n_slots = (int32_t)groups_max;
+        h->stats.device_bytes = d_bases.cap + d_seq_off.cap + d_match_off.cap + d_items.cap + d_work.cap + d_match.cap + d_best.cap + d_dev.cap + d_v.cap;
+        h->stats.dom_threads = SXG_REPEAT_WAVE;
+    }
+    if (any_failed) return fail(SXG_E_BLOCK, "a sequence is longer than SXG_POA_REPEAT_MAX_LEN");
     return SXG_OK;
 }
 

@@ -11,6 +11,7 @@
 // odgi's unchop / topological_order / to_gfa are absent from the reference snapshot; they are
 // restated by decree and mirrored line for line by oracle/smooth_oracle.py.
 #include "../../include/sxg_smooth.h"
+#include "poa_repeat.h"  // decree R: the lag range of a sequence and the host tail of the repeat scan (HIP-free)
 #include "prep_host.h"   // flatten, schedule, apply, chop of sxg_graph_prep (a header of its own: tests build it stand-alone)
 
 #include <omp.h>
@@ -2919,7 +2920,7 @@ static double repeat_length(const std::string& seq, uint64_t min_copy, uint64_t 
     mean /= (double)r.size();
     double var = 0.0;
     for (double v : r) var += (v - mean) * (v - mean);
-    const double sd = std::sqrt(var / (double)r.size());
+    const double v = var / (double)r.size(), sd = std::sqrt(v);
     if (sd == 0.0) return 0.0;
     int64_t best = -1;
     double best_z = 0.0;
@@ -2927,7 +2928,7 @@ static double repeat_length(const std::string& seq, uint64_t min_copy, uint64_t 
         const double z = (r[k] - mean) / sd;
         if (best < 0 || z > best_z) { best = (int64_t)k; best_z = z; }
     }
-    return best_z >= min_z ? (double)(min_copy + (uint64_t)best) : 0.0;
+    return sxg_repeat_decide((int64_t)min_copy, best, r[(size_t)best] - mean, v, min_z);   // decree R3: sd, sd == 0, dev / sd >= min_z -- best_z again
 }
 
 }  // extern "C"
@@ -2937,24 +2938,93 @@ static double repeat_length(const std::string& seq, uint64_t min_copy, uint64_t 
 // ranges of at least max_poa_length bases into pieces of just over that (a piece is closed by the step that takes it past
 // the limit) -- and re-ordered by length.  Splitting by identity (:335+) stays off as in the defaults
 // (block_group_identity = 0, src/main.cpp:316-320).
+static bool block_is_cut(const std::vector<path_range_t>& blk, uint64_t max_poa_length) {
+    bool to_break = false;
+    for (auto& r : blk) if (r.length > max_poa_length) { to_break = true; break; }
+    return blk.size() > 1 && to_break;
+}
+// The repeat scan of every range of every block that will be cut, through the scan provider (decree R): the range sequences of
+// at least 2 min_copy bases in ONE call on this thread, a sequence the provider declines scanned here.  found[k]: the repeat
+// lengths block k's ranges hold, in range order (what the loop of blockset_break would have pushed).
+static int scan_repeats(const sxg_graph* g, const sxg_blockset* in, uint64_t max_poa_length, uint64_t min_copy, uint64_t max_copy, double min_z, uint64_t stride,
+                        sxg_repeat_fn scan, void* ctx, std::vector<std::vector<double>>& found, int64_t* n_host) {
+    struct cand_t { int64_t blk; size_t range; };
+    std::vector<cand_t> cand;
+    std::vector<int64_t> seq_off{0};
+    for (int64_t k = 0; k < (int64_t)in->blocks.size(); ++k) {
+        const auto& blk = in->blocks[(size_t)k];
+        if (!block_is_cut(blk, max_poa_length)) continue;
+        for (size_t r = 0; r < blk.size(); ++r) {
+            const uint64_t len = g->pos[blk[r].path][blk[r].end] - g->pos[blk[r].path][blk[r].begin];
+            if (len >= 2 * min_copy) { cand.push_back(cand_t{k, r}); seq_off.push_back(seq_off.back() + (int64_t)len); }
+        }
+    }
+    const int64_t ns = (int64_t)cand.size();
+    if (ns == 0) return SXG_OK;
+    uvec<uint8_t> bases;
+    bases.resize((size_t)seq_off.back());
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t s = 0; s < ns; ++s) {
+        const path_range_t& r = in->blocks[(size_t)cand[(size_t)s].blk][cand[(size_t)s].range];
+        uint8_t* dst = bases.data() + seq_off[(size_t)s];
+        for (uint64_t st = r.begin; st != r.end; ++st) {   // R1: the letters as they stand, in step orientation
+            const std::string q = g->sequence(g->steps[r.path][st]);
+            memcpy(dst, q.data(), q.size());
+            dst += q.size();
+        }
+    }
+    sxg_poa_repeat_in ri;
+    memset(&ri, 0, sizeof(ri));
+    ri.n_seqs = ns; ri.seq_off = seq_off.data(); ri.bases = bases.data(); ri.min_copy = min_copy; ri.max_copy = max_copy; ri.stride = stride;
+    std::vector<int32_t> n_lags((size_t)ns, 0), best((size_t)ns, 0), status((size_t)ns, 0);
+    std::vector<double> dev((size_t)ns, 0.0), v((size_t)ns, 0.0), rl((size_t)ns, 0.0);
+    const int rc = scan(ctx, &ri, n_lags.data(), best.data(), dev.data(), v.data(), status.data(), nullptr);
+    if (rc != SXG_OK && rc != SXG_E_BLOCK) return fail(rc, "repeat scan provider failed");
+    std::vector<char> on_host((size_t)ns, 0);
+    for (int64_t s = 0; s < ns; ++s) {
+        if (status[(size_t)s] != SXG_ST_OK) { on_host[(size_t)s] = 1; ++*n_host; continue; }
+        const int64_t want = sxg_repeat_n_lags(seq_off[(size_t)s + 1] - seq_off[(size_t)s], (int64_t)min_copy, (int64_t)std::min<uint64_t>(max_copy, 1ull << 62));
+        if (n_lags[(size_t)s] != want || best[(size_t)s] < 0 || best[(size_t)s] >= want)
+            return fail(SXG_E_INVALID, "repeat scan provider returned n_lags or best out of range for sequence " + std::to_string(s));
+        rl[(size_t)s] = sxg_repeat_decide((int64_t)min_copy, best[(size_t)s], dev[(size_t)s], v[(size_t)s], min_z);
+    }
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t s = 0; s < ns; ++s)
+        if (on_host[(size_t)s])
+            rl[(size_t)s] = repeat_length(std::string((const char*)bases.data() + seq_off[(size_t)s], (size_t)(seq_off[(size_t)s + 1] - seq_off[(size_t)s])), min_copy, max_copy, min_z, stride);
+    for (int64_t s = 0; s < ns; ++s)
+        if (rl[(size_t)s] > 0) found[(size_t)cand[(size_t)s].blk].push_back(rl[(size_t)s]);
+    return SXG_OK;
+}
+// scan != nullptr: the repeat lengths come from scan_repeats (one provider call) instead of the loop's own repeat_length calls.
+// n_cut / n_repeat: the blocks cut and those of them cut at a repeat (src/breaks.cpp:220,265), n_host: the sequences the provider
+// declined; any of them may be NULL.
 static int blockset_break(const sxg_graph* g, const sxg_blockset* in, uint64_t max_poa_length, bool break_repeats, uint64_t min_copy_length,
-                          uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest, sxg_blockset** out) {
+                          uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest, sxg_blockset** out,
+                          sxg_repeat_fn scan = nullptr, void* scan_ctx = nullptr, int64_t* n_cut = nullptr, int64_t* n_repeat = nullptr, int64_t* n_host = nullptr) {
     if (!g || !in || !out) return fail(SXG_E_INVALID, "NULL argument");
     if (break_repeats && (min_copy_length == 0 || autocorr_stride == 0 || max_copy_length < min_copy_length)) return fail(SXG_E_INVALID, "bad repeat parameters");
-    sxg_blockset* bs = new sxg_blockset();
     const int64_t nb = (int64_t)in->blocks.size();
+    std::vector<std::vector<double>> found;
+    int64_t declined = 0, cut = 0, with_repeat = 0;
+    if (break_repeats && scan) {
+        if (min_copy_length > (1ull << 62)) return fail(SXG_E_INVALID, "bad repeat parameters");
+        found.resize((size_t)nb);
+        if (int rc = scan_repeats(g, in, max_poa_length, min_copy_length, max_copy_length, min_autocorr_z, autocorr_stride, scan, scan_ctx, found, &declined)) return rc;
+    }
+    sxg_blockset* bs = new sxg_blockset();
     bs->blocks.resize((size_t)nb);
-#pragma omp parallel for schedule(dynamic, 1)
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : cut, with_repeat)
     for (int64_t k = 0; k < nb; ++k) {
         const auto& blk = in->blocks[(size_t)k];
-        bool to_break = false;
-        for (auto& r : blk) if (r.length > max_poa_length) { to_break = true; break; }
-        if (!(blk.size() > 1 && to_break)) { bs->blocks[(size_t)k] = blk; continue; }
+        if (!block_is_cut(blk, max_poa_length)) { bs->blocks[(size_t)k] = blk; continue; }
+        ++cut;
         uint64_t cut_length = max_poa_length;
         bool found_repeat = false;
         if (break_repeats) {
             std::vector<double> lengths;
-            for (auto& r : blk) {
+            if (scan) lengths = found[(size_t)k];
+            else for (auto& r : blk) {
                 std::string seq;
                 for (uint64_t st = r.begin; st != r.end; ++st) seq += g->sequence(g->steps[r.path][st]);
                 if (seq.size() >= 2 * min_copy_length) {
@@ -2966,6 +3036,7 @@ static int blockset_break(const sxg_graph* g, const sxg_blockset* in, uint64_t m
                 double total = 0.0;
                 for (double v : lengths) total += v;
                 found_repeat = true;
+                ++with_repeat;
                 cut_length = (uint64_t)std::round(total / (double)lengths.size() / 2.0);
             }
         }
@@ -2988,6 +3059,9 @@ static int blockset_break(const sxg_graph* g, const sxg_blockset* in, uint64_t m
         bs->blocks[(size_t)k] = chopped;
     }
     *out = bs;
+    if (n_cut) *n_cut = cut;
+    if (n_repeat) *n_repeat = with_repeat;
+    if (n_host) *n_host = declined;
     return SXG_OK;
 }
 extern "C" {
@@ -3174,6 +3248,14 @@ int sxg_smooth_maf_gfa_device_rows(const sxg_graph* g, const sxg_blockset* b, co
 int sxg_smooth_maf_gfa(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
                        sxg_poa_free_fn fre, void* ctx, char** out_gfa, char** out_maf, int64_t* n_flipped) {
     return sxg_smooth_maf_gfa_adaptive(g, b, p, mp, run, fre, ctx, nullptr, nullptr, out_gfa, out_maf, n_flipped);
+}
+
+// ... with the repeat scan behind a provider (decree R) and the two counts the reference prints; scan == NULL: sxg_blockset_break_ex with break_repeats on
+int sxg_blockset_break_scan(const sxg_graph* g, const sxg_blockset* in, uint64_t max_poa_length, uint64_t min_copy_length, uint64_t max_copy_length,
+                            double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest, sxg_repeat_fn scan, void* ctx,
+                            sxg_blockset** out, int64_t* n_cut, int64_t* n_repeat, int64_t* n_host) {
+    return guarded([&] { return blockset_break(g, in, max_poa_length, true, min_copy_length, max_copy_length, min_autocorr_z, autocorr_stride, order_paths_from_longest, out,
+                                               scan, ctx, n_cut, n_repeat, n_host); });
 }
 
 int sxg_blockset_split(const sxg_graph* g, const sxg_blockset* in, double block_group_identity, double length_ratio_min, uint64_t min_dedup_depth,

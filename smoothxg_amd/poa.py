@@ -113,6 +113,12 @@ class IdentityIn(C.Structure):
                 ("min_len", C.c_int32), ("percentile", C.c_double)]
 
 
+class RepeatIn(C.Structure):
+    """sxg_poa_repeat_in: a flat set of sequences (the letters as they are) and the parameters of the tandem-repeat scan (decree R)."""
+    _fields_ = [("n_seqs", C.c_int64), ("seq_off", _i64p), ("bases", _u8p), ("min_copy", C.c_uint64), ("max_copy", C.c_uint64),
+                ("stride", C.c_uint64)]
+
+
 class SgdIn(C.Structure):
     """sxg_poa_sgd_in: the flattened graph, the schedule and the seed of the path-guided SGD node order (decree Y)."""
     _fields_ = [("n_nodes", C.c_int64), ("node_len", _i32p), ("n_paths", C.c_int64), ("path_off", _i64p), ("step_node", _i32p),
@@ -124,11 +130,12 @@ SGD_LDS_NODES = 8192   # SXG_POA_SGD_LDS_NODES: nodes the one-workgroup path of 
 MASH_SORT_TILE = 1024   # SXG_POA_MASH_SORT_TILE: k-mers a workgroup sorts on chip at once
 SPLIT_PANEL = 512   # SXG_POA_SPLIT_PANEL: columns of the second sequence a wavefront sweeps at once
 MAX_SEQ_LEN = 26623  # SXG_POA_MAX_SEQ_LEN
+REPEAT_MAX_LEN = 1 << 20   # SXG_POA_REPEAT_MAX_LEN: the longest sequence the repeat scan takes (decree R4)
 MAX_SEQ_LEN_TILED = 49151  # SXG_POA_MAX_SEQ_LEN_TILED: every mode and score set, with set_long_blocks(True)
 ST_TOO_LONG = 5
 MSA_FULL, MSA_TRIMMED = 1, 2   # SXG_MSA_FULL / SXG_MSA_TRIMMED: values of want_msa (True = the full MSA)
 
-EXPORTS = ["sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_compute_units", "sxg_poa_last_error", "sxg_poa_create",
+EXPORTS = ["sxg_poa_repeat_scan_batch", "sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_compute_units", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
            "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_get_twin_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
@@ -211,6 +218,7 @@ def load_library(build_if_missing=True):
     L.sxg_poa_split_free.restype = None
     L.sxg_poa_block_identity_batch.argtypes = [vp, C.POINTER(IdentityIn), _i32p, _i32p, _i32p, _i32p]
     L.sxg_poa_path_sgd_order.argtypes = [vp, C.POINTER(SgdIn), _i32p, _i64p]
+    L.sxg_poa_repeat_scan_batch.argtypes = [vp, C.POINTER(RepeatIn), _i32p, _i32p, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i32p]
     L.sxg_xxh64.restype = C.c_uint64
     L.sxg_xxh64.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64]
     _lib = L
@@ -679,6 +687,31 @@ class PoaEngine:
         if rc and (check or rc != -4):
             raise self._err("sxg_poa_block_identity_batch")
         return used[:nb], inter[:nb], uni[:nb], st[:nb]
+
+    # -- the tandem-repeat scan of break_blocks (src/breaks.cpp:224-272) ----------------------
+    def repeat_scan(self, seqs, min_copy=1000, max_copy=20000, stride=50, want_match=False, check=True):
+        """sxg_poa_repeat_scan_batch (decree R).  seqs: byte strings or uint8 arrays, the letters as they are.  Returns (n_lags,
+        best, dev, v, status) -- int32, int32, float64, float64, int32, one entry per sequence -- and with want_match a sixth
+        entry, the list of every sequence's int32 match counts (lag min_copy + k at index k).  A repeat of length min_copy +
+        best is reported iff sqrt(v) != 0 and dev / sqrt(v) >= min_z (the host's part of the decree)."""
+        ns = len(seqs)
+        bases, seq_off = self._flat([np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x for x in seqs])
+        ri = RepeatIn(ns, _p(seq_off, C.c_int64), _p(bases, C.c_uint8), int(min_copy), int(max_copy), int(stride))
+        lags, best, st = (np.zeros(max(ns, 1), np.int32) for _ in range(3))
+        dev, v = (np.zeros(max(ns, 1), np.float64) for _ in range(2))
+        match = None
+        if want_match:   # the layout of sxg_repeat_match_offsets (poa_repeat.h): a declined sequence has no counts
+            n = np.diff(seq_off)
+            want = np.where((n >= 2 * int(min_copy)) & (n <= REPEAT_MAX_LEN) & (int(min_copy) > 0) & (int(max_copy) >= int(min_copy)),
+                            np.minimum(int(max_copy), n - int(min_copy)) - int(min_copy) + 1, 0)
+            off = np.concatenate([[0], np.cumsum(want)]).astype(np.int64)
+            match = np.zeros(max(int(off[-1]), 1), np.int32)
+        rc = self.lib.sxg_poa_repeat_scan_batch(self.h, C.byref(ri), _p(lags, C.c_int32), _p(best, C.c_int32), _p(dev, C.c_double), _p(v, C.c_double),
+                                                _p(st, C.c_int32), _p(match, C.c_int32) if want_match else None)
+        if rc and (check or rc != -4):
+            raise self._err("sxg_poa_repeat_scan_batch")
+        res = (lags[:ns], best[:ns], dev[:ns], v[:ns], st[:ns])
+        return res + ([match[off[s]:off[s + 1]] for s in range(ns)],) if want_match else res
 
     # -- the node order of prep (src/prep.cpp:11-163) ----------------------------------------
     def path_sgd_order(self, node_len, path_off, step_node, step_pos, eta, cooling_start, terms_per_iter, seed, mode=0, want_x=True):

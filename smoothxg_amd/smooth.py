@@ -18,6 +18,8 @@ SPLIT_FREE_FN = C.CFUNCTYPE(None, C.POINTER(_poa.SplitOut))
 SPLIT_MASH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SplitIn), C.POINTER(_poa.SplitMash), C.POINTER(_poa.SplitOut), C.POINTER(C.c_int64))
 IDENT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.IdentityIn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                        C.POINTER(C.c_int32))
+REPEAT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.RepeatIn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                        C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 SGD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SgdIn), C.POINTER(C.c_int32), C.POINTER(C.c_int64))
 
 
@@ -35,7 +37,7 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_blockset_free", "sxg_blockset_size", "sxg_block_collect_text", "sxg_block_graph_gfa",
            "sxg_smooth_gfa", "sxg_adaptive_poa_scores", "sxg_block_identity_threshold",
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
-           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa",
+           "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_break_scan", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa",
            "sxg_prep_default_params", "sxg_graph_prep", "sxg_blockset_identity_thresholds", "sxg_smooth_gfa_adaptive",
            "sxg_smooth_maf_gfa_adaptive", "sxg_smooth_maf_gfa_device_rows"]
 
@@ -83,6 +85,8 @@ def load_library():
     L.sxg_blockset_smoothable.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp)]
     L.sxg_blockset_break.argtypes = [vp, vp, C.c_uint64, C.c_int, C.POINTER(vp)]
     L.sxg_blockset_break_ex.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, C.c_double, C.c_uint64, C.c_int, C.POINTER(vp)]
+    L.sxg_blockset_break_scan.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, C.c_uint64, C.c_int, vp, vp, C.POINTER(vp),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.sxg_blockset_split.argtypes = [vp, vp, C.c_double, C.c_double, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.sxg_blockset_split_mash.argtypes = [vp, vp, C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, C.c_int32, vp, vp, vp,
                                           C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -201,6 +205,39 @@ def python_identifier(fn):
     return C.cast(cb, C.c_void_p), None, cb
 
 
+def gpu_repeat_scanner(engine):
+    """(scan, ctx) backed by the GPU engine: sxg_poa_repeat_scan_batch of libsxgpoa.so and the engine handle -- the scan provider
+    of the `scanner` key of Smoother's discover dict: the tandem-repeat scan of every range of every block that is cut then runs
+    on the device, in one call (decree R).  For a device group pass one of its members: gpu_repeat_scanner(group.member(i))."""
+    return C.cast(engine.lib.sxg_poa_repeat_scan_batch, C.c_void_p), engine.h
+
+
+def python_repeat_scanner(fn):
+    """(scan, ctx) around a Python function fn(seq_off, bases, min_copy, max_copy, stride) -> (n_lags, best, dev, v, status) or
+    (n_lags, best, dev, v, status, return code), one entry per sequence, the arrays being numpy copies of the batch the library
+    collected: for tests and experiments, the production provider is gpu_repeat_scanner.  The tuple keeps the callback alive."""
+    import numpy as np
+
+    def view(ptr, n, dtype):
+        return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True) if n else np.zeros(0, dtype)
+
+    def call(ctx, inp, n_lags, best, dev, v, status, match):
+        try:
+            a = inp.contents
+            seq_off = view(a.seq_off, a.n_seqs + 1, np.int64) if a.n_seqs else np.zeros(1, np.int64)
+            res = fn(seq_off, view(a.bases, int(seq_off[-1]), np.uint8), a.min_copy, a.max_copy, a.stride)
+            for dst, src, conv in zip((n_lags, best, dev, v, status), res[:5], (int, int, float, float, int)):
+                if len(src) != a.n_seqs:
+                    return -1
+                for k in range(a.n_seqs):
+                    dst[k] = conv(src[k])
+            return int(res[5]) if len(res) > 5 else 0
+        except Exception:   # (an exception must not cross the C frames)
+            return -1
+    cb = REPEAT_FN(call)
+    return C.cast(cb, C.c_void_p), None, cb
+
+
 def python_sorter(fn):
     """(sort, ctx) around a Python function fn(node_len, path_off, step_node, step_pos, eta, cooling_start, terms_per_iter,
     seed) -> order (or (order, x)), the arrays being numpy copies of what the library flattened: for tests and experiments,
@@ -261,8 +298,10 @@ class Smoother:
 
     def __init__(self, gfa_text, target_bp=None, blocks=None, discover=None):
         """discover: block discovery as smoothxg does it -- a dict with target_poa_length and n_haps (and optionally
-        max_path_jump, max_edge_jump, max_poa_length, repeats): smoothable_blocks then the cutting half of break_blocks
-        (repeat-aware cut lengths with the reference's defaults unless repeats=None).
+        max_path_jump, max_edge_jump, max_poa_length, repeats, scanner): smoothable_blocks then the cutting half of break_blocks
+        (repeat-aware cut lengths with the reference's defaults unless repeats=None).  scanner: a scan provider
+        (gpu_repeat_scanner(engine): the tandem-repeat scan of all cut blocks in ONE call on the device, sxg_blockset_break_scan;
+        the counts it reports are kept in self.break_counts); without the key the host scans, as it always did.
         blocks: the caller's own blockset -- a list of blocks, each a list of (path, step_begin, step_end)
         or (path, step_begin, step_end, length) in alignment order (sxg_blockset_from_ranges); otherwise the
         demo partition into path windows of target_bp."""
@@ -283,6 +322,12 @@ class Smoother:
                 rep = discover.get("repeats", (1000, 20000, 5, 50))   # (min_copy_length, max_copy_length, min_autocorr_z, autocorr_stride) or None
                 if rep is None:
                     rc = self.L.sxg_blockset_break_ex(g, raw, int(discover.get("max_poa_length", 2 * tl)), 0, 1000, 20000, 5.0, 50, 1, C.byref(b))
+                elif "scanner" in discover:
+                    scan = discover["scanner"]
+                    counts = [C.c_int64(), C.c_int64(), C.c_int64()]
+                    rc = self.L.sxg_blockset_break_scan(g, raw, int(discover.get("max_poa_length", 2 * tl)), int(rep[0]), int(rep[1]), float(rep[2]),
+                                                        int(rep[3]), 1, scan[0], scan[1], C.byref(b), *(C.byref(c) for c in counts))
+                    self.break_counts = tuple(c.value for c in counts)   # (blocks cut, of which at a repeat, sequences the scanner declined)
                 else:
                     rc = self.L.sxg_blockset_break_ex(g, raw, int(discover.get("max_poa_length", 2 * tl)), 1, int(rep[0]), int(rep[1]),
                                                       float(rep[2]), int(rep[3]), 1, C.byref(b))
