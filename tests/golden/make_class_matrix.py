@@ -1,4 +1,4 @@
-"""Generates tests/golden/class_matrix.json: oracle results for one block (or one align-only problem) per built kernel class,
+"""Generates tests/golden/class_matrix.json and class_matrix_wide.json (family wide_match): oracle results for one block (or one align-only problem) per built kernel class,
 each with sequences that FILL the class's geometry.
 
 SELF-ORACLE fixtures (oracle/poa_oracle.c and its AVX2 twin, which tests/test_oracle.py holds equal to it; NOT reference-derived --
@@ -24,6 +24,8 @@ Families (scores in spoa's sign convention):
   cb4_affine   gen2_affine's cases run with SXG_POA_CELL_BYTES=4: with |g| <= 120 no affine set needs more than 15 code bits
                (H 8 + F 7), so the 4-byte affine classes are reachable through the knob only.  Results do not depend on the cell
                format: the cases share gen2_affine's expectations and have no entries of their own.
+  wide_match   64,127,96,32,127,16        int32 row words by the scores alone (64 L >= 30 000 from 469 letters on, no knob): every
+               geometry of the 32-bit sweep as a block and as an align-only problem, local and global
 Expectations are in spoa's node order (mode | 0x10, the product default: the re-sort is a graph phase whose batch size differs
 by class): scores, summed cells, node and edge counts, digests of nodes / edges / paths (make_fullshape.digest_block's arrays,
 folded into three to keep the file small), no consensus.
@@ -44,6 +46,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 FIXTURE = os.path.join(HERE, "class_matrix.json")
+FIXTURE_WIDE = os.path.join(HERE, "class_matrix_wide.json")   # the families added later (WIDE_FAMILIES): the first file keeps its bytes
+WIDE_FAMILIES = ("wide_match",)
 
 SCORES = {
     "ds": (1, -4, -6, -2, -26, -1),
@@ -51,6 +55,7 @@ SCORES = {
     "gen2_affine": (1, -4, -6, -2, -6, -2),
     "cb4_convex": (1, -19, -39, -3, -81, -1),
     "convex_heavy": (3, -5, -9, -3, -30, -1),
+    "wide_match": (64, -127, -96, -32, -127, -16),
 }
 BLOCK_FAMILIES = ("ds", "gen2_convex", "gen2_affine", "cb4_convex")
 ALIGN_FAMILIES = ("cb4_convex", "gen2_affine")
@@ -313,6 +318,17 @@ def list_cases():
         assert cell_bytes(prm) == TIER_CELL_BYTES[ti], (prm, code_bits(prm))
         for W, length in ((10, 5000), (11, 5200)):
             add("tier", "tier%d" % ti, prm, 0, 2, W, 4, 4000000 + 1000 * W + ti, length=length)
+    # int32 row words WITHOUT a knob: m = 64 leaves the packed sweep and int16 row words at 469 letters, before the smallest
+    # geometry's target range begins (512 - 42), so every geometry of the 32-bit sweep is the host's own choice.  (Listed last,
+    # and kept in class_matrix_wide.json: class_matrix.json is one line and keeps its bytes.)
+    for kind in ("block", "align"):
+        for mode in (0, 1):
+            for W, NW in natural_geometries(1, mode == 0, 12287):
+                top = capacity(W, NW, 1) - 1
+                for L in (top - 42, top):
+                    assert row_mode(SCORES["wide_match"], mode == 0, L, L, clamp_ok=kind == "block") == 1
+                    assert row_mode(SCORES["wide_match"], mode == 0, L, int(L * 1.03)) == 1
+                add(kind, "wide_match", SCORES["wide_match"], mode, 1, W, NW, 5000000 + 100000 * (kind == "align") + 1000 * W + 10 * NW, no_packed=False)
     assert len({case_id(c) for c in cases}) == len(cases)
     return cases
 
@@ -383,23 +399,39 @@ def run_case(case):
     return case
 
 
+PROVENANCE = ("self-oracle (oracle/poa_oracle.c; AVX2 twin beyond 2 100 letters), generated by tests/golden/make_class_matrix.py; "
+              "NOT reference-derived")
+
+
+def load_cases():
+    """every case of the two fixture files, in list_cases' order: class_matrix.json, then class_matrix_wide.json"""
+    cases = []
+    for path in (FIXTURE, FIXTURE_WIDE):
+        with open(path) as f:
+            cases += json.load(f)["cases"]
+    return cases
+
+
 def main():
+    """Cases the fixtures already hold are kept as they stand (the files are re-written from their parsed values, which
+    round-trip byte for byte); only cases they lack are computed.  Delete a fixture to regenerate its cases."""
     from oracle import oracle_py as O
     O.build()
-    cases = list_cases()
+    have = {case_id(c): c for c in load_cases()} if os.path.exists(FIXTURE) and os.path.exists(FIXTURE_WIDE) else {}
+    listed = list_cases()
+    cases = [c for c in listed if case_id(c) not in have]
     # the long ones first, so that the pool does not end on one of them
     order = sorted(range(len(cases)), key=lambda i: -capacity(cases[i]["W"], cases[i]["NW"], cases[i]["rm"]))
     with mp.Pool(min(16, max(1, os.cpu_count() or 1))) as pool:
         done = pool.map(run_case, [cases[i] for i in order], chunksize=1)
-    res = [None] * len(cases)
-    for i, c in zip(order, done):
-        res[i] = c
-    out = {"provenance": "self-oracle (oracle/poa_oracle.c; AVX2 twin beyond 2 100 letters), generated by tests/golden/make_class_matrix.py; "
-                         "NOT reference-derived", "cases": res}
-    with open(FIXTURE, "w") as f:
-        json.dump(out, f, indent=None, separators=(",", ":"))
-        f.write("\n")
-    print("wrote", len(res), "cases,", os.path.getsize(FIXTURE), "bytes")
+    have.update({case_id(c): c for c in done})
+    res = [have[case_id(c)] for c in listed]
+    dump = lambda c: json.dumps(c, indent=None, separators=(",", ":"))
+    with open(FIXTURE, "w") as f:       # (one line, as it was first written)
+        f.write(dump({"provenance": PROVENANCE, "cases": [c for c in res if c["family"] not in WIDE_FAMILIES]}) + "\n")
+    with open(FIXTURE_WIDE, "w") as f:  # (one case per line: a later family shows in a diff as the lines it adds)
+        f.write('{"provenance":%s,"cases":[\n%s\n]}\n' % (json.dumps(PROVENANCE), ",\n".join(dump(c) for c in res if c["family"] in WIDE_FAMILIES)))
+    print("wrote", len(res), "cases,", os.path.getsize(FIXTURE), "+", os.path.getsize(FIXTURE_WIDE), "bytes")
 
 
 if __name__ == "__main__":

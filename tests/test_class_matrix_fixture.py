@@ -15,32 +15,21 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_class_matrix as M  # noqa: E402
 
-# Built classes no case runs: (kind, rm, cb, tmax, W, sw, ds) -> reason.  Only two kinds of entries are allowed here: banded
-# classes, and int32-row-word classes at geometries no score set of the matrix reaches without the widening ladder.  (The 16-wave
-# global classes beyond the packed score range need no entry: the block classes run as the 768-thread launch of the (12,8)
-# blocks, the align-only class on the longest global query the strict rule admits.)
+# Built classes no case runs: (kind, rm, cb, tmax, W, sw, ds) -> reason.  Banded classes only: every class of the full-matrix
+# sweeps has a case.  (The int32-row-word classes run for the wide_match family, whose m = 64 reaches them from 469 letters on
+# without a knob.  The 16-wave global classes beyond the packed score range need no entry: the block classes run as the
+# 768-thread launch of the (12,8) blocks, the align-only class on the longest global query the strict rule admits.)
 BANDED = "banded sweep: the subject of test_gpu_banded.py / test_gpu_adaptive_band.py"
-RM1 = "int32 row words: reached from the matrix's scores only by the widening ladder (3 L >= 30 000 needs L > 10 000: 16 waves x 12; " \
-      "a global affine align query leaves int16 row words from 7 498 letters: 8 waves x 16, 12 and 16 waves x 12)"
 EXCLUDED = {}
 for w in (6, 8, 11):
     EXCLUDED[(0, 3, 2, 64, w, 1, 0)] = BANDED
     for sw in (0, 1):
         EXCLUDED[(0, 3, 4, 64, w, sw, 0)] = BANDED
-for kind in (0, 1):
-    for tmax, widths in ((256, (8, 12, 16)), (512, (12, 16)), (1024, (12,))):
-        for w in widths:
-            for sw in (0, 1):
-                EXCLUDED[(kind, 1, 4, tmax, w, sw, 0)] = RM1
-del EXCLUDED[(0, 1, 4, 1024, 12, 1, 0)]      # convex_heavy, local, 12 285 letters
-del EXCLUDED[(1, 1, 4, 512, 16, 0, 0)]       # global affine align queries beyond 7 498 letters
-del EXCLUDED[(1, 1, 4, 1024, 12, 0, 0)]
 
 
 @pytest.fixture(scope="module")
 def fixture_cases():
-    with open(M.FIXTURE) as f:
-        return json.load(f)["cases"]
+    return M.load_cases()
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +46,8 @@ def built(tmp_path_factory):
 
 
 def covered_classes(cases):
-    """The classes the GPU test's runs select: every case's own, the 4-byte affine classes of gen2_affine's packed block cases
+    """The classes the GPU test's runs select: every case's own (the wide_match family's among them: the int32-row-word classes,
+    block and align-only), the 4-byte affine classes of gen2_affine's packed block cases
     under SXG_POA_CELL_BYTES=4, the 768-thread launch (SXG_POA_FORCE_P16=8,12) of the (12,8) blocks, and the forced re-runs of
     the longest packed global align query (M.ALIGN_GLOBAL_FORCED)."""
     got = {}
@@ -84,11 +74,13 @@ def test_cases_cover_every_built_class(built, fixture_cases):
     assert not unknown, "exclusions that name no built class: %s" % unknown
     assert not stale, "excluded classes that a case does run: %s" % stale
     assert not missing, "built classes (kind rm cb tmax W sw ds) without a case and without a reason: %s" % missing
+    assert all(k[1] == 3 for k in EXCLUDED), "only banded classes may go without a case"
     assert len(built) >= 250 and len(EXCLUDED) < len(built) // 5   # (each line stands for two kernels: convex and affine)
     # the check bites: without a family's cases its classes are reported (the 4-byte classes run for cb4_convex and, under the
     # knob, for gen2_affine; the align-only classes for both align families)
     for kind, fams, expect in (("block", ("ds",), (0, 2, 2, 256, 10, 0, 1)), ("block", ("cb4_convex", "gen2_affine"), (0, 2, 4, 512, 11, 1, 0)),
-                               ("block", ("cb4_convex",), (0, 2, 4, 1024, 8, 0, 0)), ("align", M.ALIGN_FAMILIES, (1, 0, 4, 256, 16, 1, 0))):
+                               ("block", ("cb4_convex",), (0, 2, 4, 1024, 8, 0, 0)), ("align", M.ALIGN_FAMILIES, (1, 0, 4, 256, 16, 1, 0)),
+                               ("block", ("wide_match",), (0, 1, 4, 256, 8, 0, 0)), ("align", ("wide_match",), (1, 1, 4, 512, 12, 1, 0))):
         some = [c for c in fixture_cases if not (c["family"] in fams and c["kind"] == kind)]
         assert expect in missing_and_stale(built, some)[0], (kind, fams)
 
@@ -125,7 +117,7 @@ def test_every_case_regenerates_and_selects_its_geometry(fixture_cases):
         cap = M.capacity(W, NW, rm)
         if c["kind"] == "block":
             assert cap - 3 <= top <= cap - 1, M.case_id(c)
-            assert M.row_mode(tuple(c["params"]), sw, top, top, no_packed=rm != 2, clamp_ok=True) == rm, M.case_id(c)
+            assert M.row_mode(tuple(c["params"]), sw, top, top, no_packed=c.get("no_packed", rm != 2), clamp_ok=True) == rm, M.case_id(c)
         elif c["kind"] == "align":
             assert top > cap * (NW - 1) // NW + 64 and top <= c.get("top", cap - 1), M.case_id(c)
             assert M.row_mode(tuple(c["params"]), sw, top, c["rows"], no_packed=c["no_packed"]) == rm, M.case_id(c)

@@ -1,4 +1,4 @@
-"""Every built kernel class against committed oracle output (tests/golden/class_matrix.json, made by
+"""Every built kernel class against committed oracle output (tests/golden/class_matrix.json and class_matrix_wide.json, made by
 tests/golden/make_class_matrix.py -- see its docstring for the inputs and the families): one block, or one align-only problem,
 per class, with sequences that fill the class's geometry to within three letters, so that the carry scans across strips, the
 wave-to-wave hand-over, the stored-row read-back, the compiled-in thread count, the T < TMAX launch of the 4-byte classes and
@@ -14,7 +14,6 @@ Re-runs at no fixture cost (results do not depend on the geometry):
   * the (12,8) blocks under SXG_POA_FORCE_P16=8,12: the 768-thread launch of the 1 024-thread class, which the chooser never picks;
   * gen2_affine's blocks under SXG_POA_CELL_BYTES=4 (family cb4_affine): the affine 4-byte classes;
   * the longest packed global align-only query under the wider forced geometries (make_class_matrix.ALIGN_GLOBAL_FORCED)."""
-import json
 import os
 import re
 import sys
@@ -29,8 +28,7 @@ import make_class_matrix as M  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-with open(M.FIXTURE) as _f:
-    CASES = json.load(_f)["cases"]
+CASES = M.load_cases()
 VARIANT_LINE = re.compile(r"^\[sxg\] variant T=(\d+) W=(\d+) cvx=(\d+) rowmode=(\d+) attempt=(\d+) .* tmax=(\d+) cb=(\d+) ds=(\d+) w2=(\d+)$", re.M)
 PACKED_FAMILIES = M.BLOCK_FAMILIES + ("cb4_affine",)
 
@@ -43,7 +41,8 @@ def cases_of(kind, family, mode, **where):
 def set_env(monkeypatch, case, knob4=False, force=None):
     monkeypatch.setenv("SXG_POA_NO_SPREAD", "1")
     monkeypatch.setenv("SXG_POA_DEBUG", "1")
-    for name, on, value in (("SXG_POA_NO_PACKED", case["rm"] != 2 or case.get("no_packed", False), "1"), ("SXG_POA_CELL_BYTES", knob4, "4"),
+    # (a 32-bit case takes the knob unless it says that its scores reach the sweep by themselves: no_packed = False)
+    for name, on, value in (("SXG_POA_NO_PACKED", case.get("no_packed", case["rm"] != 2), "1"), ("SXG_POA_CELL_BYTES", knob4, "4"),
                             ("SXG_POA_FORCE_P16", force or case["force"], "%d,%d" % (force or (case["W"], case["NW"])))):
         if on:
             monkeypatch.setenv(name, value)
@@ -120,10 +119,19 @@ def test_packed_block_classes(engine, monkeypatch, capfd, family, mode, waves):
         assert st["dom_threads"] == 768
 
 
-@pytest.mark.parametrize("family,mode", [("ds", 0), ("ds", 1), ("convex_heavy", 0)], ids=["int16-local", "int16-global", "int32-local"])
-def test_32_bit_block_classes(engine, monkeypatch, capfd, family, mode):
-    cases = [c for c in cases_of("block", family, mode) if c["rm"] != 2]
-    assert len(cases) == (12 if family == "ds" else 1) and {c["rm"] for c in cases} == {0 if family == "ds" else 1}
+# (wide_match: int32 row words with no knob set, every geometry; split by wave count to keep each function short)
+WIDE_WAVES = {"few": (1, 2, 3, 4), "many": (8, 12, 16)}
+BLOCK32 = [("ds", 0, None), ("ds", 1, None), ("convex_heavy", 0, None)] + [("wide_match", m, w) for m in (0, 1) for w in WIDE_WAVES]
+BLOCK32_IDS = ["int16-local", "int16-global", "int32-local"] + ["int32-wide-%s-%s-waves" % (("local", "global")[m], w) for m in (0, 1) for w in WIDE_WAVES]
+
+
+@pytest.mark.parametrize("family,mode,waves", BLOCK32, ids=BLOCK32_IDS)
+def test_32_bit_block_classes(engine, monkeypatch, capfd, family, mode, waves):
+    cases = [c for c in cases_of("block", family, mode) if c["rm"] != 2 and (waves is None or c["NW"] in WIDE_WAVES[waves])]
+    if family == "wide_match":
+        assert sorted((c["W"], c["NW"]) for c in cases) == sorted(g for g in M.natural_geometries(1, mode == 0, 12287) if g[1] in WIDE_WAVES[waves])
+        assert len(cases) == (8 if waves == "few" else 4) and all(c["no_packed"] is False for c in cases)
+    assert len(cases) == ({"ds": 12, "convex_heavy": 1}.get(family, len(cases))) and {c["rm"] for c in cases} == {0 if family == "ds" else 1}
     for c in cases:
         run_block(engine, monkeypatch, capfd, c)
 
@@ -152,12 +160,15 @@ def run_align(engine, monkeypatch, capfd, case, force=None):
     check_launch(st, err, case, M.case_class(case, force=force), force or (case["W"], case["NW"]), 0, label)
 
 
-@pytest.mark.parametrize("sweep", ["packed", "32-bit"])
-@pytest.mark.parametrize("mode", [0, 1], ids=["local", "global"])
-@pytest.mark.parametrize("family", M.ALIGN_FAMILIES)
+ALIGN_CASES = [(f, m, s) for s in ("packed", "32-bit") for m in (0, 1) for f in M.ALIGN_FAMILIES] + [("wide_match", m, "int32-wide") for m in (0, 1)]
+
+
+@pytest.mark.parametrize("family,mode,sweep", ALIGN_CASES, ids=["%s-%s-%s" % (f, ("local", "global")[m], s) for f, m, s in ALIGN_CASES])
 def test_align_only_classes(engine, monkeypatch, capfd, family, mode, sweep):
     cases = cases_of("align", family, mode, no_packed=sweep == "32-bit")
-    assert len(cases) >= (12 if sweep == "32-bit" else 21) and all((c["rm"] == 2) == (sweep == "packed") for c in cases)
+    if sweep == "int32-wide":      # int32 row words by the scores alone: no knob, every geometry of the 32-bit sweep
+        assert [(c["W"], c["NW"]) for c in cases] == M.natural_geometries(1, mode == 0, 12287) and {c["rm"] for c in cases} == {1}
+    assert len(cases) >= (12 if sweep != "packed" else 21) and all((c["rm"] == 2) == (sweep == "packed") for c in cases)
     for c in cases:
         run_align(engine, monkeypatch, capfd, c)
         if "top" in c and (c["W"], c["NW"]) == (8, 8):
