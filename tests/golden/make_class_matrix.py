@@ -1,5 +1,5 @@
-"""Generates tests/golden/class_matrix.json and class_matrix_wide.json (family wide_match): oracle results for one block (or one align-only problem) per built kernel class,
-each with sequences that FILL the class's geometry.
+"""Generates tests/golden/class_matrix.json, class_matrix_wide.json (family wide_match) and class_matrix_banded.json (kind "band"):
+oracle results for one block (or one align-only problem) per built kernel class, each with sequences that FILL the class's geometry.
 
 SELF-ORACLE fixtures (oracle/poa_oracle.c and its AVX2 twin, which tests/test_oracle.py holds equal to it; NOT reference-derived --
 see the header of tests/golden/make_golden.py).  tests/test_gpu_class_matrix.py runs every case on the GPU and compares with the
@@ -26,11 +26,25 @@ Families (scores in spoa's sign convention):
                format: the cases share gen2_affine's expectations and have no entries of their own.
   wide_match   64,127,96,32,127,16        int32 row words by the scores alone (64 L >= 30 000 from 469 letters on, no knob): every
                geometry of the 32-bit sweep as a block and as an align-only problem, local and global
+  banded       kind "band": the one-wave banded sweep (row mode 3), one block per strip width W = 6, 8, 11 (decree B2 of
+               oracle/poa_oracle.c), its longest sequence within three letters of the LAST length on W = 6 (2 266) and on W = 8
+               (6 466) and at the FIRST lengths with the capped half-width 693 (12 734 .. 12 740): there the band of a row spans
+               127 - 128 of the window's 128 strips, so the window has no slack and re-centres at every second band move at the
+               latest.  Local mode with the static (banded = 1) and the adaptive band (banded = 2) for gen2_convex, gen2_affine
+               (2-byte band cells) and cb4_convex (4-byte); global mode, adaptive band (4-byte cells by rule), for ds (convex),
+               gen2_affine and affine_e1 1,4,6,1,6,1 (affine).  The strict range rule bounds a global block (m L < 15 800 and
+               the all-gap floor < 15 800 on the true row count): ds fills W = 6 and W = 8 and reaches W = 11 up to ~7 600
+               letters, gen2_affine (e = -2) fills W = 6 and reaches W = 8 up to ~3 800, affine_e1 reaches W = 11 -- partial
+               fills, the most a global block of these scores can do; such a case takes the longest length the model admits
+               with 4 % more rows than letters, and records the oracle's row counts in front of every sequence ("rows_before"),
+               on which the model says that no sweep is refused and re-run.  Expectations come from the scalar oracle (the AVX2
+               twin is not held equal to it in banded mode); cells = band cells.
 Expectations are in spoa's node order (mode | 0x10, the product default: the re-sort is a graph phase whose batch size differs
 by class): scores, summed cells, node and edge counts, digests of nodes / edges / paths (make_fullshape.digest_block's arrays,
 folded into three to keep the file small), no consensus.
 
-    python tests/golden/make_class_matrix.py      (from the repository root; ~10 min of CPU over up to 16 processes)
+    python tests/golden/make_class_matrix.py      (from the repository root; ~10 min of CPU over up to 16 processes; cases the
+                                                   fixtures hold already are kept, the banded file alone takes ~10 s)
 """
 import hashlib
 import json
@@ -48,6 +62,7 @@ if ROOT not in sys.path:
 FIXTURE = os.path.join(HERE, "class_matrix.json")
 FIXTURE_WIDE = os.path.join(HERE, "class_matrix_wide.json")   # the families added later (WIDE_FAMILIES): the first file keeps its bytes
 WIDE_FAMILIES = ("wide_match",)
+FIXTURE_BANDED = os.path.join(HERE, "class_matrix_banded.json")   # kind "band": the banded sweep's cases, one per line
 
 SCORES = {
     "ds": (1, -4, -6, -2, -26, -1),
@@ -56,6 +71,7 @@ SCORES = {
     "cb4_convex": (1, -19, -39, -3, -81, -1),
     "convex_heavy": (3, -5, -9, -3, -30, -1),
     "wide_match": (64, -127, -96, -32, -127, -16),
+    "affine_e1": (1, -4, -6, -1, -6, -1),
 }
 BLOCK_FAMILIES = ("ds", "gen2_convex", "gen2_affine", "cb4_convex")
 ALIGN_FAMILIES = ("cb4_convex", "gen2_affine")
@@ -68,6 +84,13 @@ FORCED_768_FAMILIES = ("ds", "gen2_convex", "cb4_convex")   # their (12,8) block
 TIERS = ((1, -19, -39, -3, -81, -1), (1, -13, -31, -3, -51, -1), (1, -9, -16, -2, -41, -1), (1, -7, -11, -2, -33, -1), (1, -4, -6, -2, -26, -1))
 TIER_CELL_BYTES = (4, 4, 2, 2, 2)
 SPLICE = 40
+# the banded sweep (kind "band"): (longest sequence from, to) per strip width -- to = the last length on W = 6 and on W = 8, from
+# = the first length with the capped half-width at W = 11; and the score families of each (mode, gap model)
+BAND_LENGTHS = {6: (2264, 2266), 8: (6464, 6466), 11: (12734, 12740)}
+BAND_LOCAL_FAMILIES = ("gen2_convex", "gen2_affine", "cb4_convex")
+BAND_GLOBAL_FAMILIES = {6: ("ds", "gen2_affine"), 8: ("ds", "gen2_affine"), 11: ("ds", "affine_e1")}
+BAND_ROWS_MARGIN = 1.04   # rows per letter a partial global case is sized for (the oracle's count is recorded and asserted on)
+MAX_SEQ_LEN = 26623       # SXG_POA_MAX_SEQ_LEN (include/sxg_poa.h)
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # The host's choice of a class, written down a second time (sxg_poa.hip: p16_safe / h16_safe / row_mode / plane_cell_bytes,
@@ -150,11 +173,71 @@ def second_width(W, NW, cb):
     return W - 1 if cb == 2 and NW in (4, 8) and 9 <= W <= 12 else 0
 
 
+# Row mode 3, the banded sweep (sxg_poa.hip, upload: the `bnd && (sw || bnd == 2) && rm == 2` branch; decrees B1, B2 of
+# oracle/poa_oracle.c).  tests/test_class_matrix_fixture.py holds band_strip_width() equal to the oracle's
+# poa_band_strip_width for every length; the product's own copy lives in a HIP header, and the GPU test holds it through the
+# variant line of every banded case.
+
+def band_half_width(L):
+    return min(311 + int(0.03 * L), 693)
+
+
+def band_strip_width(maxlen):
+    w = band_half_width(maxlen)
+    return 6 if 2 * w <= 756 else (8 if 2 * w <= 1008 else 11)
+
+
+def band_cell_bytes(scores, sw, knob4=False):
+    """2 only for local alignments whose delta code fits; knob4: SXG_POA_BAND_CELL_BYTES=4"""
+    return 4 if knob4 or not sw else cell_bytes(scores)
+
+
+def block_sweep(scores, mode, maxlen, banded, knob4=False):
+    """(rm, W, NW, cb, tmax, ds) of a block's first launch; a banded block runs row mode 3 when its alignments are local or its
+    band adaptive, and the STRICT range rule keeps it packed (a banded block has no clamp and no re-run of its own)"""
+    sw = mode == 0
+    rm = row_mode(scores, sw, maxlen, maxlen, clamp_ok=banded == 0)
+    if banded and (sw or banded == 2) and rm == 2 and maxlen <= MAX_SEQ_LEN:
+        return 3, band_strip_width(maxlen), 1, band_cell_bytes(scores, sw, knob4), 64, 0
+    cb = cell_bytes(scores) if rm == 2 else 4
+    W, NW = variant_for_len(maxlen, rm, sw)
+    return rm, W, NW, cb, class_tmax(NW, rm, cb), int(rm == 2 and cb == 2 and tuple(scores) == SCORES["ds"])
+
+
+def band_no_rerun(scores, mode, seq_lens, rows_before):
+    """The banded kernel re-checks a global alignment's all-gap floor with the true row count in front of every sequence
+    (poa_kernels.hip.h: ST_RANGE_OVERFLOW at 15 800); True when no sequence is refused"""
+    if mode == 0:
+        return True
+    return all(-(gap_cost(scores, n) + gap_cost(scores, L)) < 15800 for L, n in zip(seq_lens, rows_before))
+
+
+def band_global_top(scores, W):
+    """the longest sequence of a global banded case at strip width W: the last length on W if the strict rule admits it with
+    BAND_ROWS_MARGIN rows per letter, else the longest length it admits -- None if that is not on W"""
+    ok = lambda L: abs(scores[0]) * L < 15800 and band_no_rerun(scores, 1, [L, L], [L, int(L * BAND_ROWS_MARGIN) + 1])
+    full = BAND_LENGTHS[W][1]
+    if ok(full) and W != 11:
+        return full
+    top = max(L for L in range(1, BAND_LENGTHS[11][1] + 1) if ok(L))
+    return top if band_strip_width(top) == W and band_strip_width(top - 2) == W else None
+
+
+def band_splices(W, top):
+    """(column of the deletion, of the insertion): two strip boundaries a third and two thirds along the sequence"""
+    strips = (top + 1) // W
+    return W * (strips // 3), W * (2 * strips // 3)
+
+
 def case_class(case, knob4=False, force=None):
     """(kind, rm, cb, tmax, W, sw, ds) of the class a case runs on -- the line tests/csrc/class_list.cpp prints for it"""
     W, NW = force or (case["W"], case["NW"])
     sw = 1 - case["mode"]
     scores = tuple(case["params"])
+    if case["kind"] == "band":
+        rm, bw, _, cb, tmax, ds = block_sweep(scores, case["mode"], max(case["seq_lens"]) if "seq_lens" in case else case["top"], case["banded"], knob4)
+        assert (rm, bw) == (3, W), case
+        return (0, 3, cb, tmax, W, sw, ds)
     if case["kind"] == "align":
         return (1, case["rm"], 4, class_tmax(NW, case["rm"], 4), W, sw, 0)
     cb = cell_bytes(scores, knob4) if case["rm"] == 2 else 4
@@ -183,11 +266,11 @@ def make_inputs(block_id, length, del_at, ins_at):
     return [a, b, c]
 
 
-def search_inputs(seed, W, NW, rm, lo=3, hi=1, top=None):
+def search_inputs(seed, W, NW, rm, lo=3, hi=1, top=None, splices=None):
     """(block_id, length, del_at, ins_at, seqs) whose longest sequence has capacity - lo .. capacity - hi letters (top: that many
-    letters at most in place of capacity - 1)"""
+    letters at most in place of capacity - 1; splices: their columns in place of splice_columns')"""
     cap = capacity(W, NW, rm) if top is None else top + 1
-    del_at, ins_at = splice_columns(W, NW, rm)
+    del_at, ins_at = splices or splice_columns(W, NW, rm)
     for k in range(400):
         block_id = seed + k
         length = cap - 2 - SPLICE
@@ -261,7 +344,7 @@ def natural_geometries(rm, sw, max_len):
 
 
 def case_id(c):
-    return "%s/%s/%s/rm%d/W%dx%d" % (c["kind"], c["family"], "global" if c["mode"] else "local", c["rm"], c["W"], c["NW"])
+    return "%s/%s/%s/rm%d/W%dx%d" % (c["kind"], c["family"], "global" if c["mode"] else "local", c["rm"], c["W"], c["NW"]) + ("/b%d" % c["banded"] if c["kind"] == "band" else "")
 
 
 def list_cases():
@@ -329,6 +412,20 @@ def list_cases():
                     assert row_mode(SCORES["wide_match"], mode == 0, L, L, clamp_ok=kind == "block") == 1
                     assert row_mode(SCORES["wide_match"], mode == 0, L, int(L * 1.03)) == 1
                 add(kind, "wide_match", SCORES["wide_match"], mode, 1, W, NW, 5000000 + 100000 * (kind == "align") + 1000 * W + 10 * NW, no_packed=False)
+    # the banded sweep (listed last, kept in class_matrix_banded.json): "top" = the longest sequence aimed at, "lo" = how far below
+    # it the search may end
+    for W in (6, 8, 11):
+        lo_len, hi_len = BAND_LENGTHS[W]
+        for fi, fam in enumerate(BAND_LOCAL_FAMILIES):
+            for banded in (1, 2):
+                for L in (lo_len, hi_len):
+                    assert block_sweep(SCORES[fam], 0, L, banded)[:3] == (3, W, 1)
+                add("band", fam, SCORES[fam], 0, 3, W, 1, 6000000 + 100000 * fi + 1000 * W + banded, banded=banded, top=hi_len, lo=hi_len - lo_len)
+        for fi, fam in enumerate(BAND_GLOBAL_FAMILIES[W]):
+            top = band_global_top(SCORES[fam], W)
+            assert top is not None and block_sweep(SCORES[fam], 1, top, 2)[:4] == (3, W, 1, 4), (fam, W, top)
+            assert block_sweep(SCORES[fam], 1, top, 1)[0] == 2       # (the static band is for local mode only)
+            add("band", fam, SCORES[fam], 1, 3, W, 1, 6500000 + 100000 * fi + 1000 * W, banded=2, top=top, lo=2)
     assert len({case_id(c) for c in cases}) == len(cases)
     return cases
 
@@ -359,18 +456,21 @@ def digest_pairs(rows, pos):
 def expectations(case, impl=None):
     """What the oracle computes for a case with inputs: the fixture's result fields."""
     from oracle import oracle_py as O
-    p = O.mkparams(*case["params"], mode=case["mode"] | (0 if case["kind"] == "align" else 0x10))
+    p = O.mkparams(*case["params"], mode=case["mode"] | (0 if case["kind"] == "align" else 0x10), banded=case.get("banded", 0))
     if case["kind"] == "align":
         codes, off, pred, sink, q = align_problem(case)
         an, ap, sc = O.align_csr(codes, off, pred, sink, q, p)
         return {"rows": int(len(codes)), "score": int(sc), "n_pairs": int(len(an)), "digest": digest_pairs(an, ap)}
     seqs = case_inputs(case)
-    if impl is None:
-        impl = O.IMPL_AVX2 if max(case["seq_lens"]) > 2100 else O.IMPL_SCALAR
+    if impl is None:   # (banded: the scalar oracle at every length -- the AVX2 twin is not held equal to it there)
+        impl = O.IMPL_AVX2 if max(case["seq_lens"]) > 2100 and case["kind"] != "band" else O.IMPL_SCALAR
     g, sc, cells = O.block_run(seqs, None, p, impl=impl)
     code, rank, grp = g.nodes()
     t, h, w = g.edges()
-    return {"scores": [int(x) for x in sc], "cells": int(cells.sum()), "n_nodes": int(g.n_nodes), "n_edges": int(g.n_edges),
+    extra = {}
+    if case["kind"] == "band":   # graph rows in front of every sequence: what the kernel's range re-check sees
+        extra["rows_before"] = [0] + [int(O.block_run(seqs[:k], None, p, impl=impl)[0].n_nodes) for k in range(1, len(seqs))]
+    return {**extra, "scores": [int(x) for x in sc], "cells": int(cells.sum()), "n_nodes": int(g.n_nodes), "n_edges": int(g.n_edges),
             "digests": digest_block(code, rank, grp, t, h, w, [g.seq_path(s) for s in range(g.n_seqs)])}
 
 
@@ -385,6 +485,9 @@ def run_case(case):
             if variant_for_len(max(len(s) for s in seqs), 2, True) == (W, NW):
                 break
         block_id, length = case["seed"] + k, case["length"]
+    elif case["kind"] == "band":
+        block_id, length, del_at, ins_at, seqs = search_inputs(case["seed"], case["W"], 1, 3, lo=case["lo"] + 1, top=case["top"],
+                                                               splices=band_splices(case["W"], case["top"]))
     else:
         lo = 42 if case["kind"] == "align" else 3            # (an align case's query is the third sequence, the longest or nearly)
         block_id, length, del_at, ins_at, seqs = search_inputs(case["seed"], case["W"], case["NW"], case["rm"], lo=lo, top=case.get("top"))
@@ -395,18 +498,22 @@ def run_case(case):
     case.update(expectations(case))
     if case["kind"] == "align":
         assert row_mode(tuple(case["params"]), case["mode"] == 0, len(seqs[2]), case["rows"], no_packed=case["no_packed"]) == case["rm"], case
+    if case["kind"] == "band":
+        assert band_no_rerun(tuple(case["params"]), case["mode"], case["seq_lens"], case["rows_before"]), case
     print("done %-44s %6.1f s" % (case_id(case), time.time() - t0), flush=True)
     return case
 
 
 PROVENANCE = ("self-oracle (oracle/poa_oracle.c; AVX2 twin beyond 2 100 letters), generated by tests/golden/make_class_matrix.py; "
               "NOT reference-derived")
+PROVENANCE_BANDED = ("self-oracle (oracle/poa_oracle.c, the scalar oracle's banded modes), generated by tests/golden/make_class_matrix.py; "
+                     "NOT reference-derived")
 
 
 def load_cases():
-    """every case of the two fixture files, in list_cases' order: class_matrix.json, then class_matrix_wide.json"""
+    """every case of the three fixture files, in list_cases' order: class_matrix.json, class_matrix_wide.json, class_matrix_banded.json"""
     cases = []
-    for path in (FIXTURE, FIXTURE_WIDE):
+    for path in (FIXTURE, FIXTURE_WIDE, FIXTURE_BANDED):
         with open(path) as f:
             cases += json.load(f)["cases"]
     return cases
@@ -417,21 +524,27 @@ def main():
     round-trip byte for byte); only cases they lack are computed.  Delete a fixture to regenerate its cases."""
     from oracle import oracle_py as O
     O.build()
-    have = {case_id(c): c for c in load_cases()} if os.path.exists(FIXTURE) and os.path.exists(FIXTURE_WIDE) else {}
+    have = {}
+    for path in (FIXTURE, FIXTURE_WIDE, FIXTURE_BANDED):   # (a fixture that is not there: its cases are computed)
+        if os.path.exists(path):
+            with open(path) as f:
+                have.update({case_id(c): c for c in json.load(f)["cases"]})
     listed = list_cases()
     cases = [c for c in listed if case_id(c) not in have]
     # the long ones first, so that the pool does not end on one of them
-    order = sorted(range(len(cases)), key=lambda i: -capacity(cases[i]["W"], cases[i]["NW"], cases[i]["rm"]))
+    order = sorted(range(len(cases)), key=lambda i: -cases[i].get("top", capacity(cases[i]["W"], cases[i]["NW"], cases[i]["rm"])))
     with mp.Pool(min(16, max(1, os.cpu_count() or 1))) as pool:
         done = pool.map(run_case, [cases[i] for i in order], chunksize=1)
     have.update({case_id(c): c for c in done})
     res = [have[case_id(c)] for c in listed]
     dump = lambda c: json.dumps(c, indent=None, separators=(",", ":"))
     with open(FIXTURE, "w") as f:       # (one line, as it was first written)
-        f.write(dump({"provenance": PROVENANCE, "cases": [c for c in res if c["family"] not in WIDE_FAMILIES]}) + "\n")
+        f.write(dump({"provenance": PROVENANCE, "cases": [c for c in res if c["family"] not in WIDE_FAMILIES and c["kind"] != "band"]}) + "\n")
     with open(FIXTURE_WIDE, "w") as f:  # (one case per line: a later family shows in a diff as the lines it adds)
         f.write('{"provenance":%s,"cases":[\n%s\n]}\n' % (json.dumps(PROVENANCE), ",\n".join(dump(c) for c in res if c["family"] in WIDE_FAMILIES)))
-    print("wrote", len(res), "cases,", os.path.getsize(FIXTURE), "+", os.path.getsize(FIXTURE_WIDE), "bytes")
+    with open(FIXTURE_BANDED, "w") as f:
+        f.write('{"provenance":%s,"cases":[\n%s\n]}\n' % (json.dumps(PROVENANCE_BANDED), ",\n".join(dump(c) for c in res if c["kind"] == "band")))
+    print("wrote", len(res), "cases,", os.path.getsize(FIXTURE), "+", os.path.getsize(FIXTURE_WIDE), "+", os.path.getsize(FIXTURE_BANDED), "bytes")
 
 
 if __name__ == "__main__":

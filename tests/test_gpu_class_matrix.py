@@ -1,4 +1,4 @@
-"""Every built kernel class against committed oracle output (tests/golden/class_matrix.json and class_matrix_wide.json, made by
+"""Every built kernel class against committed oracle output (tests/golden/class_matrix.json, class_matrix_wide.json and class_matrix_banded.json, made by
 tests/golden/make_class_matrix.py -- see its docstring for the inputs and the families): one block, or one align-only problem,
 per class, with sequences that fill the class's geometry to within three letters, so that the carry scans across strips, the
 wave-to-wave hand-over, the stored-row read-back, the compiled-in thread count, the T < TMAX launch of the 4-byte classes and
@@ -13,7 +13,14 @@ Re-runs at no fixture cost (results do not depend on the geometry):
     the natural (W, NW) case of such a class sweeps its longest sequence at W (both from the width counters);
   * the (12,8) blocks under SXG_POA_FORCE_P16=8,12: the 768-thread launch of the 1 024-thread class, which the chooser never picks;
   * gen2_affine's blocks under SXG_POA_CELL_BYTES=4 (family cb4_affine): the affine 4-byte classes;
-  * the longest packed global align-only query under the wider forced geometries (make_class_matrix.ALIGN_GLOBAL_FORCED)."""
+  * the longest packed global align-only query under the wider forced geometries (make_class_matrix.ALIGN_GLOBAL_FORCED);
+  * the banded sweep's local 2-byte cases under SXG_POA_BAND_CELL_BYTES=4: the 4-byte local kernels, of which the affine ones
+    are reachable through the knob only (the argument of cb4_affine).
+
+The banded sweep (kind "band", row mode 3): one block per strip width W = 6, 8, 11 whose band fills the one-wave window, per band
+mode, alignment mode and gap model -- the variant line must name W (which holds the product's band_strip_width, a HIP header's,
+equal to the model's and the oracle's at the lengths where it changes), tmax 64, the band cell bytes, ds 0 and the gap model,
+which is what tells the two kernels of a class line apart."""
 import os
 import re
 import sys
@@ -174,3 +181,59 @@ def test_align_only_classes(engine, monkeypatch, capfd, family, mode, sweep):
         if "top" in c and (c["W"], c["NW"]) == (8, 8):
             for f in M.ALIGN_GLOBAL_FORCED:
                 run_align(engine, monkeypatch, capfd, c, force=f)
+
+
+# ---- the banded sweep: nine class lines, 18 kernels (tests/test_class_matrix_fixture.py: covered_band_kernels)
+
+def run_band(engine, monkeypatch, capfd, case, knob4=False):
+    label = M.case_id(case) + ("+bcb4" if knob4 else "")
+    monkeypatch.setenv("SXG_POA_NO_SPREAD", "1")
+    monkeypatch.setenv("SXG_POA_DEBUG", "1")
+    for name in ("SXG_POA_NO_PACKED", "SXG_POA_CELL_BYTES", "SXG_POA_FORCE_P16", "SXG_POA_BAND_CELL_BYTES"):
+        monkeypatch.delenv(name, raising=False)
+    if knob4:
+        monkeypatch.setenv("SXG_POA_BAND_CELL_BYTES", "4")
+    seqs = M.case_inputs(case)
+    assert [len(s) for s in seqs] == case["seq_lens"], label
+    capfd.readouterr()
+    res = engine.run_blocks([seqs], Params(*case["params"], case["mode"] | 0x10, case["banded"]))[0]
+    st = engine.stats()
+    err = capfd.readouterr().err
+    assert res.status == 0, (label, res.status)          # (never ST_INTERNAL, never a refused sweep)
+    got = {"scores": [int(x) for x in res.scores], "cells": int(res.cells.sum()), "n_nodes": int(len(res.node_code)), "n_edges": int(len(res.edge_tail)),
+           "digests": M.digest_block(res.node_code, res.node_rank, res.node_group, res.edge_tail, res.edge_head, res.edge_weight, res.paths)}
+    print(label, got["scores"], got["cells"], got["n_nodes"], got["n_edges"], st["retries"])
+    for k, v in got.items():
+        assert v == case[k], (label, k, v, case[k])
+    kind, rm, cb, tmax, W, sw, ds = M.case_class(case, knob4)
+    assert (kind, rm, tmax, W, sw, ds) == (0, 3, 64, case["W"], 1 - case["mode"], 0) and cb == (2 if not knob4 and sw and M.code_bits(tuple(case["params"])) <= 16 else 4), label
+    assert (st["dom_row_mode"], st["dom_threads"], st["dom_cols_per_lane"]) == (3, 64, 2 * W), (label, st)
+    lines = VARIANT_LINE.findall(err)
+    assert len(lines) == 1, (label, lines, [x for x in err.splitlines() if "round" in x])
+    T, lw, cvx, lrm, attempt, ltmax, lcb, lds, lw2 = map(int, lines[0])
+    assert (T, lw, lrm, attempt, ltmax, lcb, lds, lw2) == (64, W, 3, 0, 64, cb, 0, 0), (label, lines)
+    assert cvx == int(M.normalise(tuple(case["params"]))[6]), (label, lines)
+    assert st["retries"] == 0 and st["dp_launches"] == 1, (label, st)
+    return W, cb, sw, cvx
+
+
+BAND_CASES = [(W, 0, f) for W in (6, 8, 11) for f in M.BAND_LOCAL_FAMILIES] + [(W, 1, None) for W in (6, 8, 11)]
+
+
+@pytest.mark.parametrize("W,mode,family", BAND_CASES, ids=["W%d-%s" % (W, "local-" + f if f else "global") for W, m, f in BAND_CASES])
+def test_banded_classes(engine, monkeypatch, capfd, W, mode, family):
+    cases = [c for c in CASES if c["kind"] == "band" and c["W"] == W and c["mode"] == mode and (family is None or c["family"] == family)]
+    ran = set()
+    if mode == 0:     # the static and the adaptive band; the 2-byte families again with 4-byte band cells
+        assert sorted(c["banded"] for c in cases) == [1, 2]
+        for c in cases:
+            ran.add(run_band(engine, monkeypatch, capfd, c))
+            if family != "cb4_convex":
+                ran.add(run_band(engine, monkeypatch, capfd, c, knob4=True))
+        cvx = int(family != "gen2_affine")
+        assert ran == ({(W, 4, 1, 1)} if family == "cb4_convex" else {(W, 2, 1, cvx), (W, 4, 1, cvx)})
+    else:             # global: the adaptive band only, 4-byte cells by rule, a convex and an affine set
+        assert [c["banded"] for c in cases] == [2, 2] and sorted(c["family"] for c in cases) == sorted(M.BAND_GLOBAL_FAMILIES[W])
+        for c in cases:
+            ran.add(run_band(engine, monkeypatch, capfd, c))
+        assert ran == {(W, 4, 0, 0), (W, 4, 0, 1)}
