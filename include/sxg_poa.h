@@ -43,7 +43,10 @@
 extern "C" {
 #endif
 
-/* 5 (addition, no number change, no struct change): sxg_poa_set_long_blocks, sxg_poa_group_set_long_blocks, sxg_poa_get_tile_stats
+/* 5 (addition, no number change, no struct change): sxg_poa_letters_*, sxg_poa_range_gather, sxg_poa_repeat_scan_ranges,
+ *    sxg_poa_block_identity_ranges and their structs -- a graph's path letters resident on the device, and the repeat scan and the
+ *    identity estimate fed with ranges of them.
+ * 5 (addition, no number change, no struct change): sxg_poa_set_long_blocks, sxg_poa_group_set_long_blocks, sxg_poa_get_tile_stats
  *    and SXG_POA_MAX_SEQ_LEN_TILED -- the 32-bit sweep in column tiles: with the switch on, one length limit for every mode.
  * 5 (addition, no number change, no struct change): sxg_poa_group_* -- one process, several GPUs: a group of handles, one host
  *    thread per member, the results reassembled in the batch's block order (trimmed MSA and block cycles included).
@@ -606,6 +609,67 @@ typedef struct sxg_poa_repeat_in {
 /* caller-allocated [n_seqs] each; match: NULL or [sum of n_lags] */
 int sxg_poa_repeat_scan_batch(sxg_poa_handle *h, const sxg_poa_repeat_in *in, int32_t *n_lags, int32_t *best, double *dev, double *v,
                               int32_t *status, int32_t *match);
+
+/* Resident path letters (an addition to ABI 5, no struct changed): a graph's path letters go to the device ONCE, and the repeat
+ * scan and the identity estimate take RANGES of them; a kernel cuts the ranges out of the resident copy into the layout each
+ * consumer reads.  Both providers of the host library are fed ranges of paths -- contiguous substrings of
+ * a path's spelled sequence --, so this replaces the per-call concatenation and upload of those substrings.
+ *   Which letters a call uses.  A ranges call works on the resident letters if their id equals letters_id.  If it differs and
+ *     letters != NULL with letters->id == letters_id, the call uploads them first: the one upload of an iteration, whichever
+ *     provider comes first; a caller that always passes the pointer keeps no call order and cannot read stale letters.  If the
+ *     id differs and there is no usable pointer, the call returns SXG_E_INVALID before any work.  id 0 names nothing.
+ *   Validation.  A range with path outside 0 .. n_paths - 1, begin < 0, end < begin or end beyond the path is SXG_E_INVALID; the
+ *     message names the range, and nothing is launched.  Empty ranges are legal; ranges may overlap and may repeat.
+ *   Results.  Results, statuses and return codes are those of the `bases` calls on the same sequences, array for array:
+ *     SXG_ST_TOO_LONG / SXG_E_BLOCK, the identity's min_len filter and its 65 536 cap, the rounds under a small memory budget,
+ *     `match`, and sxg_poa_stats -- whose kernel_ms now includes the gather, which sxg_poa_letters_stats also reports by itself
+ *     (dp_launches counts the gather as one more launch).  Only the sequences that take part are cut out.
+ *   Memory.  The resident letters lie OUTSIDE sxg_poa_set_memory_budget, like the handle's result buffers; they are counted in
+ *     device_bytes of the ranges calls.  They survive sxg_poa_batch_* calls and are freed by _drop, by a replacing upload or by
+ *     sxg_poa_destroy.  An allocation that fails is SXG_E_NOMEM and leaves nothing resident.
+ *   Upload.  Staged through pinned memory of bounded size -- two buffers of the handle's pool in flight --, never a pinned copy of
+ *     the whole text.
+ *   Scope.  Every handle holds its own copy; a device-group member is a handle.  The sharded entry points are not touched.
+ *   Orientation.  There is no reverse-complement flag: ranges are read in step orientation, the path's own spelling, and neither
+ *     consumer has a use for another.
+ * The gather: a work item is a chunk of sxg_poa_letters_geometry's chunk_bytes destination bytes, dealt grid-stride, its ranges
+ * found on the device from the prefix sums of the range lengths by binary search (the host sends no item list, no atomics); 16-byte
+ * stores inside a range, byte stores for the at most 15 head and 15 tail bytes, unaligned 16-byte loads that stay inside the
+ * range: the resident buffer needs no padding.  coded == 1 applies the table of the identity estimate: either case of A C G T ->
+ * 0..3, anything else -> 4. */
+typedef struct sxg_poa_letters {   /* a graph's path letters, on the host */
+    uint64_t id;                   /* caller-chosen, non-zero: names this set of letters */
+    int64_t n_paths;
+    const int64_t *path_off;       /* [n_paths+1], path_off[0] == 0 */
+    const uint8_t *letters;        /* [path_off[n_paths]] the bytes as they stand in the graph, step orientation */
+} sxg_poa_letters;
+typedef struct sxg_poa_range { int64_t path, begin, end; } sxg_poa_range;   /* letters [begin, end) of `path` */
+
+int  sxg_poa_letters_upload(sxg_poa_handle *h, const sxg_poa_letters *l);   /* replaces what is resident */
+void sxg_poa_letters_drop(sxg_poa_handle *h);
+int  sxg_poa_letters_resident(sxg_poa_handle *h, uint64_t *id, int64_t *n_paths, int64_t *n_letters);   /* id 0 = none */
+/* since the handle was created: uploads and their bytes, the gathers' kernel time (HIP events) and the bytes they wrote */
+int  sxg_poa_letters_stats(sxg_poa_handle *h, uint64_t *uploads, uint64_t *bytes_uploaded, double *gather_ms, uint64_t *gathered_bytes);
+void sxg_poa_letters_geometry(int32_t *chunk_bytes);   /* the gather kernel's work-item size, for tests */
+
+/* what the gather kernel writes, for callers and tests: coded == 0 the bytes as they are, coded == 1 the identity code */
+int  sxg_poa_range_gather(sxg_poa_handle *h, const sxg_poa_letters *l, uint64_t id, int64_t n, const sxg_poa_range *r, int coded, uint8_t *out /* [sum of lengths] */);
+
+typedef struct sxg_poa_repeat_ranges_in {
+    const sxg_poa_letters *letters; uint64_t letters_id;
+    int64_t n_seqs; const sxg_poa_range *ranges;
+    uint64_t min_copy, max_copy, stride;
+} sxg_poa_repeat_ranges_in;
+/* as sxg_poa_repeat_scan_batch on the sequences the ranges spell */
+int sxg_poa_repeat_scan_ranges(sxg_poa_handle *h, const sxg_poa_repeat_ranges_in *in, int32_t *n_lags, int32_t *best, double *dev, double *v, int32_t *status, int32_t *match);
+
+typedef struct sxg_poa_identity_ranges_in {
+    const sxg_poa_letters *letters; uint64_t letters_id;
+    int32_t n_blocks; const int32_t *blk_off; const sxg_poa_range *ranges;
+    int32_t kmer_size, min_len; double percentile;
+} sxg_poa_identity_ranges_in;
+/* as sxg_poa_block_identity_batch on the sequences the ranges spell, coded by the table above */
+int sxg_poa_block_identity_ranges(sxg_poa_handle *h, const sxg_poa_identity_ranges_in *in, int32_t *n_used, int32_t *inter, int32_t *uni, int32_t *status);
 
 /* The node order of prep (src/prep.cpp:11-163: odgi's path_linear_sgd_order, called from src/main.cpp:423-433 before every
  * iteration unless -n), decree Y of DESIGN.md section 9.  odgi is absent from the snapshot and its hogwild updates are not

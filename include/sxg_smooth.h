@@ -151,6 +151,41 @@ typedef int (*sxg_repeat_fn)(void *ctx, const sxg_poa_repeat_in *in, int32_t *n_
 int sxg_blockset_break_scan(const sxg_graph *g, const sxg_blockset *in, uint64_t max_poa_length, uint64_t min_copy_length,
                             uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest,
                             sxg_repeat_fn scan, void *ctx, sxg_blockset **out, int64_t *n_cut, int64_t *n_repeat, int64_t *n_host);
+/* Range providers (additions to ABI 2, no struct changed).  Both providers above are fed ranges of paths, contiguous substrings of
+ * a path's spelled sequence; with these forms the library sends the RANGES -- sxg_poa_range{path, pos[begin], pos[end]} in letters of
+ * the path -- and the graph's path letters by pointer, and builds no sequence (include/sxg_poa.h, "Resident path letters": the engine
+ * uploads the letters once per graph, whichever provider comes first).  Everything behind the provider call is shared with the
+ * `bases` forms: the checks of the returned counts, the decision, the host's own scan or estimate of a declined item; a provider
+ * error fails the call.
+ * sxg_graph_path_letters: the graph's path letters, concatenated once and cached in the graph (OpenMP over paths; path p ==
+ * its spelled sequence); out points into the graph and lives as long as it; id is unique per graph object in the process. */
+int sxg_graph_path_letters(const sxg_graph *g, sxg_poa_letters *out);
+typedef int (*sxg_repeat_ranges_fn)(void *ctx, const sxg_poa_repeat_ranges_in *in, int32_t *n_lags, int32_t *best, double *dev, double *v,
+                                    int32_t *status, int32_t *match);
+typedef int (*sxg_identity_ranges_fn)(void *ctx, const sxg_poa_identity_ranges_in *in, int32_t *n_used, int32_t *inter, int32_t *uni,
+                                      int32_t *status);
+/* as sxg_blockset_break_scan (scan must not be NULL) */
+int sxg_blockset_break_scan_ranges(const sxg_graph *g, const sxg_blockset *in, uint64_t max_poa_length, uint64_t min_copy_length,
+                                   uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest,
+                                   sxg_repeat_ranges_fn scan, void *ctx, sxg_blockset **out, int64_t *n_cut, int64_t *n_repeat,
+                                   int64_t *n_host);
+/* as sxg_blockset_identity_thresholds (ident == NULL: the host estimator) */
+int sxg_blockset_identity_thresholds_ranges(const sxg_graph *g, const sxg_blockset *b, int32_t kmer_size, uint64_t max_depth,
+                                            sxg_identity_ranges_fn ident, void *ctx, float *est_identity_threshold, int32_t *n_used);
+/* The range providers of an iteration and their context (the engine handle).  sxg_smooth_iteration_ranges is the iteration with
+ * the identity estimate of -a fed ranges: mp == NULL (then out_maf must be NULL and device_rows 0) is sxg_smooth_gfa_adaptive,
+ * mp != NULL sxg_smooth_maf_gfa_adaptive, and with device_rows != 0 sxg_smooth_maf_gfa_device_rows; rp == NULL or rp->identity ==
+ * NULL: the host estimator.  rp->scan is not called by the iteration (block discovery runs before it: sxg_blockset_break_scan_ranges);
+ * the record carries it so that a caller binds both providers to one handle in one place. */
+typedef struct sxg_range_providers {
+    sxg_repeat_ranges_fn scan;
+    sxg_identity_ranges_fn identity;
+    void *ctx;
+} sxg_range_providers;
+struct sxg_merge_params;
+int sxg_smooth_iteration_ranges(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p, const struct sxg_merge_params *mp,
+                                sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, const sxg_range_providers *rp, int device_rows,
+                                char **out_gfa, char **out_maf, int64_t *n_flipped);
 /* The splitting half of break_blocks, src/breaks.cpp:335-586 (-I / --block-id-min, -R / --block-ratio-min and the dedup
  * depth; an addition to ABI 2, no struct changed): a block whose sequences fall into more than one identity group becomes one
  * block per group.  Decree P3 of DESIGN.md section 9, statement by statement as the reference: nothing happens to a block

@@ -31,6 +31,7 @@
 #include "poa_mash.hip.h"          // its mash-based branch: k-mer sets, intersections, the walk of M4 (kernels in kern_split.hip)
 #include "poa_identity.hip.h"      // the identity estimate of -a on those sets: all pairs of a block, the percentile's pair (kern_split.hip)
 #include "poa_repeat.hip.h"        // the tandem-repeat scan of the cutting half of break_blocks: counts per lag, then the double pass (kern_repeat.hip)
+#include "poa_letters.hip.h"       // the resident path letters: the gather that cuts ranges out of them for the two calls above (kern_letters.hip)
 #include "poa_sgd.hip.h"           // the path-guided SGD node order of prep: argument struct and launchers (kernels in kern_sgd.hip)
 #include "poa_msa.hip.h"           // the trimmed MSA (want_msa == SXG_MSA_TRIMMED): argument structs and launchers (kernels in kern_msa.hip)
 
@@ -352,6 +353,19 @@ struct sxg_poa_handle {
     std::vector<int32_t> d_trim_h;   // host copy of d_trim
     std::vector<int32_t> msa_cols_h;
     double msa_cols_ms = 0, msa_rows_ms = 0;
+    // resident path letters (sxg_poa_letters_*): outside the memory budget, kept across batches; path_off is the host's copy for
+    // the validation of ranges, d_src / d_off the per-call arrays of the gather (kept here so that they outlive its launch)
+    struct Letters {
+        uint64_t id = 0;
+        int64_t n_paths = 0, n_letters = 0;
+        std::vector<int64_t> path_off;
+        DevBuf d, d_src, d_off;
+        DevEvent g0, g1;
+        bool pending = false;   // a gather stands between g0 and g1 and is not yet in the sums
+        uint64_t pending_bytes = 0;
+        uint64_t uploads = 0, bytes_uploaded = 0, gathered_bytes = 0;
+        double gather_ms = 0;
+    } letters;
     sxg_poa_stats stats{};
     sxg_poa_width_stats wstats{};   // packed sweeps of the last execute per strip width (sxg_poa_get_width_stats)
     sxg_poa_twin_stats tstats{};    // twin steps and join rows of the last execute (sxg_poa_get_twin_stats)
@@ -3010,6 +3024,183 @@ extern "C" int sxg_poa_kmer_jaccard_batch(sxg_poa_handle* h, int64_t n_seqs, con
 }
 
 // ---------------------------------------------------------------------------------------
+// Resident path letters (include/sxg_poa.h): one copy of a graph's path letters per handle, outside the
+// memory budget; the ranges calls below cut their sequences out of it with range_gather_kernel (poa_letters.hip.h /
+// kern_letters.hip) instead of uploading them.  Here the staged upload, the validation of ranges and the gather's launch and timing.
+static_assert(SXG_LETTERS_CHUNK % 16 == 0, "a chunk is whole granules");
+namespace {
+constexpr size_t LETTERS_STAGE_BYTES = (size_t)8 << 20;   // one pinned staging buffer of the upload; two are in flight
+struct PinLoan {   // a buffer of the pool, given back on every way out
+    PinPool* pool = nullptr;
+    void* p = nullptr;
+    PinLoan() = default;
+    PinLoan(const PinLoan&) = delete;
+    PinLoan& operator=(const PinLoan&) = delete;
+    ~PinLoan() { if (p) pool->release(p); }
+};
+void letters_forget(sxg_poa_handle* h) {
+    auto& L = h->letters;
+    L.id = 0; L.n_paths = 0; L.n_letters = 0;
+    L.path_off.clear();
+    L.d.release();
+}
+int letters_upload(sxg_poa_handle* h, const sxg_poa_letters* l) {
+    if (!l || l->id == 0 || l->n_paths < 0 || !l->path_off || l->path_off[0] != 0) return fail(SXG_E_INVALID, "letters: id must be non-zero, path_off[0] must be 0");
+    for (int64_t p = 0; p < l->n_paths; ++p)
+        if (l->path_off[p + 1] < l->path_off[p]) return fail(SXG_E_INVALID, "letters: path_off not monotone");
+    const int64_t n = l->path_off[l->n_paths];
+    if (n > 0 && !l->letters) return fail(SXG_E_INVALID, "letters is NULL");
+    auto& L = h->letters;
+    letters_forget(h);   // (a failure below leaves nothing resident)
+    if (int rc = L.d.ensure((size_t)std::max<int64_t>(n, 1))) return rc;
+    PinLoan pin[2];
+    DevEvent done[2];
+    if (h->pins && !getenv("SXG_POA_NO_PINNED"))
+        for (int b = 0; b < 2 && (b == 0 || (size_t)n > LETTERS_STAGE_BYTES); ++b) {
+            pin[b].pool = h->pins.get();
+            pin[b].p = h->pins->acquire(std::min<size_t>(LETTERS_STAGE_BYTES, (size_t)std::max<int64_t>(n, 1)));
+            if (pin[b].p && done[b].create() != hipSuccess) { (void)hipGetLastError(); h->pins->release(pin[b].p); pin[b].p = nullptr; }
+        }
+    struct Forget { sxg_poa_handle* h; ~Forget() { if (h) letters_forget(h); } } forget{h};
+    int64_t k = 0;
+    for (int64_t at = 0; at < n; at += (int64_t)LETTERS_STAGE_BYTES, ++k) {
+        const size_t len = (size_t)std::min<int64_t>((int64_t)LETTERS_STAGE_BYTES, n - at);
+        const int b = pin[1].p ? (int)(k & 1) : 0;
+        if (pin[b].p) {
+            if (k >= (pin[1].p ? 2 : 1)) HIPCHK(hipEventSynchronize(done[b]));   // (the copy that last read this buffer)
+            memcpy(pin[b].p, l->letters + at, len);
+            HIPCHK(hipMemcpyAsync(L.d.as<uint8_t>() + at, pin[b].p, len, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipEventRecord(done[b], h->stream));
+        } else {   // (no pinned buffer to borrow: the runtime stages the pageable copy itself)
+            HIPCHK(hipMemcpyAsync(L.d.as<uint8_t>() + at, l->letters + at, len, hipMemcpyHostToDevice, h->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    forget.h = nullptr;
+    L.id = l->id; L.n_paths = l->n_paths; L.n_letters = n;
+    L.path_off.assign(l->path_off, l->path_off + l->n_paths + 1);
+    ++L.uploads; L.bytes_uploaded += (uint64_t)n;
+    return SXG_OK;
+}
+// The letters a ranges call works on -- uploaded here when other letters, or none, are resident and the caller passed these --
+// and its ranges, checked: len[s] and src[s], the length of range s and where it starts in the resident letters.
+int letters_resolve(sxg_poa_handle* h, const sxg_poa_letters* l, uint64_t id, int64_t n, const sxg_poa_range* r, const char* what,
+                    std::vector<int64_t>& len, std::vector<int64_t>& src) {
+    auto& L = h->letters;
+    if (id == 0) return fail(SXG_E_INVALID, std::string(what) + ": letters_id is 0");
+    if (n < 0 || (n > 0 && !r)) return fail(SXG_E_INVALID, std::string(what) + ": ranges is NULL");
+    if (L.id != id) {
+        if (!l || l->id != id) return fail(SXG_E_INVALID, std::string(what) + ": letters " + std::to_string(id) + " are not resident and were not passed");
+        if (int rc = letters_upload(h, l)) return rc;
+    }
+    len.assign((size_t)n, 0); src.assign((size_t)n, 0);
+    for (int64_t s = 0; s < n; ++s) {
+        if (r[s].path < 0 || r[s].path >= L.n_paths || r[s].begin < 0 || r[s].end < r[s].begin ||
+            r[s].end > L.path_off[(size_t)r[s].path + 1] - L.path_off[(size_t)r[s].path])
+            return fail(SXG_E_INVALID, std::string(what) + ": range " + std::to_string(s) + " (path " + std::to_string(r[s].path) + ", " + std::to_string(r[s].begin) + " .. " +
+                                           std::to_string(r[s].end) + ") lies outside the resident letters");
+        len[(size_t)s] = r[s].end - r[s].begin;
+        src[(size_t)s] = L.path_off[(size_t)r[s].path] + r[s].begin;
+    }
+    return SXG_OK;
+}
+// the gather's per-call arrays, enqueued on the handle's stream: where every destination sequence starts in the resident letters
+// and -- unless the caller has them on the device already -- the destination offsets.  The caller waits for the stream.
+int letters_stage(sxg_poa_handle* h, const std::vector<int64_t>& src, const int64_t* dst_off) {
+    auto& L = h->letters;
+    const size_t n = src.size();
+    if (int rc = L.d_src.ensure(8 * std::max<size_t>(n, 1))) return rc;
+    if (n) HIPCHK(hipMemcpyAsync(L.d_src.p, src.data(), 8 * n, hipMemcpyHostToDevice, h->stream));
+    if (dst_off) {
+        if (int rc = L.d_off.ensure(8 * (n + 1))) return rc;
+        HIPCHK(hipMemcpyAsync(L.d_off.p, dst_off, 8 * (n + 1), hipMemcpyHostToDevice, h->stream));
+    }
+    return SXG_OK;
+}
+// the launch, between the call's timer_start and timer_stop, bracketed by events of its own; letters_account after timer_stop
+int letters_launch(sxg_poa_handle* h, int64_t n, int64_t total, const int64_t* d_dst_off, uint8_t* d_dst, int coded) {
+    auto& L = h->letters;
+    if (n <= 0 || total <= 0) return SXG_OK;
+    if (!L.g0.raw) HIPCHK(L.g0.create());
+    if (!L.g1.raw) HIPCHK(L.g1.create());
+    LettersGatherArgs A;
+    A.letters = L.d.as<uint8_t>(); A.dst = d_dst; A.dst_off = d_dst_off; A.src = L.d_src.as<int64_t>(); A.n = n; A.total = total;
+    const int64_t groups = std::min<int64_t>(sxg_letters_n_chunks(total), (int64_t)std::max(h->num_cu, 1) * 8);
+    HIPCHK(hipEventRecord(L.g0, h->stream));
+    sxg_letters_launch_gather(A, coded, (int)groups, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(L.g1, h->stream));
+    L.pending = true; L.pending_bytes = (uint64_t)total;
+    return SXG_OK;
+}
+int letters_account(sxg_poa_handle* h) {
+    auto& L = h->letters;
+    if (!L.pending) return SXG_OK;
+    L.pending = false;
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, L.g0, L.g1));
+    L.gather_ms += ms; L.gathered_bytes += L.pending_bytes;
+    return SXG_OK;
+}
+}  // namespace
+
+extern "C" int sxg_poa_letters_upload(sxg_poa_handle* h, const sxg_poa_letters* l) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    RoctxRange range("sxg_poa_letters_upload");
+    HIPCHK(hipSetDevice(h->device));
+    return letters_upload(h, l);
+}
+extern "C" void sxg_poa_letters_drop(sxg_poa_handle* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    letters_forget(h);
+}
+extern "C" int sxg_poa_letters_resident(sxg_poa_handle* h, uint64_t* id, int64_t* n_paths, int64_t* n_letters) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    if (id) *id = h->letters.id;
+    if (n_paths) *n_paths = h->letters.n_paths;
+    if (n_letters) *n_letters = h->letters.n_letters;
+    return SXG_OK;
+}
+extern "C" int sxg_poa_letters_stats(sxg_poa_handle* h, uint64_t* uploads, uint64_t* bytes_uploaded, double* gather_ms, uint64_t* gathered_bytes) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    if (uploads) *uploads = h->letters.uploads;
+    if (bytes_uploaded) *bytes_uploaded = h->letters.bytes_uploaded;
+    if (gather_ms) *gather_ms = h->letters.gather_ms;
+    if (gathered_bytes) *gathered_bytes = h->letters.gathered_bytes;
+    return SXG_OK;
+}
+extern "C" void sxg_poa_letters_geometry(int32_t* chunk_bytes) {
+    if (chunk_bytes) *chunk_bytes = SXG_LETTERS_CHUNK;
+}
+extern "C" int sxg_poa_range_gather(sxg_poa_handle* h, const sxg_poa_letters* l, uint64_t id, int64_t n, const sxg_poa_range* r, int coded, uint8_t* out) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    RoctxRange range("sxg_poa_range_gather");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    std::vector<int64_t> len, src;
+    if (int rc = letters_resolve(h, l, id, n, r, "range_gather", len, src)) return rc;
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    for (int64_t s = 0; s < n; ++s) off[(size_t)s + 1] = off[(size_t)s] + len[(size_t)s];
+    const int64_t total = off[(size_t)n];
+    if (total == 0) return SXG_OK;
+    if (!out) return fail(SXG_E_INVALID, "range_gather: out is NULL");
+    DevBuf d_dst;
+    if (int rc = d_dst.ensure((size_t)total)) return rc;
+    if (int rc = letters_stage(h, src, off.data())) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    float ms = 0;
+    if (int rc = timer_start(h)) return rc;
+    if (int rc = letters_launch(h, n, total, h->letters.d_off.as<int64_t>(), d_dst.as<uint8_t>(), coded ? 1 : 0)) return rc;
+    if (int rc = timer_stop(h, &ms)) return rc;
+    if (int rc = letters_account(h)) return rc;
+    HIPCHK(hipMemcpy(out, d_dst.p, (size_t)total, hipMemcpyDeviceToHost));
+    h->stats.kernel_ms = ms; h->stats.dom_kernel_ms = ms; h->stats.dp_launches = 1; h->stats.dom_threads = SXG_LETTERS_THREADS;
+    h->stats.device_bytes = h->letters.d.cap + h->letters.d_src.cap + h->letters.d_off.cap + d_dst.cap;
+    return SXG_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // The identity estimate of the adaptive scores (A14, src/smooth.cpp:1972-2069): decree Q (include/sxg_poa.h).
 // Kernels in poa_identity.hip.h / kern_split.hip on the sets of poa_mash.hip.h; here the validation, the sequences that take
 // part (the device sees no others), Q3's ranks, the rounds and the timing.  Memory: the sets (8 bytes per base that takes part
@@ -3017,8 +3208,11 @@ extern "C" int sxg_poa_kmer_jaccard_batch(sxg_poa_handle* h, int64_t n_seqs, con
 // bounded by it on its own, as in the split calls --; blocks go round after round, in order, as many as their words fit; a
 // block whose words alone do not fit, or sets that do not, are SXG_E_NOMEM.  Everything is enqueued on the handle's stream
 // without a host wait in between: the words' buffer is reused by the next round in stream order.
-extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_identity_in* in, int32_t* n_used, int32_t* inter, int32_t* uni,
-                                            int32_t* status) {
+// Three steps: (a) validation and planning from the sequence LENGTHS; (b) the letters of the sequences that take part: uploaded
+// from in->bases, or -- src != nullptr, the ranges entry point: src[s] is where sequence s starts in the resident letters and
+// in->bases is not read -- cut out of the resident letters by the gather, coded; (c) the launches and the downloads.
+static int block_identity_run(sxg_poa_handle* h, const sxg_poa_identity_in* in, const int64_t* src, const char* name, int32_t* n_used, int32_t* inter,
+                              int32_t* uni, int32_t* status) {
     if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
     const int nb = in->n_blocks;
     if (nb < 0 || (nb > 0 && (!in->blk_off || !in->seq_off || !n_used || !inter || !uni || !status))) return fail(SXG_E_INVALID, "block_identity: NULL arrays");
@@ -3032,15 +3226,16 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
     const int64_t ns_in = nb ? in->blk_off[nb] : 0;
     for (int64_t s = 0; s < ns_in; ++s)
         if (in->seq_off[s + 1] < in->seq_off[s]) return fail(SXG_E_INVALID, "seq_off not monotone");
-    if (ns_in > 0 && in->seq_off[ns_in] > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
-    RoctxRange range("sxg_poa_block_identity_batch");
+    if (!src && ns_in > 0 && in->seq_off[ns_in] > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
+    RoctxRange range(name);
     HIPCHK(hipSetDevice(h->device));
     h->stats = sxg_poa_stats{};
     // the sequences that take part, block after block: the batch the device sees (a block with one of them too long stays out)
     std::vector<int32_t> blk_off((size_t)nb + 1, 0);
     std::vector<int64_t> seq_off{0}, pair_off((size_t)nb + 1, 0), idx((size_t)std::max(nb, 1), 0);
     std::vector<uint8_t> bases;
-    bases.reserve((size_t)(ns_in ? in->seq_off[ns_in] : 0));
+    std::vector<int64_t> gather_src;
+    if (!src) bases.reserve((size_t)(ns_in ? in->seq_off[ns_in] : 0));
     bool any_failed = false;
     int64_t max_pairs = 0;
     for (int b = 0; b < nb; ++b) {
@@ -3060,6 +3255,7 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
             for (int64_t s = in->blk_off[b]; s < in->blk_off[b + 1]; ++s) {
                 const int64_t o = in->seq_off[s], len = in->seq_off[s + 1] - o;
                 if (len < in->min_len) continue;
+                if (src) { gather_src.push_back(src[s]); seq_off.push_back(seq_off.back() + len); continue; }
                 const size_t at = bases.size();
                 bases.resize(at + (size_t)len);
                 for (int64_t x = 0; x < len; ++x) bases[at + (size_t)x] = in->bases[o + x] > 4 ? 4 : in->bases[o + x];
@@ -3094,7 +3290,8 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
         int rc;
         if ((rc = seqs.seq_off.ensure(8 * (size_t)(ns + 1))) || (rc = seqs.bases.ensure((size_t)nbases + 16))) return rc;
         HIPCHK(hipMemcpyAsync(seqs.seq_off.p, seq_off.data(), 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(seqs.bases.p, bases.data(), (size_t)nbases, hipMemcpyHostToDevice, h->stream));
+        if (src) { if ((rc = letters_stage(h, gather_src, nullptr))) return rc; }
+        else HIPCHK(hipMemcpyAsync(seqs.bases.p, bases.data(), (size_t)nbases, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         if ((rc = split_up(h, d_blk_off, blk_off.data(), (size_t)nb + 1)) || (rc = split_up(h, d_pair_off, pair_off.data(), (size_t)nb + 1)) ||
             (rc = split_up(h, d_idx, idx.data(), (size_t)nb)) || (rc = d_inter.ensure(4 * (size_t)nb)) || (rc = d_uni.ensure(4 * (size_t)nb)) ||
@@ -3112,6 +3309,10 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
         uint64_t launches = 1;
         float ms = 0;
         if (int rc = timer_start(h)) return rc;
+        if (src) {   // the taking-part ranges out of the resident letters, coded, into the layout the sketch reads
+            if (int rc = letters_launch(h, ns, nbases, seqs.seq_off.as<int64_t>(), seqs.bases.as<uint8_t>(), 1)) return rc;
+            ++launches;
+        }
         if (int rc = mash_sketch(h, seqs, ns, seq_off.data(), work, k, false, &dev_bytes)) return rc;   // Q1: M1's sets, one launch
         for (size_t r = 0, b0 = 0; r < round_end.size(); b0 = (size_t)round_end[r++]) {
             const int32_t b1 = round_end[r];
@@ -3133,13 +3334,38 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
             launches += 2;
         }
         if (int rc = timer_stop(h, &ms)) return rc;
+        if (int rc = letters_account(h)) return rc;
         HIPCHK(hipMemcpy(inter, d_inter.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(uni, d_uni.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
-        split_stats(h, ms, 0, pair_slots, dev_bytes + d_words.cap);
-        h->stats.dp_launches = launches;   // the sketch + (pairs, select) of every round
+        split_stats(h, ms, 0, pair_slots, dev_bytes + d_words.cap + (src ? h->letters.d.cap + h->letters.d_src.cap : 0));
+        h->stats.dp_launches = launches;   // the sketch + (pairs, select) of every round (+ the gather of a ranges call)
     }
     if (any_failed) return fail(SXG_E_BLOCK, "a block holds a sequence longer than SXG_POA_MAX_SEQ_LEN");
     return SXG_OK;
+}
+extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_identity_in* in, int32_t* n_used, int32_t* inter, int32_t* uni,
+                                            int32_t* status) {
+    return block_identity_run(h, in, nullptr, "sxg_poa_block_identity_batch", n_used, inter, uni, status);
+}
+extern "C" int sxg_poa_block_identity_ranges(sxg_poa_handle* h, const sxg_poa_identity_ranges_in* in, int32_t* n_used, int32_t* inter, int32_t* uni,
+                                             int32_t* status) {
+    if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
+    const int nb = in->n_blocks;
+    if (nb < 0 || (nb > 0 && !in->blk_off)) return fail(SXG_E_INVALID, "block_identity: NULL arrays");
+    if (nb > 0 && in->blk_off[0] != 0) return fail(SXG_E_INVALID, "blk_off[0] and seq_off[0] must be 0");
+    for (int b = 0; b < nb; ++b)
+        if (in->blk_off[b + 1] < in->blk_off[b]) return fail(SXG_E_INVALID, "blk_off not monotone");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    const int64_t ns = nb ? in->blk_off[nb] : 0;
+    std::vector<int64_t> len, src, seq_off((size_t)ns + 1, 0);
+    if (int rc = letters_resolve(h, in->letters, in->letters_id, ns, in->ranges, "block_identity_ranges", len, src)) return rc;
+    for (int64_t s = 0; s < ns; ++s) seq_off[(size_t)s + 1] = seq_off[(size_t)s] + len[(size_t)s];
+    sxg_poa_identity_in seqs;
+    memset(&seqs, 0, sizeof(seqs));
+    seqs.n_blocks = nb; seqs.blk_off = in->blk_off; seqs.seq_off = seq_off.data();
+    seqs.kmer_size = in->kmer_size; seqs.min_len = in->min_len; seqs.percentile = in->percentile;
+    return block_identity_run(h, &seqs, src.data(), "sxg_poa_block_identity_ranges", n_used, inter, uni, status);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3150,8 +3376,13 @@ extern "C" int sxg_poa_block_identity_batch(sxg_poa_handle* h, const sxg_poa_ide
 // many as their counts fit; a sequence whose counts alone do not fit is SXG_E_NOMEM.  Everything is enqueued on the handle's
 // stream without a host wait in between: the counts' buffer is reused by the next round in stream order.
 static_assert(SXG_POA_REPEAT_MAX_LEN == SXG_REPEAT_MAX_LEN, "length limit of the header");
-extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat_in* in, int32_t* n_lags, int32_t* best, double* dev, double* v,
-                                         int32_t* status, int32_t* match) {
+// Three steps: (a) validation and planning from the sequence LENGTHS; (b) the letters: uploaded from in->bases as they came, or
+// -- src != nullptr, the ranges entry point: src[s] is where sequence s starts in the resident letters and in->bases is not read
+// -- the sequences that are scanned cut out of the resident letters by the gather (the device's offsets then give every other
+// sequence no letters; the budget's sums stay those of the lengths, so the rounds are the bases call's); (c) the launches and
+// the downloads.
+static int repeat_scan_run(sxg_poa_handle* h, const sxg_poa_repeat_in* in, const int64_t* src, const char* name, int32_t* n_lags, int32_t* best, double* dev,
+                           double* v, int32_t* status, int32_t* match) {
     if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
     const int64_t ns = in->n_seqs;
     if (ns < 0 || ns > 0x7fffffff || (ns > 0 && (!in->seq_off || !n_lags || !best || !dev || !v || !status))) return fail(SXG_E_INVALID, "repeat_scan: bad argument");
@@ -3160,8 +3391,8 @@ extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat
     for (int64_t s = 0; s < ns; ++s)
         if (in->seq_off[s + 1] < in->seq_off[s]) return fail(SXG_E_INVALID, "seq_off not monotone");
     const int64_t nbases = ns ? in->seq_off[ns] : 0;
-    if (nbases > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
-    RoctxRange range("sxg_poa_repeat_scan_batch");
+    if (!src && nbases > 0 && !in->bases) return fail(SXG_E_INVALID, "bases is NULL");
+    RoctxRange range(name);
     HIPCHK(hipSetDevice(h->device));
     h->stats = sxg_poa_stats{};
     // what the device sees is 32-bit: a stride or a max_copy beyond the length limit, clamped to it, changes no count
@@ -3223,12 +3454,22 @@ extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat
         }
         DevBuf d_bases, d_seq_off, d_match_off, d_items, d_work, d_match, d_best, d_dev, d_v;
         int rc;
-        if ((rc = d_bases.ensure((size_t)std::max<int64_t>(nbases, 1))) || (rc = d_seq_off.ensure(8 * (size_t)(ns + 1))) || (rc = d_match_off.ensure(8 * (size_t)(ns + 1))) ||
+        std::vector<int64_t> dev_off, gather_src;   // a ranges call: the scanned sequences back to back, and where each comes from
+        if (src) {
+            dev_off.assign((size_t)ns + 1, 0);
+            gather_src.assign((size_t)ns, 0);
+            for (int32_t s : work) { dev_off[(size_t)s + 1] = in->seq_off[s + 1] - in->seq_off[s]; gather_src[(size_t)s] = src[s]; }
+            for (int64_t s = 0; s < ns; ++s) dev_off[(size_t)s + 1] += dev_off[(size_t)s];
+        }
+        const int64_t dev_bases = src ? dev_off[(size_t)ns] : nbases;
+        const int64_t* const seq_off_up = src ? dev_off.data() : in->seq_off;
+        if ((rc = d_bases.ensure((size_t)std::max<int64_t>(dev_bases, 1))) || (rc = d_seq_off.ensure(8 * (size_t)(ns + 1))) || (rc = d_match_off.ensure(8 * (size_t)(ns + 1))) ||
             (rc = d_items.ensure(4 * items.size())) || (rc = d_work.ensure(4 * work.size())) || (rc = d_match.ensure(4 * (size_t)std::max<int64_t>(round_counts, 1))) ||
             (rc = d_best.ensure(4 * (size_t)ns)) || (rc = d_dev.ensure(8 * (size_t)ns)) || (rc = d_v.ensure(8 * (size_t)ns)))
             return rc;
-        if (nbases > 0) HIPCHK(hipMemcpyAsync(d_bases.p, in->bases, (size_t)nbases, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d_seq_off.p, in->seq_off, 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
+        if (src) { if ((rc = letters_stage(h, gather_src, nullptr))) return rc; }
+        else if (nbases > 0) HIPCHK(hipMemcpyAsync(d_bases.p, in->bases, (size_t)nbases, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_seq_off.p, seq_off_up, 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(d_match_off.p, match_off.data(), 8 * (size_t)(ns + 1), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(d_items.p, items.data(), 4 * items.size(), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(d_work.p, work.data(), 4 * work.size(), hipMemcpyHostToDevice, h->stream));
@@ -3242,6 +3483,10 @@ extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat
         uint64_t launches = 0;
         float ms = 0;
         if (int rc = timer_start(h)) return rc;
+        if (src) {   // the scanned ranges out of the resident letters, as they stand, into the layout the counting kernel reads
+            if (int rc = letters_launch(h, ns, dev_bases, d_seq_off.as<int64_t>(), d_bases.as<uint8_t>(), 0)) return rc;
+            ++launches;
+        }
         for (const round_t& r : rounds) {
             RepeatArgs A;
             A.bases = d_bases.as<uint8_t>(); A.seq_off = d_seq_off.as<int64_t>(); A.match_off = d_match_off.as<int64_t>();
@@ -3264,6 +3509,7 @@ extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat
                 }
         }
         if (int rc = timer_stop(h, &ms)) return rc;
+        if (int rc = letters_account(h)) return rc;
         std::vector<int32_t> got_best((size_t)ns);
         std::vector<double> got_dev((size_t)ns), got_v((size_t)ns);
         HIPCHK(hipMemcpy(got_best.data(), d_best.p, 4 * (size_t)ns, hipMemcpyDeviceToHost));
@@ -3272,10 +3518,30 @@ extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat
         for (int32_t s : work) { best[s] = got_best[(size_t)s]; dev[s] = got_dev[(size_t)s]; v[s] = got_v[(size_t)s]; }
         h->stats.kernel_ms = ms; h->stats.dom_kernel_ms = ms; h->stats.dp_launches = launches; h->stats.n_slots = (int32_t)groups_max;
         h->stats.device_bytes = d_bases.cap + d_seq_off.cap + d_match_off.cap + d_items.cap + d_work.cap + d_match.cap + d_best.cap + d_dev.cap + d_v.cap;
+        if (src) h->stats.device_bytes += h->letters.d.cap + h->letters.d_src.cap;
         h->stats.dom_threads = SXG_REPEAT_WAVE;
     }
     if (any_failed) return fail(SXG_E_BLOCK, "a sequence is longer than SXG_POA_REPEAT_MAX_LEN");
     return SXG_OK;
+}
+extern "C" int sxg_poa_repeat_scan_batch(sxg_poa_handle* h, const sxg_poa_repeat_in* in, int32_t* n_lags, int32_t* best, double* dev, double* v,
+                                         int32_t* status, int32_t* match) {
+    return repeat_scan_run(h, in, nullptr, "sxg_poa_repeat_scan_batch", n_lags, best, dev, v, status, match);
+}
+extern "C" int sxg_poa_repeat_scan_ranges(sxg_poa_handle* h, const sxg_poa_repeat_ranges_in* in, int32_t* n_lags, int32_t* best, double* dev, double* v,
+                                          int32_t* status, int32_t* match) {
+    if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
+    const int64_t ns = in->n_seqs;
+    if (ns < 0 || ns > 0x7fffffff) return fail(SXG_E_INVALID, "repeat_scan: bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    h->stats = sxg_poa_stats{};
+    std::vector<int64_t> len, src, seq_off((size_t)ns + 1, 0);
+    if (int rc = letters_resolve(h, in->letters, in->letters_id, ns, in->ranges, "repeat_scan_ranges", len, src)) return rc;
+    for (int64_t s = 0; s < ns; ++s) seq_off[(size_t)s + 1] = seq_off[(size_t)s] + len[(size_t)s];
+    sxg_poa_repeat_in seqs;
+    memset(&seqs, 0, sizeof(seqs));
+    seqs.n_seqs = ns; seqs.seq_off = seq_off.data(); seqs.min_copy = in->min_copy; seqs.max_copy = in->max_copy; seqs.stride = in->stride;
+    return repeat_scan_run(h, &seqs, src.data(), "sxg_poa_repeat_scan_ranges", n_lags, best, dev, v, status, match);
 }
 
 // ---------------------------------------------------------------------------------------

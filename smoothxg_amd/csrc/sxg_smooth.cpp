@@ -77,6 +77,10 @@ struct sxg_graph {
         for (handle_t h : steps[p]) s += sequence(h);
         return s;
     }
+    // the path letters, concatenated once (sxg_graph_path_letters): path p's letters == path_sequence(p)
+    mutable std::vector<int64_t> letters_off;
+    mutable std::vector<uint8_t> letters;
+    mutable uint64_t letters_id = 0;   // 0: not built yet
 };
 
 struct path_range_t { uint64_t path, begin, end, length; };  // steps [begin,end), length in bp (src/blocks.hpp:29-33)
@@ -792,15 +796,44 @@ sxg_poa_params block_poa_params(const sxg_graph& g, const std::vector<path_range
 // anything else code 4, exactly as canonical_kmers reads them (the inline coder of the iteration's prepare() takes upper case
 // only and codes PADDED, dedup'd sequences: not this batch) --, and the (inter, uni) it returns per block become thresholds
 // through identity_from_counts.  A block the provider reports with a status other than SXG_ST_OK gets the host estimator.
-int identity_table(const sxg_graph& g, const sxg_blockset& b, int k, uint64_t max_depth, sxg_identity_fn ident, void* ctx, float* thr, int32_t* n_used) {
+// The graph's path letters, concatenated once and kept in the graph: what both range providers read (sxg_graph_path_letters).
+// Path p's letters are path_sequence(p), byte for byte; the id is unique per graph object in the process.
+int graph_path_letters(const sxg_graph& g, sxg_poa_letters* out) {
+    static std::mutex mu;
+    static uint64_t next_id = 1;
+    std::lock_guard<std::mutex> lock(mu);
+    if (g.letters_id == 0) {
+        const int64_t np = (int64_t)g.steps.size();
+        g.letters_off.assign((size_t)np + 1, 0);
+        for (int64_t p = 0; p < np; ++p) g.letters_off[(size_t)p + 1] = g.letters_off[(size_t)p] + (int64_t)g.pos[(size_t)p].back();
+        g.letters.resize((size_t)g.letters_off[(size_t)np]);
+#pragma omp parallel for schedule(dynamic, 1)
+        for (int64_t p = 0; p < np; ++p) {
+            uint8_t* dst = g.letters.data() + g.letters_off[(size_t)p];
+            for (handle_t h : g.steps[(size_t)p]) {
+                const std::string& q = g.seq[nid(h)];
+                if (rev(h)) { const std::string rc = revcomp(q); memcpy(dst, rc.data(), rc.size()); }
+                else memcpy(dst, q.data(), q.size());
+                dst += q.size();
+            }
+        }
+        g.letters_id = next_id++;
+    }
+    out->id = g.letters_id; out->n_paths = (int64_t)g.steps.size(); out->path_off = g.letters_off.data(); out->letters = g.letters.data();
+    return SXG_OK;
+}
+// ident_r (instead of ident): the same call with the sequences as RANGES of the graph's path letters -- range r of path p is
+// letters [pos[p][begin], pos[p][end]) of it --, which the provider codes itself; no sequence is built here.
+int identity_table(const sxg_graph& g, const sxg_blockset& b, int k, uint64_t max_depth, sxg_identity_fn ident, void* ctx, float* thr, int32_t* n_used,
+                   sxg_identity_ranges_fn ident_r = nullptr) {
     const int64_t nb = (int64_t)b.blocks.size();
     std::vector<int64_t> sent;
     for (int64_t q = 0; q < nb; ++q) {
         thr[q] = 0; n_used[q] = 0;
         if (b.blocks[(size_t)q].size() > 1 && b.blocks[(size_t)q].size() <= max_depth) sent.push_back(q);
     }
-    std::vector<char> on_host(sent.size(), ident ? 0 : 1);
-    if (ident && !sent.empty()) {
+    std::vector<char> on_host(sent.size(), ident || ident_r ? 0 : 1);
+    if ((ident || ident_r) && !sent.empty()) {
         if (sent.size() > 0x7fffffffull) return fail(SXG_E_INVALID, "too many blocks for one identity call");
         const int64_t n = (int64_t)sent.size();
         std::vector<int32_t> blk_off((size_t)n + 1, 0);
@@ -813,6 +846,24 @@ int identity_table(const sxg_graph& g, const sxg_blockset& b, int k, uint64_t ma
                 seq_off[(size_t)blk_off[(size_t)q] + r + 1] = (int64_t)(g.pos[ranges[r].path][ranges[r].end] - g.pos[ranges[r].path][ranges[r].begin]);
         }
         for (size_t s = 0; s < ns; ++s) seq_off[s + 1] += seq_off[s];
+        const int32_t min_len = 8 * k;   // :1995
+        std::vector<int32_t> used((size_t)n, 0), inter((size_t)n, 0), uni((size_t)n, 0), status((size_t)n, 0);
+        int rc;
+        if (ident_r) {
+            sxg_poa_letters letters;
+            if (int lrc = graph_path_letters(g, &letters)) return lrc;
+            std::vector<sxg_poa_range> rr(ns);
+            for (int64_t q = 0; q < n; ++q) {
+                const auto& ranges = b.blocks[(size_t)sent[(size_t)q]];
+                for (size_t r = 0; r < ranges.size(); ++r)
+                    rr[(size_t)blk_off[(size_t)q] + r] = sxg_poa_range{(int64_t)ranges[r].path, (int64_t)g.pos[ranges[r].path][ranges[r].begin], (int64_t)g.pos[ranges[r].path][ranges[r].end]};
+            }
+            sxg_poa_identity_ranges_in in;
+            memset(&in, 0, sizeof(in));
+            in.letters = &letters; in.letters_id = letters.id; in.n_blocks = (int32_t)n; in.blk_off = blk_off.data(); in.ranges = rr.data();
+            in.kmer_size = k; in.min_len = min_len; in.percentile = 0.30;   // :2026
+            rc = ident_r(ctx, &in, used.data(), inter.data(), uni.data(), status.data());
+        } else {
         uvec<uint8_t> bases;
         bases.resize((size_t)seq_off[ns]);
 #pragma omp parallel for schedule(dynamic, 1)
@@ -833,14 +884,14 @@ int identity_table(const sxg_graph& g, const sxg_blockset& b, int k, uint64_t ma
         sxg_poa_identity_in in;
         memset(&in, 0, sizeof(in));
         in.n_blocks = (int32_t)n; in.blk_off = blk_off.data(); in.seq_off = seq_off.data(); in.bases = bases.empty() ? &dummy : bases.data();
-        in.kmer_size = k; in.min_len = 8 * k; in.percentile = 0.30;   // :1995, :2026
-        std::vector<int32_t> used((size_t)n, 0), inter((size_t)n, 0), uni((size_t)n, 0), status((size_t)n, 0);
-        const int rc = ident(ctx, &in, used.data(), inter.data(), uni.data(), status.data());
+        in.kmer_size = k; in.min_len = min_len; in.percentile = 0.30;   // :2026
+        rc = ident(ctx, &in, used.data(), inter.data(), uni.data(), status.data());
+        }
         if (rc != SXG_OK && rc != SXG_E_BLOCK) return fail(rc, "identity provider failed");
         for (int64_t q = 0; q < n; ++q) {
             if (status[(size_t)q] != SXG_ST_OK) { on_host[(size_t)q] = 1; continue; }
             int32_t want = 0;
-            for (int32_t s = blk_off[(size_t)q]; s < blk_off[(size_t)q + 1]; ++s) want += seq_off[(size_t)s + 1] - seq_off[(size_t)s] >= in.min_len ? 1 : 0;
+            for (int32_t s = blk_off[(size_t)q]; s < blk_off[(size_t)q + 1]; ++s) want += seq_off[(size_t)s + 1] - seq_off[(size_t)s] >= min_len ? 1 : 0;
             if (used[(size_t)q] != want || inter[(size_t)q] < 0 || inter[(size_t)q] > uni[(size_t)q] || uni[(size_t)q] > 0xffff)
                 return fail(SXG_E_INVALID, "identity provider returned counts out of range for block " + std::to_string(sent[(size_t)q]));
             n_used[sent[(size_t)q]] = want;
@@ -2305,7 +2356,7 @@ static void reap(std::function<void()> fn) { g_reaper.run(std::move(fn)); }
 
 static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp,
                             sxg_poa_run_fn run, sxg_poa_free_fn fre, void* ctx, sxg_identity_fn ident, void* ident_ctx, char** out_gfa,
-                            char** out_maf, int64_t* n_flipped, const bool device_rows = false) {
+                            char** out_maf, int64_t* n_flipped, const bool device_rows = false, sxg_identity_ranges_fn ident_r = nullptr) {
     if (!g || !b || !p || !run || !out_gfa) return fail(SXG_E_INVALID, "NULL argument");
     if (int prc = check_params(p)) return prc;
     if (out_maf) *out_maf = nullptr;
@@ -2367,10 +2418,10 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
     // flight together.  prepare() then reads the tiers from this table.
     std::vector<float> ident_thr;
     std::vector<int32_t> ident_used;
-    if (p->adaptive_poa_params && ident && nb > 0) {
+    if (p->adaptive_poa_params && (ident || ident_r) && nb > 0) {
         ident_thr.assign((size_t)nb, 0); ident_used.assign((size_t)nb, 0);
         if (int irc = identity_table(*g, *b, p->kmer_size > 0 ? p->kmer_size : 17, p->max_block_depth_for_padding_more, ident, ident_ctx,
-                                     ident_thr.data(), ident_used.data())) return irc;
+                                     ident_thr.data(), ident_used.data(), ident_r)) return irc;
         lap("identity estimate");
     }
     // stage 1: A2-A4 for every block of the chunk, in parallel over blocks as the reference's OpenMP loop
@@ -2947,7 +2998,7 @@ static bool block_is_cut(const std::vector<path_range_t>& blk, uint64_t max_poa_
 // at least 2 min_copy bases in ONE call on this thread, a sequence the provider declines scanned here.  found[k]: the repeat
 // lengths block k's ranges hold, in range order (what the loop of blockset_break would have pushed).
 static int scan_repeats(const sxg_graph* g, const sxg_blockset* in, uint64_t max_poa_length, uint64_t min_copy, uint64_t max_copy, double min_z, uint64_t stride,
-                        sxg_repeat_fn scan, void* ctx, std::vector<std::vector<double>>& found, int64_t* n_host) {
+                        sxg_repeat_fn scan, void* ctx, std::vector<std::vector<double>>& found, int64_t* n_host, sxg_repeat_ranges_fn scan_r = nullptr) {
     struct cand_t { int64_t blk; size_t range; };
     std::vector<cand_t> cand;
     std::vector<int64_t> seq_off{0};
@@ -2961,12 +3012,31 @@ static int scan_repeats(const sxg_graph* g, const sxg_blockset* in, uint64_t max
     }
     const int64_t ns = (int64_t)cand.size();
     if (ns == 0) return SXG_OK;
+    std::vector<int32_t> n_lags((size_t)ns, 0), best((size_t)ns, 0), status((size_t)ns, 0);
+    std::vector<double> dev((size_t)ns, 0.0), v((size_t)ns, 0.0), rl((size_t)ns, 0.0);
     uvec<uint8_t> bases;
+    std::vector<const uint8_t*> seq_at((size_t)ns, nullptr);   // where sequence s stands: in `bases`, or in the graph's path letters
+    int rc;
+    if (scan_r) {   // the candidates as ranges of the graph's path letters: no sequence is built here
+        sxg_poa_letters letters;
+        if (int lrc = graph_path_letters(*g, &letters)) return lrc;
+        std::vector<sxg_poa_range> rr((size_t)ns);
+        for (int64_t s = 0; s < ns; ++s) {
+            const path_range_t& r = in->blocks[(size_t)cand[(size_t)s].blk][cand[(size_t)s].range];
+            rr[(size_t)s] = sxg_poa_range{(int64_t)r.path, (int64_t)g->pos[r.path][r.begin], (int64_t)g->pos[r.path][r.end]};
+            seq_at[(size_t)s] = letters.letters + letters.path_off[r.path] + rr[(size_t)s].begin;
+        }
+        sxg_poa_repeat_ranges_in ri;
+        memset(&ri, 0, sizeof(ri));
+        ri.letters = &letters; ri.letters_id = letters.id; ri.n_seqs = ns; ri.ranges = rr.data(); ri.min_copy = min_copy; ri.max_copy = max_copy; ri.stride = stride;
+        rc = scan_r(ctx, &ri, n_lags.data(), best.data(), dev.data(), v.data(), status.data(), nullptr);
+    } else {
     bases.resize((size_t)seq_off.back());
 #pragma omp parallel for schedule(dynamic, 16)
     for (int64_t s = 0; s < ns; ++s) {
         const path_range_t& r = in->blocks[(size_t)cand[(size_t)s].blk][cand[(size_t)s].range];
         uint8_t* dst = bases.data() + seq_off[(size_t)s];
+        seq_at[(size_t)s] = dst;
         for (uint64_t st = r.begin; st != r.end; ++st) {   // R1: the letters as they stand, in step orientation
             const std::string q = g->sequence(g->steps[r.path][st]);
             memcpy(dst, q.data(), q.size());
@@ -2976,9 +3046,8 @@ static int scan_repeats(const sxg_graph* g, const sxg_blockset* in, uint64_t max
     sxg_poa_repeat_in ri;
     memset(&ri, 0, sizeof(ri));
     ri.n_seqs = ns; ri.seq_off = seq_off.data(); ri.bases = bases.data(); ri.min_copy = min_copy; ri.max_copy = max_copy; ri.stride = stride;
-    std::vector<int32_t> n_lags((size_t)ns, 0), best((size_t)ns, 0), status((size_t)ns, 0);
-    std::vector<double> dev((size_t)ns, 0.0), v((size_t)ns, 0.0), rl((size_t)ns, 0.0);
-    const int rc = scan(ctx, &ri, n_lags.data(), best.data(), dev.data(), v.data(), status.data(), nullptr);
+    rc = scan(ctx, &ri, n_lags.data(), best.data(), dev.data(), v.data(), status.data(), nullptr);
+    }
     if (rc != SXG_OK && rc != SXG_E_BLOCK) return fail(rc, "repeat scan provider failed");
     std::vector<char> on_host((size_t)ns, 0);
     for (int64_t s = 0; s < ns; ++s) {
@@ -2991,7 +3060,7 @@ static int scan_repeats(const sxg_graph* g, const sxg_blockset* in, uint64_t max
 #pragma omp parallel for schedule(dynamic, 1)
     for (int64_t s = 0; s < ns; ++s)
         if (on_host[(size_t)s])
-            rl[(size_t)s] = repeat_length(std::string((const char*)bases.data() + seq_off[(size_t)s], (size_t)(seq_off[(size_t)s + 1] - seq_off[(size_t)s])), min_copy, max_copy, min_z, stride);
+            rl[(size_t)s] = repeat_length(std::string((const char*)seq_at[(size_t)s], (size_t)(seq_off[(size_t)s + 1] - seq_off[(size_t)s])), min_copy, max_copy, min_z, stride);
     for (int64_t s = 0; s < ns; ++s)
         if (rl[(size_t)s] > 0) found[(size_t)cand[(size_t)s].blk].push_back(rl[(size_t)s]);
     return SXG_OK;
@@ -3001,16 +3070,17 @@ static int scan_repeats(const sxg_graph* g, const sxg_blockset* in, uint64_t max
 // declined; any of them may be NULL.
 static int blockset_break(const sxg_graph* g, const sxg_blockset* in, uint64_t max_poa_length, bool break_repeats, uint64_t min_copy_length,
                           uint64_t max_copy_length, double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest, sxg_blockset** out,
-                          sxg_repeat_fn scan = nullptr, void* scan_ctx = nullptr, int64_t* n_cut = nullptr, int64_t* n_repeat = nullptr, int64_t* n_host = nullptr) {
+                          sxg_repeat_fn scan = nullptr, void* scan_ctx = nullptr, int64_t* n_cut = nullptr, int64_t* n_repeat = nullptr, int64_t* n_host = nullptr,
+                          sxg_repeat_ranges_fn scan_r = nullptr) {
     if (!g || !in || !out) return fail(SXG_E_INVALID, "NULL argument");
     if (break_repeats && (min_copy_length == 0 || autocorr_stride == 0 || max_copy_length < min_copy_length)) return fail(SXG_E_INVALID, "bad repeat parameters");
     const int64_t nb = (int64_t)in->blocks.size();
     std::vector<std::vector<double>> found;
     int64_t declined = 0, cut = 0, with_repeat = 0;
-    if (break_repeats && scan) {
+    if (break_repeats && (scan || scan_r)) {
         if (min_copy_length > (1ull << 62)) return fail(SXG_E_INVALID, "bad repeat parameters");
         found.resize((size_t)nb);
-        if (int rc = scan_repeats(g, in, max_poa_length, min_copy_length, max_copy_length, min_autocorr_z, autocorr_stride, scan, scan_ctx, found, &declined)) return rc;
+        if (int rc = scan_repeats(g, in, max_poa_length, min_copy_length, max_copy_length, min_autocorr_z, autocorr_stride, scan, scan_ctx, found, &declined, scan_r)) return rc;
     }
     sxg_blockset* bs = new sxg_blockset();
     bs->blocks.resize((size_t)nb);
@@ -3023,7 +3093,7 @@ static int blockset_break(const sxg_graph* g, const sxg_blockset* in, uint64_t m
         bool found_repeat = false;
         if (break_repeats) {
             std::vector<double> lengths;
-            if (scan) lengths = found[(size_t)k];
+            if (scan || scan_r) lengths = found[(size_t)k];
             else for (auto& r : blk) {
                 std::string seq;
                 for (uint64_t st = r.begin; st != r.end; ++st) seq += g->sequence(g->steps[r.path][st]);
@@ -3256,6 +3326,35 @@ int sxg_blockset_break_scan(const sxg_graph* g, const sxg_blockset* in, uint64_t
                             sxg_blockset** out, int64_t* n_cut, int64_t* n_repeat, int64_t* n_host) {
     return guarded([&] { return blockset_break(g, in, max_poa_length, true, min_copy_length, max_copy_length, min_autocorr_z, autocorr_stride, order_paths_from_longest, out,
                                                scan, ctx, n_cut, n_repeat, n_host); });
+}
+
+// ... and with the scan provider fed ranges of the graph's path letters (sxg_poa_repeat_scan_ranges' contract)
+int sxg_blockset_break_scan_ranges(const sxg_graph* g, const sxg_blockset* in, uint64_t max_poa_length, uint64_t min_copy_length, uint64_t max_copy_length,
+                                   double min_autocorr_z, uint64_t autocorr_stride, int order_paths_from_longest, sxg_repeat_ranges_fn scan, void* ctx,
+                                   sxg_blockset** out, int64_t* n_cut, int64_t* n_repeat, int64_t* n_host) {
+    return guarded([&] { return blockset_break(g, in, max_poa_length, true, min_copy_length, max_copy_length, min_autocorr_z, autocorr_stride, order_paths_from_longest, out,
+                                               nullptr, ctx, n_cut, n_repeat, n_host, scan); });
+}
+int sxg_graph_path_letters(const sxg_graph* g, sxg_poa_letters* out) {
+    if (!g || !out) return fail(SXG_E_INVALID, "NULL argument");
+    const OmpTeamGuard team(host_threads());
+    return guarded([&] { return graph_path_letters(*g, out); });
+}
+int sxg_blockset_identity_thresholds_ranges(const sxg_graph* g, const sxg_blockset* b, int32_t kmer_size, uint64_t max_depth, sxg_identity_ranges_fn ident,
+                                            void* ctx, float* thr, int32_t* n_used) {
+    if (!g || !b || kmer_size < 1 || kmer_size > 32 || (!b->blocks.empty() && (!thr || !n_used))) return fail(SXG_E_INVALID, "bad argument");
+    const OmpTeamGuard team(host_threads());
+    return guarded([&] { return identity_table(*g, *b, kmer_size, max_depth, nullptr, ctx, thr, n_used, ident); });
+}
+// one iteration entry point for the range providers: mp == NULL is sxg_smooth_gfa_adaptive, otherwise sxg_smooth_maf_gfa_adaptive
+// or (device_rows) sxg_smooth_maf_gfa_device_rows, each with the identity estimate fed ranges
+int sxg_smooth_iteration_ranges(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
+                                sxg_poa_free_fn fre, void* ctx, const sxg_range_providers* rp, int device_rows, char** out_gfa, char** out_maf,
+                                int64_t* n_flipped) {
+    if (mp && !out_maf) return fail(SXG_E_INVALID, "NULL argument");
+    if (!mp && (out_maf || device_rows)) return fail(SXG_E_INVALID, "MAF output needs merge parameters");
+    return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, nullptr, rp ? rp->ctx : nullptr, out_gfa, out_maf, n_flipped, device_rows != 0,
+                                                 rp ? rp->identity : nullptr); });
 }
 
 int sxg_blockset_split(const sxg_graph* g, const sxg_blockset* in, double block_group_identity, double length_ratio_min, uint64_t min_dedup_depth,

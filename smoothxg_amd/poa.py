@@ -119,6 +119,28 @@ class RepeatIn(C.Structure):
                 ("stride", C.c_uint64)]
 
 
+class LettersIn(C.Structure):
+    """sxg_poa_letters: a graph's path letters on the host (the bytes as they stand, step orientation) and the id that names them."""
+    _fields_ = [("id", C.c_uint64), ("n_paths", C.c_int64), ("path_off", _i64p), ("letters", _u8p)]
+
+
+class Range(C.Structure):
+    """sxg_poa_range: letters [begin, end) of `path`."""
+    _fields_ = [("path", C.c_int64), ("begin", C.c_int64), ("end", C.c_int64)]
+
+
+class RepeatRangesIn(C.Structure):
+    """sxg_poa_repeat_ranges_in: the repeat scan's sequences as ranges of the resident letters."""
+    _fields_ = [("letters", C.POINTER(LettersIn)), ("letters_id", C.c_uint64), ("n_seqs", C.c_int64), ("ranges", C.POINTER(Range)),
+                ("min_copy", C.c_uint64), ("max_copy", C.c_uint64), ("stride", C.c_uint64)]
+
+
+class IdentityRangesIn(C.Structure):
+    """sxg_poa_identity_ranges_in: the identity estimate's blocks as ranges of the resident letters."""
+    _fields_ = [("letters", C.POINTER(LettersIn)), ("letters_id", C.c_uint64), ("n_blocks", C.c_int32), ("blk_off", _i32p),
+                ("ranges", C.POINTER(Range)), ("kmer_size", C.c_int32), ("min_len", C.c_int32), ("percentile", C.c_double)]
+
+
 class SgdIn(C.Structure):
     """sxg_poa_sgd_in: the flattened graph, the schedule and the seed of the path-guided SGD node order (decree Y)."""
     _fields_ = [("n_nodes", C.c_int64), ("node_len", _i32p), ("n_paths", C.c_int64), ("path_off", _i64p), ("step_node", _i32p),
@@ -135,7 +157,8 @@ MAX_SEQ_LEN_TILED = 49151  # SXG_POA_MAX_SEQ_LEN_TILED: every mode and score set
 ST_TOO_LONG = 5
 MSA_FULL, MSA_TRIMMED = 1, 2   # SXG_MSA_FULL / SXG_MSA_TRIMMED: values of want_msa (True = the full MSA)
 
-EXPORTS = ["sxg_poa_repeat_scan_batch", "sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_compute_units", "sxg_poa_last_error", "sxg_poa_create",
+EXPORTS = ["sxg_poa_letters_upload", "sxg_poa_letters_drop", "sxg_poa_letters_resident", "sxg_poa_letters_stats", "sxg_poa_letters_geometry", "sxg_poa_range_gather",
+           "sxg_poa_repeat_scan_ranges", "sxg_poa_block_identity_ranges", "sxg_poa_repeat_scan_batch", "sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_compute_units", "sxg_poa_last_error", "sxg_poa_create",
            "sxg_poa_destroy", "sxg_poa_batch_run", "sxg_poa_batch_upload", "sxg_poa_batch_execute",
            "sxg_poa_batch_download", "sxg_poa_batch_free", "sxg_poa_align_batch", "sxg_poa_align_free",
            "sxg_poa_get_stats", "sxg_poa_get_width_stats", "sxg_poa_get_twin_stats", "sxg_poa_set_memory_budget", "sxg_xxh64", "sxg_poa_comm_unique_id", "sxg_poa_comm_init",
@@ -219,6 +242,16 @@ def load_library(build_if_missing=True):
     L.sxg_poa_block_identity_batch.argtypes = [vp, C.POINTER(IdentityIn), _i32p, _i32p, _i32p, _i32p]
     L.sxg_poa_path_sgd_order.argtypes = [vp, C.POINTER(SgdIn), _i32p, _i64p]
     L.sxg_poa_repeat_scan_batch.argtypes = [vp, C.POINTER(RepeatIn), _i32p, _i32p, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i32p]
+    L.sxg_poa_letters_upload.argtypes = [vp, C.POINTER(LettersIn)]
+    L.sxg_poa_letters_drop.argtypes = [vp]
+    L.sxg_poa_letters_drop.restype = None
+    L.sxg_poa_letters_resident.argtypes = [vp, C.POINTER(C.c_uint64), _i64p, _i64p]
+    L.sxg_poa_letters_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.sxg_poa_letters_geometry.argtypes = [C.POINTER(C.c_int32)]
+    L.sxg_poa_letters_geometry.restype = None
+    L.sxg_poa_range_gather.argtypes = [vp, C.POINTER(LettersIn), C.c_uint64, C.c_int64, C.POINTER(Range), C.c_int, _u8p]
+    L.sxg_poa_repeat_scan_ranges.argtypes = [vp, C.POINTER(RepeatRangesIn), _i32p, _i32p, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i32p]
+    L.sxg_poa_block_identity_ranges.argtypes = [vp, C.POINTER(IdentityRangesIn), _i32p, _i32p, _i32p, _i32p]
     L.sxg_xxh64.restype = C.c_uint64
     L.sxg_xxh64.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64]
     _lib = L
@@ -237,6 +270,49 @@ def _arr(ptr, n, dtype):
     if n == 0 or not ptr:
         return np.zeros(0, dtype)
     return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dtype, copy=True)
+
+
+class PathLetters:
+    """A graph's path letters on the host, as the engine takes them (sxg_poa_letters): `letters`, the paths' spelled sequences
+    back to back, `path_off` [n_paths + 1], and the non-zero `id` that names them on a handle.  Built from a list of byte strings
+    or uint8 arrays, or from (path_off, letters) arrays that are used as they are; id: None = a fresh one in this process."""
+    _next_id = [1]
+
+    def __init__(self, paths=None, path_off=None, letters=None, id=None):
+        if paths is not None:
+            arrs = [np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, np.uint8) for x in paths]
+            path_off = np.zeros(len(arrs) + 1, np.int64)
+            if arrs:
+                path_off[1:] = np.cumsum([len(a) for a in arrs])
+            letters = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
+        self.path_off = np.ascontiguousarray(path_off, np.int64)
+        self.letters = np.ascontiguousarray(letters, np.uint8)
+        if id is None:
+            id = PathLetters._next_id[0]
+            PathLetters._next_id[0] += 1
+        self.id = int(id)
+        self._hold = self.letters if len(self.letters) else np.zeros(1, np.uint8)
+        self.c = LettersIn(self.id, len(self.path_off) - 1, _p(self.path_off, C.c_int64), _p(self._hold, C.c_uint8))
+
+    @property
+    def n_paths(self):
+        return len(self.path_off) - 1
+
+    def slice(self, path, begin, end):
+        o = int(self.path_off[path])
+        return self.letters[o + begin:o + end]
+
+
+def _ranges(ranges):
+    """(n, 3) int64 (path, begin, end) -> the array and its sxg_poa_range pointer"""
+    r = np.ascontiguousarray(np.asarray(ranges, np.int64).reshape(-1, 3))
+    hold = r if len(r) else np.zeros((1, 3), np.int64)
+    return r, hold, C.cast(hold.ctypes.data, C.POINTER(Range))
+
+
+LETTERS_CODE = np.full(256, 4, np.uint8)   # the code of the identity estimate: either case of A C G T -> 0..3, anything else -> 4
+for _i, _ch in enumerate("ACGT"):
+    LETTERS_CODE[ord(_ch)] = LETTERS_CODE[ord(_ch.lower())] = _i
 
 
 class BlockResult:
@@ -712,6 +788,92 @@ class PoaEngine:
             raise self._err("sxg_poa_repeat_scan_batch")
         res = (lags[:ns], best[:ns], dev[:ns], v[:ns], st[:ns])
         return res + ([match[off[s]:off[s + 1]] for s in range(ns)],) if want_match else res
+
+    # -- resident path letters: the two calls above on ranges of them ---------------------------
+    def upload_letters(self, letters):
+        """sxg_poa_letters_upload: `letters` (a PathLetters) replace what is resident on this handle."""
+        if self.lib.sxg_poa_letters_upload(self.h, C.byref(letters.c)):
+            raise self._err("sxg_poa_letters_upload")
+
+    def drop_letters(self):
+        self.lib.sxg_poa_letters_drop(self.h)
+
+    def letters_resident(self):
+        """(id, n_paths, n_letters) of the resident letters; id 0 = none."""
+        i, p, n = C.c_uint64(), C.c_int64(), C.c_int64()
+        if self.lib.sxg_poa_letters_resident(self.h, C.byref(i), C.byref(p), C.byref(n)):
+            raise self._err("sxg_poa_letters_resident")
+        return int(i.value), int(p.value), int(n.value)
+
+    def letters_stats(self):
+        """Since the handle was created: uploads, their bytes, the gather kernels' time and the bytes they wrote."""
+        u, b, g = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        ms = C.c_double()
+        if self.lib.sxg_poa_letters_stats(self.h, C.byref(u), C.byref(b), C.byref(ms), C.byref(g)):
+            raise self._err("sxg_poa_letters_stats")
+        return {"uploads": int(u.value), "bytes_uploaded": int(b.value), "gather_ms": float(ms.value), "gathered_bytes": int(g.value)}
+
+    def letters_geometry(self):
+        c = C.c_int32()
+        self.lib.sxg_poa_letters_geometry(C.byref(c))
+        return int(c.value)
+
+    @staticmethod
+    def _letters_arg(letters, letters_id):
+        """letters: a PathLetters (passed to the call, which uploads them if they are not resident) or None with letters_id"""
+        if letters is None:
+            return None, int(letters_id)
+        return C.pointer(letters.c), int(letters.id if letters_id is None else letters_id)
+
+    def gather_ranges(self, letters, ranges, coded=False, letters_id=None):
+        """sxg_poa_range_gather: what the gather kernel writes for `ranges` ((n, 3) int64: path, begin, end), one uint8 array."""
+        r, hold, rp = _ranges(ranges)
+        lp, lid = self._letters_arg(letters, letters_id)
+        total = int((r[:, 2] - r[:, 1]).sum()) if len(r) else 0
+        out = np.zeros(max(total, 1), np.uint8)
+        if self.lib.sxg_poa_range_gather(self.h, lp, lid, len(r), rp, 1 if coded else 0, _p(out, C.c_uint8)):
+            raise self._err("sxg_poa_range_gather")
+        return out[:total]
+
+    def repeat_scan_ranges(self, letters, ranges, min_copy=1000, max_copy=20000, stride=50, want_match=False, check=True, letters_id=None):
+        """sxg_poa_repeat_scan_ranges: repeat_scan on the sequences `ranges` spell in `letters`; the same results."""
+        r, hold, rp = _ranges(ranges)
+        ns = len(r)
+        lp, lid = self._letters_arg(letters, letters_id)
+        ri = RepeatRangesIn(lp, lid, ns, rp, int(min_copy), int(max_copy), int(stride))
+        lags, best, st = (np.zeros(max(ns, 1), np.int32) for _ in range(3))
+        dev, v = (np.zeros(max(ns, 1), np.float64) for _ in range(2))
+        match = None
+        if want_match:
+            n = (r[:, 2] - r[:, 1]) if ns else np.zeros(0, np.int64)
+            want = np.where((n >= 2 * int(min_copy)) & (n <= REPEAT_MAX_LEN) & (int(min_copy) > 0) & (int(max_copy) >= int(min_copy)),
+                            np.minimum(int(max_copy), n - int(min_copy)) - int(min_copy) + 1, 0)
+            off = np.concatenate([[0], np.cumsum(want)]).astype(np.int64)
+            match = np.zeros(max(int(off[-1]), 1), np.int32)
+        rc = self.lib.sxg_poa_repeat_scan_ranges(self.h, C.byref(ri), _p(lags, C.c_int32), _p(best, C.c_int32), _p(dev, C.c_double), _p(v, C.c_double),
+                                                 _p(st, C.c_int32), _p(match, C.c_int32) if want_match else None)
+        if rc and (check or rc != -4):
+            raise self._err("sxg_poa_repeat_scan_ranges")
+        res = (lags[:ns], best[:ns], dev[:ns], v[:ns], st[:ns])
+        return res + ([match[off[s]:off[s + 1]] for s in range(ns)],) if want_match else res
+
+    def block_identity_ranges(self, letters, blocks, kmer_size=17, min_len=None, percentile=0.30, check=True, letters_id=None):
+        """sxg_poa_block_identity_ranges: block_identity on the sequences the blocks' ranges spell in `letters`, coded on the device.
+        blocks: list of lists of (path, begin, end)."""
+        nb = len(blocks)
+        r, hold, rp = _ranges([x for blk in blocks for x in blk])
+        blk_off = np.zeros(nb + 1, np.int32)
+        if nb:
+            blk_off[1:] = np.cumsum([len(b) for b in blocks])
+        lp, lid = self._letters_arg(letters, letters_id)
+        ii = IdentityRangesIn(lp, lid, nb, _p(blk_off, C.c_int32), rp, int(kmer_size), 8 * int(kmer_size) if min_len is None else int(min_len),
+                              float(percentile))
+        used, inter, uni, st = (np.zeros(max(nb, 1), np.int32) for _ in range(4))
+        rc = self.lib.sxg_poa_block_identity_ranges(self.h, C.byref(ii), _p(used, C.c_int32), _p(inter, C.c_int32), _p(uni, C.c_int32),
+                                                    _p(st, C.c_int32))
+        if rc and (check or rc != -4):
+            raise self._err("sxg_poa_block_identity_ranges")
+        return used[:nb], inter[:nb], uni[:nb], st[:nb]
 
     # -- the node order of prep (src/prep.cpp:11-163) ----------------------------------------
     def path_sgd_order(self, node_len, path_off, step_node, step_pos, eta, cooling_start, terms_per_iter, seed, mode=0, want_x=True):

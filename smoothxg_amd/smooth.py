@@ -20,6 +20,10 @@ IDENT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.IdentityIn), C.POINTE
                        C.POINTER(C.c_int32))
 REPEAT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.RepeatIn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                         C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+IDENT_RANGES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.IdentityRangesIn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_int32))
+REPEAT_RANGES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.RepeatRangesIn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
 SGD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SgdIn), C.POINTER(C.c_int32), C.POINTER(C.c_int64))
 
 
@@ -39,7 +43,8 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
            "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_break_scan", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa",
            "sxg_prep_default_params", "sxg_graph_prep", "sxg_blockset_identity_thresholds", "sxg_smooth_gfa_adaptive",
-           "sxg_smooth_maf_gfa_adaptive", "sxg_smooth_maf_gfa_device_rows"]
+           "sxg_smooth_maf_gfa_adaptive", "sxg_smooth_maf_gfa_device_rows", "sxg_graph_path_letters", "sxg_blockset_break_scan_ranges",
+           "sxg_blockset_identity_thresholds_ranges", "sxg_smooth_iteration_ranges"]
 
 
 class PrepParams(C.Structure):
@@ -52,6 +57,16 @@ class MergeParams(C.Structure):
     """sxg_merge_params: -M / -J / -N of smoothxg (src/main.cpp:282,297-298)."""
     _fields_ = [("merge_blocks", C.c_int32), ("contiguous_path_jaccard", C.c_double), ("preserve_unmerged_consensus", C.c_int32),
                 ("max_merged_groups_in_memory", C.c_uint64), ("maf_header", C.c_char_p)]
+
+
+class RangeProviders(C.Structure):
+    """sxg_range_providers: the scan provider, the identity provider and their context."""
+    _fields_ = [("scan", C.c_void_p), ("identity", C.c_void_p), ("ctx", C.c_void_p)]
+
+
+class RangeProvider(tuple):
+    """A provider that takes RANGES of the graph's path letters (gpu_range_scanner, gpu_range_identifier and their python_ forms):
+    a (function, ctx[, keep-alive]) tuple like every provider; the type tells Smoother which form of the call to make."""
 
 
 class PathRange(C.Structure):
@@ -104,6 +119,11 @@ def load_library():
                                               C.POINTER(vp), C.POINTER(C.c_int64)]
     L.sxg_smooth_maf_gfa_device_rows.argtypes = L.sxg_smooth_maf_gfa_adaptive.argtypes
     L.sxg_blockset_identity_thresholds.argtypes = [vp, vp, C.c_int32, C.c_uint64, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    L.sxg_graph_path_letters.argtypes = [vp, C.POINTER(_poa.LettersIn)]
+    L.sxg_blockset_break_scan_ranges.argtypes = L.sxg_blockset_break_scan.argtypes
+    L.sxg_blockset_identity_thresholds_ranges.argtypes = L.sxg_blockset_identity_thresholds.argtypes
+    L.sxg_smooth_iteration_ranges.argtypes = [vp, vp, C.POINTER(SmoothParams), C.POINTER(MergeParams), vp, vp, vp, C.POINTER(RangeProviders), C.c_int,
+                                              C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
     L.sxg_block_maf_rows.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
     L.sxg_block_maf.argtypes = [vp, vp, C.c_int64, C.POINTER(SmoothParams), vp, vp, vp, C.POINTER(vp)]
     L.sxg_prep_default_params.restype = None
@@ -238,6 +258,82 @@ def python_repeat_scanner(fn):
     return C.cast(cb, C.c_void_p), None, cb
 
 
+def gpu_range_scanner(engine):
+    """gpu_repeat_scanner on RANGES: sxg_poa_repeat_scan_ranges and the engine handle.  The host library sends the candidates as
+    ranges of the graph's path letters, which go to the device once per graph -- with this call or with gpu_range_identifier's,
+    whichever comes first on the handle -- and a kernel cuts the sequences out there.  The same blocks, the same counts."""
+    return RangeProvider((C.cast(engine.lib.sxg_poa_repeat_scan_ranges, C.c_void_p), engine.h))
+
+
+def gpu_range_identifier(engine):
+    """gpu_identifier on RANGES: sxg_poa_block_identity_ranges and the engine handle (see gpu_range_scanner); the letters are coded
+    on the device.  The same thresholds, the same GFA."""
+    return RangeProvider((C.cast(engine.lib.sxg_poa_block_identity_ranges, C.c_void_p), engine.h))
+
+
+def _ranges_view(a, n):
+    """(letters bytes per range) of a ranges call, read through the letters pointer the library passed"""
+    import numpy as np
+    L = a.letters.contents
+    path_off = np.ctypeslib.as_array(L.path_off, shape=(L.n_paths + 1,))
+    total = int(path_off[-1])
+    letters = np.ctypeslib.as_array(L.letters, shape=(total,)) if total else np.zeros(0, np.uint8)
+    out = []
+    for s in range(n):
+        r = a.ranges[s]
+        if not (0 <= r.path < L.n_paths and 0 <= r.begin <= r.end <= path_off[r.path + 1] - path_off[r.path]) or a.letters_id != L.id or L.id == 0:
+            raise ValueError("range outside its path")
+        out.append(letters[path_off[r.path] + r.begin:path_off[r.path] + r.end].copy())
+    return out
+
+
+def python_range_scanner(fn):
+    """python_repeat_scanner on RANGES: the same fn(seq_off, bases, min_copy, max_copy, stride), fed the sequences the ranges spell
+    in the letters the library passed.  For CPU tests; the production provider is gpu_range_scanner."""
+    import numpy as np
+
+    def call(ctx, inp, n_lags, best, dev, v, status, match):
+        try:
+            a = inp.contents
+            seqs = _ranges_view(a, a.n_seqs)
+            seq_off = np.concatenate([[0], np.cumsum([len(x) for x in seqs])]).astype(np.int64)
+            res = fn(seq_off, np.concatenate(seqs) if seqs else np.zeros(0, np.uint8), a.min_copy, a.max_copy, a.stride)
+            for dst, src, conv in zip((n_lags, best, dev, v, status), res[:5], (int, int, float, float, int)):
+                if len(src) != a.n_seqs:
+                    return -1
+                for k in range(a.n_seqs):
+                    dst[k] = conv(src[k])
+            return int(res[5]) if len(res) > 5 else 0
+        except Exception:   # (an exception must not cross the C frames)
+            return -1
+    cb = REPEAT_RANGES_FN(call)
+    return RangeProvider((C.cast(cb, C.c_void_p), None, cb))
+
+
+def python_range_identifier(fn):
+    """python_identifier on RANGES: the same fn(blk_off, seq_off, bases, kmer_size, min_len, percentile), fed the sequences the
+    ranges spell, coded by the table of the identity estimate.  For CPU tests; the production provider is gpu_range_identifier."""
+    import numpy as np
+
+    def call(ctx, inp, n_used, inter, uni, status):
+        try:
+            a = inp.contents
+            blk_off = np.ctypeslib.as_array(a.blk_off, shape=(a.n_blocks + 1,)).astype(np.int32) if a.n_blocks else np.zeros(1, np.int32)
+            seqs = [_poa.LETTERS_CODE[x] for x in _ranges_view(a, int(blk_off[-1]))]
+            seq_off = np.concatenate([[0], np.cumsum([len(x) for x in seqs])]).astype(np.int64)
+            res = fn(blk_off, seq_off, np.concatenate(seqs) if seqs else np.zeros(0, np.uint8), a.kmer_size, a.min_len, a.percentile)
+            for dst, src in zip((n_used, inter, uni, status), res[:4]):
+                if len(src) != a.n_blocks:
+                    return -1
+                for k in range(a.n_blocks):
+                    dst[k] = int(src[k])
+            return int(res[4]) if len(res) > 4 else 0
+        except Exception:   # (an exception must not cross the C frames)
+            return -1
+    cb = IDENT_RANGES_FN(call)
+    return RangeProvider((C.cast(cb, C.c_void_p), None, cb))
+
+
 def python_sorter(fn):
     """(sort, ctx) around a Python function fn(node_len, path_off, step_node, step_pos, eta, cooling_start, terms_per_iter,
     seed) -> order (or (order, x)), the arrays being numpy copies of what the library flattened: for tests and experiments,
@@ -301,7 +397,8 @@ class Smoother:
         max_path_jump, max_edge_jump, max_poa_length, repeats, scanner): smoothable_blocks then the cutting half of break_blocks
         (repeat-aware cut lengths with the reference's defaults unless repeats=None).  scanner: a scan provider
         (gpu_repeat_scanner(engine): the tandem-repeat scan of all cut blocks in ONE call on the device, sxg_blockset_break_scan;
-        the counts it reports are kept in self.break_counts); without the key the host scans, as it always did.
+        the counts it reports are kept in self.break_counts; gpu_range_scanner(engine): the same through sxg_blockset_break_scan_ranges,
+        the candidates sent as ranges of the graph's path letters); without the key the host scans, as it always did.
         blocks: the caller's own blockset -- a list of blocks, each a list of (path, step_begin, step_end)
         or (path, step_begin, step_end, length) in alignment order (sxg_blockset_from_ranges); otherwise the
         demo partition into path windows of target_bp."""
@@ -325,8 +422,9 @@ class Smoother:
                 elif "scanner" in discover:
                     scan = discover["scanner"]
                     counts = [C.c_int64(), C.c_int64(), C.c_int64()]
-                    rc = self.L.sxg_blockset_break_scan(g, raw, int(discover.get("max_poa_length", 2 * tl)), int(rep[0]), int(rep[1]), float(rep[2]),
-                                                        int(rep[3]), 1, scan[0], scan[1], C.byref(b), *(C.byref(c) for c in counts))
+                    call = self.L.sxg_blockset_break_scan_ranges if isinstance(scan, RangeProvider) else self.L.sxg_blockset_break_scan
+                    rc = call(g, raw, int(discover.get("max_poa_length", 2 * tl)), int(rep[0]), int(rep[1]), float(rep[2]),
+                              int(rep[3]), 1, scan[0], scan[1], C.byref(b), *(C.byref(c) for c in counts))
                     self.break_counts = tuple(c.value for c in counts)   # (blocks cut, of which at a repeat, sequences the scanner declined)
                 else:
                     rc = self.L.sxg_blockset_break_ex(g, raw, int(discover.get("max_poa_length", 2 * tl)), 1, int(rep[0]), int(rep[1]),
@@ -347,6 +445,17 @@ class Smoother:
             self.g = None
             raise SmoothError(msg)
         self.b = b
+
+    def path_letters(self):
+        """sxg_graph_path_letters: the graph's path letters as a PathLetters (id, path_off, letters) -- what the range providers
+        read; built once per graph and cached in it.  The arrays are copies."""
+        import numpy as np
+        li = _poa.LettersIn()
+        if self.L.sxg_graph_path_letters(self.g, C.byref(li)):
+            raise SmoothError(self.L.sxg_smooth_last_error().decode())
+        path_off = np.ctypeslib.as_array(li.path_off, shape=(li.n_paths + 1,)).copy()
+        letters = np.ctypeslib.as_array(li.letters, shape=(int(path_off[-1]),)).copy() if path_off[-1] else np.zeros(0, np.uint8)
+        return _poa.PathLetters(path_off=path_off, letters=letters, id=li.id)
 
     def block_ranges(self, block_id):
         """The ranges of a block as (path, step_begin, step_end, length) tuples."""
@@ -448,8 +557,9 @@ class Smoother:
         n = self.n_blocks
         thr, used = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32)
         ident = identity if identity is not None else (None, None)
-        if self.L.sxg_blockset_identity_thresholds(self.g, self.b, int(kmer_size), int(max_depth), ident[0], ident[1],
-                                                   thr.ctypes.data_as(C.POINTER(C.c_float)), used.ctypes.data_as(C.POINTER(C.c_int32))):
+        call = self.L.sxg_blockset_identity_thresholds_ranges if isinstance(ident, RangeProvider) else self.L.sxg_blockset_identity_thresholds
+        if call(self.g, self.b, int(kmer_size), int(max_depth), ident[0], ident[1],
+                thr.ctypes.data_as(C.POINTER(C.c_float)), used.ctypes.data_as(C.POINTER(C.c_int32))):
             raise SmoothError(self.L.sxg_smooth_last_error().decode())
         return thr[:n], used[:n]
 
@@ -468,7 +578,12 @@ class Smoother:
         mp.maf_header = header.encode() if header is not None else None
         gfa, maf, nf = C.c_void_p(), C.c_void_p(), C.c_int64()
         call = self.L.sxg_smooth_maf_gfa_device_rows if device_rows else self.L.sxg_smooth_maf_gfa_adaptive
-        rc = call(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, ident[0], ident[1], C.byref(gfa), C.byref(maf), C.byref(nf))
+        if isinstance(ident, RangeProvider):
+            rp = RangeProviders(None, ident[0], ident[1])
+            rc = self.L.sxg_smooth_iteration_ranges(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, C.byref(rp), int(bool(device_rows)),
+                                                    C.byref(gfa), C.byref(maf), C.byref(nf))
+        else:
+            rc = call(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, ident[0], ident[1], C.byref(gfa), C.byref(maf), C.byref(nf))
         if rc:
             raise SmoothError(self.L.sxg_smooth_last_error().decode())
         try:
@@ -480,11 +595,15 @@ class Smoother:
     def smooth_gfa(self, params, provider, identity=None):
         """One smoothing iteration -> GFA text; None on a rank of a multi-GPU provider that does not lace.
         identity: an identity provider for adaptive_poa_params (gpu_identifier(engine): the estimates of all blocks in one
-        device call before the POA calls); None = the host estimator.  Without adaptive_poa_params it is never called."""
+        device call before the POA calls; gpu_range_identifier(engine): the same on ranges of the resident path letters); None = the host estimator.  Without adaptive_poa_params it is never called."""
         run, fre, ctx = provider
         ident = identity if identity is not None else (None, None)
         out = C.c_void_p()
-        rc = self.L.sxg_smooth_gfa_adaptive(self.g, self.b, C.byref(params), run, fre, ctx, ident[0], ident[1], C.byref(out))
+        if isinstance(ident, RangeProvider):
+            rp = RangeProviders(None, ident[0], ident[1])
+            rc = self.L.sxg_smooth_iteration_ranges(self.g, self.b, C.byref(params), None, run, fre, ctx, C.byref(rp), 0, C.byref(out), None, None)
+        else:
+            rc = self.L.sxg_smooth_gfa_adaptive(self.g, self.b, C.byref(params), run, fre, ctx, ident[0], ident[1], C.byref(out))
         if rc == 1:   # SXG_NOT_ROOT
             return None
         return self._text(rc, out)
