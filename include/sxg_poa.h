@@ -52,6 +52,9 @@ extern "C" {
  *    thread per member, the results reassembled in the batch's block order (trimmed MSA and block cycles included).
  * 5 (addition, no number change, no struct change): want_msa = SXG_MSA_TRIMMED -- the rows of the MAF built on the device -- and
  *    sxg_poa_get_msa_stats.
+ * 5 (addition, no number change, no struct change): want_msa = SXG_MSA_TRIMMED_RESIDENT, sxg_poa_msa_row_letters and
+ *    sxg_poa_maf_text (with sxg_poa_maf_seg, sxg_poa_maf_text_in, _geometry, _stats) -- the text of unmerged MAF blocks laid out on
+ *    the device from the resident trimmed rows.
  * 5 (addition, no number change): sxg_poa_path_sgd_order and struct sxg_poa_sgd_in -- the path-guided SGD node order of prep
  *    (src/prep.cpp:11-163) on the device, decree Y.
  * 5 (addition, no number change: no struct or existing entry point changed): sxg_poa_repeat_scan_batch and struct
@@ -148,7 +151,8 @@ typedef struct sxg_poa_params {
 
 /* sxg_poa_batch_in::want_msa.
  * SXG_MSA_FULL: rows = the block's sequences (+ the consensus row when want_consensus), columns = every aligned group in rank order
- *   (decree S8); formatted on the host from the per-base paths.  Any other non-zero value but SXG_MSA_TRIMMED means this.
+ *   (decree S8); formatted on the host from the per-base paths.  Any other non-zero value but SXG_MSA_TRIMMED and
+ *   SXG_MSA_TRIMMED_RESIDENT means this.
  * SXG_MSA_TRIMMED (an addition to ABI 5): the rows the MAF is written from (src/smooth.cpp:791-847; the `text` fields of
  *   maf_rows_from_msa, before rows are repeated for duplicates), built on the device: in every row -- the consensus row, which
  *   comes last, included -- the first and the last bg_trim[b] letters are blanked (bg_trim NULL = 0; a row with fewer than
@@ -162,9 +166,15 @@ typedef struct sxg_poa_params {
  *   reassembled across ranks.
  *   sxg_poa_get_msa_stats: HIP-event milliseconds of the two kernels of the last execute (columns; rows) and the bytes of rows
  *   it wrote (any pointer may be NULL).  The columns and the scan scratch take 8 bytes per POA node of the batch, allocated
- *   with the handle's other result buffers (outside sxg_poa_set_memory_budget, which caps the block arenas). */
+ *   with the handle's other result buffers (outside sxg_poa_set_memory_budget, which caps the block arenas).
+ * SXG_MSA_TRIMMED_RESIDENT (an addition to ABI 5): everything SXG_MSA_TRIMMED does on the device, want_block_graph not downgraded
+ *   either, but the rows do not cross PCIe: the download fills msa_off and msa_cols and leaves msa NULL.  The rows stay on the
+ *   handle until its next upload, for sxg_poa_msa_row_letters and sxg_poa_maf_text (below).  The sharded entry points refuse it
+ *   as they refuse SXG_MSA_TRIMMED; sxg_poa_group_batch_upload / _run refuse it with SXG_E_INVALID: the rows would lie on several
+ *   members. */
 #define SXG_MSA_FULL 1
 #define SXG_MSA_TRIMMED 2
+#define SXG_MSA_TRIMMED_RESIDENT 3
 
 typedef struct sxg_poa_handle sxg_poa_handle;
 
@@ -730,6 +740,33 @@ int sxg_poa_get_twin_stats(sxg_poa_handle *h, sxg_poa_twin_stats *out);
 int sxg_poa_get_msa_stats(sxg_poa_handle *h, double *cols_ms, double *rows_ms, uint64_t *msa_bytes);
 /* The rows kernel's geometry: kept letters of a row one work item places, bytes of a row it builds on chip at once (tests). */
 void sxg_poa_msa_geometry(int32_t *chunk_letters, int32_t *tile_bytes);
+
+/* The resident trimmed MSA of the batch last executed on the handle (want_msa = SXG_MSA_TRIMMED or SXG_MSA_TRIMMED_RESIDENT,
+ * nothing uploaded since; anything else is SXG_E_INVALID).  Rows are counted block after block -- GLOBAL ROW INDEX --: a block's
+ * rows number nseq (+ 1 with consensus), and 0 for a block that is not live (status not SXG_ST_OK, or no sequences).
+ *
+ * sxg_poa_msa_row_letters: letters[r] = the bytes other than '-' of row r: what a caller checks the contract of SXG_MSA_TRIMMED
+ *   with (a sequence row holds its length minus twice the trim, or nothing) without seeing a row.
+ *
+ * sxg_poa_maf_text: `out` receives the segments back to back; out_bytes must equal the sum of their len.
+ *   kind 0: `len` bytes of `literal` from offset src;
+ *   kind 1: row `src` as it stands, len must equal its block's msa_cols;
+ *   kind 2: the same row reversed and complemented: '-' -> '-', 'A' <-> 'T', 'C' <-> 'G', every other byte value -> 'N'.
+ *   Every segment is checked on the host before anything is launched (kind, row index, len == msa_cols, literal range, out_bytes):
+ *   a bad one is SXG_E_INVALID, nothing is launched and `out` is untouched.  One kernel lays the text out in a device buffer
+ *   (16-byte stores, granules assembled in registers from every segment that overlaps them), one copy brings it to `out`.
+ * sxg_poa_maf_text_geometry: the destination bytes of one work item of that kernel (tests).
+ * sxg_poa_maf_text_stats: HIP-event milliseconds of the text kernel and the bytes it wrote, summed over the handle's calls (either
+ *   pointer may be NULL). */
+typedef struct sxg_poa_maf_seg { int64_t src; int32_t len; int32_t kind; } sxg_poa_maf_seg;
+typedef struct sxg_poa_maf_text_in {
+    int64_t n_segs; const sxg_poa_maf_seg *segs;
+    const uint8_t *literal; int64_t literal_bytes;
+} sxg_poa_maf_text_in;
+int sxg_poa_msa_row_letters(sxg_poa_handle *h, int32_t *letters /* [sum over blocks of rows] */);
+int sxg_poa_maf_text(sxg_poa_handle *h, const sxg_poa_maf_text_in *in, char *out, int64_t out_bytes);
+void sxg_poa_maf_text_geometry(int32_t *chunk_bytes);
+int sxg_poa_maf_text_stats(sxg_poa_handle *h, double *kernel_ms, uint64_t *bytes);
 /* Cap on device memory the handle may use for scratch arenas (bytes; 0 = default 3/4 of free). */
 int sxg_poa_set_memory_budget(sxg_poa_handle *h, uint64_t bytes);
 

@@ -329,6 +329,30 @@ int sxg_smooth_maf_gfa_device_rows(const sxg_graph *g, const sxg_blockset *b, co
                                    sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx, sxg_identity_fn ident, void *ident_ctx,
                                    char **out_gfa, char **out_maf, int64_t *n_flipped);
 
+/* sxg_smooth_maf_gfa_device_rows over MAF TEXT laid out by a provider (an addition to ABI 2, no struct changed): without block
+ * merging every block is its own MAF group, whose text is literals the library formats without looking at a row -- the "a
+ * blocks=K loops=..." line, "s name start size strand srcSize " of every row, newlines -- and the block's trimmed rows, one copy
+ * per duplicate, reversed and complemented where the block is groom-flipped.  With tp != NULL, mp->merge_blocks == 0 and
+ * SXG_SMOOTH_LEGACY unset the iteration asks the POA provider for want_msa = SXG_MSA_TRIMMED_RESIDENT (include/sxg_poa.h: msa_off
+ * and msa_cols come back, the rows stay with the provider until its next call) and, per chunk of blocks, in the thread that made
+ * the provider call and before the next one, calls tp->letters once -- letters[r] = bytes other than '-' of row r, rows counted
+ * block after block of the chunk: nseq (+ 1 with consensus) per block with sequences and status SXG_ST_OK --, checks the contract
+ * sxg_smooth_maf_gfa_device_rows checks (a violation fails the call with the same message, naming the first bad block), and
+ * calls tp->text once with the chunk's literal bytes and segment list (struct sxg_poa_maf_text_in) and the chunk's part of the
+ * MAF as `out`.  The host never holds a row.  sxg_poa_msa_row_letters and sxg_poa_maf_text with the engine handle as ctx are such
+ * a provider, next to sxg_poa_batch_run on the same handle (not a device group, not the sharded entry: both refuse resident
+ * rows).  rp: NULL, or the identity estimate of -a fed ranges (rp->identity; rp->scan is not called).
+ * Same GFA, same MAF, *n_flipped = 0, as sxg_smooth_maf_gfa_device_rows.  In every other case -- tp == NULL, mp->merge_blocks != 0,
+ * SXG_SMOOTH_LEGACY=1 -- the call IS sxg_smooth_maf_gfa_device_rows (with the identity estimate over rp's ranges), fallbacks
+ * included: same bytes, and the text provider is never called. */
+typedef int (*sxg_msa_letters_fn)(void *ctx, int32_t *letters);
+typedef int (*sxg_maf_text_fn)(void *ctx, const sxg_poa_maf_text_in *in, char *out, int64_t out_bytes);
+typedef struct sxg_maf_text_provider { sxg_msa_letters_fn letters; sxg_maf_text_fn text; void *ctx; } sxg_maf_text_provider;
+int sxg_smooth_maf_gfa_device_text(const sxg_graph *g, const sxg_blockset *b, const sxg_smooth_params *p,
+                                   const struct sxg_merge_params *mp, sxg_poa_run_fn run, sxg_poa_free_fn fre, void *ctx,
+                                   const sxg_maf_text_provider *tp, const sxg_range_providers *rp /* NULL or the -a identity over ranges */,
+                                   char **out_gfa, char **out_maf, int64_t *n_flipped);
+
 /* prep (src/prep.cpp:11-163, called from src/main.cpp:423-433 before every iteration unless -n): the graph is sorted by
  * path-guided SGD and chopped to nodes of at most max_node_length bases, so that block discovery -- a sweep over the nodes in
  * rank order -- meets the nodes in the order the paths walk them (an addition to ABI 2, no existing struct changed).  odgi is

@@ -12,13 +12,14 @@ SO = os.path.join(CSRC, "libsxgpoa.so")
 # path-guided SGD node order (poa_sgd.hip.h), without floating-point contraction (decree Y5: one rounding per operation);
 # kern_msa.hip: the kernels of the trimmed MSA (poa_msa.hip.h, arithmetic in poa_msa_cols.h); kern_repeat.hip: the kernels of the
 # tandem-repeat scan (poa_repeat.hip.h, arithmetic in poa_repeat.h), without contraction as kern_sgd.hip (decree R3);
-# kern_letters.hip: the range gather of the resident path letters (poa_letters.hip.h, arithmetic in poa_letters.h)
+# kern_letters.hip: the range gather of the resident path letters (poa_letters.hip.h, arithmetic in poa_letters.h);
+# kern_maf.hip: the MAF text gather and the letter count of the resident trimmed rows (poa_maf_text.hip.h, arithmetic in poa_maf_text.h)
 KERN_PARTS = range(1, 10)
 SOURCES = [("sxg_poa.hip", "sxg_poa.o", []), ("kern_split.hip", "kern_split.o", []), ("kern_msa.hip", "kern_msa.o", []),
            ("kern_sgd.hip", "kern_sgd.o", ["-ffp-contract=off"]), ("kern_repeat.hip", "kern_repeat.o", ["-ffp-contract=off"]),
-           ("kern_letters.hip", "kern_letters.o", [])] + [("kern_part.hip", "kern_part%d.o" % k, ["-DSXG_KERN_PART=%d" % k]) for k in KERN_PARTS]
+           ("kern_letters.hip", "kern_letters.o", []), ("kern_maf.hip", "kern_maf.o", [])] + [("kern_part.hip", "kern_part%d.o" % k, ["-DSXG_KERN_PART=%d" % k]) for k in KERN_PARTS]
 DEPS = ["sxg_poa.hip", "kern_part.hip", "poa_classes.h", "poa_slot_prof.h", "poa_cost.h", "poa_tiles.h", "poa_deal.h", "poa_results.h", "poa_devres.h", "poa_kernels.hip.h", "poa_kern_tables.hip.h", "poa_dp.hip.h", "poa_dp16.hip.h", "poa_dp16_fill.inc.h", "poa_dp16_row.inc.h", "poa_prep_rows.inc.h", "poa_rowcode.h", "poa_fields.h", "poa_band16.hip.h", "poa_graph_dev.h",
-                  "poa_bgraph_dev.h", "poa_types.h", "kern_split.hip", "poa_split.hip.h", "poa_mash.hip.h", "poa_identity.hip.h", "poa_identity_key.h", "kern_sgd.hip", "poa_sgd.hip.h", "kern_msa.hip", "poa_msa.hip.h", "poa_msa_cols.h", "kern_repeat.hip", "poa_repeat.hip.h", "poa_repeat.h", "kern_letters.hip", "poa_letters.hip.h", "poa_letters.h", os.path.join("..", "..", "include", "sxg_poa.h")]
+                  "poa_bgraph_dev.h", "poa_types.h", "kern_split.hip", "poa_split.hip.h", "poa_mash.hip.h", "poa_identity.hip.h", "poa_identity_key.h", "kern_sgd.hip", "poa_sgd.hip.h", "kern_msa.hip", "poa_msa.hip.h", "poa_msa_cols.h", "kern_repeat.hip", "poa_repeat.hip.h", "poa_repeat.h", "kern_letters.hip", "poa_letters.hip.h", "poa_letters.h", "kern_maf.hip", "poa_maf_text.hip.h", "poa_maf_text.h", os.path.join("..", "..", "include", "sxg_poa.h")]
 OBJ_DIR = os.path.join(CSRC, "build")
 
 

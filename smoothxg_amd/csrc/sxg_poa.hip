@@ -34,6 +34,7 @@
 #include "poa_letters.hip.h"       // the resident path letters: the gather that cuts ranges out of them for the two calls above (kern_letters.hip)
 #include "poa_sgd.hip.h"           // the path-guided SGD node order of prep: argument struct and launchers (kernels in kern_sgd.hip)
 #include "poa_msa.hip.h"           // the trimmed MSA (want_msa == SXG_MSA_TRIMMED): argument structs and launchers (kernels in kern_msa.hip)
+#include "poa_maf_text.hip.h"      // the MAF text of the resident trimmed rows, their letter counts: argument structs and launchers (kernels in kern_maf.hip)
 
 
 // ---------------------------------------------------------------------------------------
@@ -306,6 +307,7 @@ struct PinPool {
     void prewarm(size_t bytes) { if (void* p = acquire(bytes)) release(p); }   // (pin now, lend later)
     ~PinPool() { for (auto& b : bufs) (void)hipHostFree(b.p); }
 };
+static inline bool msa_trimmed(int want_msa) { return want_msa == SXG_MSA_TRIMMED || want_msa == SXG_MSA_TRIMMED_RESIDENT; }
 struct sxg_poa_handle {
     // Every device resource of the handle is a member that frees itself (poa_devres.h): `delete h`, with h->device current, is the
     // whole teardown.  The stream and the events stand first: members die in reverse order, the buffers before their stream.
@@ -353,6 +355,15 @@ struct sxg_poa_handle {
     std::vector<int32_t> d_trim_h;   // host copy of d_trim
     std::vector<int32_t> msa_cols_h;
     double msa_cols_ms = 0, msa_rows_ms = 0;
+    // the MAF text (sxg_poa_maf_text) and the letter counts of the resident rows: where every row starts in d_msa (built on first
+    // use after an execute), the per-call arrays and the text on the device, events and sums of the text kernel
+    std::vector<int64_t> msa_row_begin_h;
+    std::vector<char> msa_live_h;   // [n_blocks] the blocks run_msa_rows built rows for (status OK, with sequences)
+    bool msa_rows_staged = false;
+    DevBuf d_maf_rowb, d_maf_letters, d_maf_off, d_maf_srck, d_maf_lit, d_maf_text;
+    DevEvent maf_e0, maf_e1;
+    double maf_text_ms = 0;
+    uint64_t maf_text_bytes = 0;
     // resident path letters (sxg_poa_letters_*): outside the memory budget, kept across batches; path_off is the host's copy for
     // the validation of ranges, d_src / d_off the per-call arrays of the gather (kept here so that they outlive its launch)
     struct Letters {
@@ -586,9 +597,9 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
     h->want_consensus = in->want_consensus; h->want_msa = in->want_msa;
     h->want_block_graph = in->want_block_graph < 0 || in->want_block_graph > 3 ? 0 : in->want_block_graph;
     // (the full MSA is formatted on the host from the per-base paths; the trimmed one is built on the device)
-    if (h->want_block_graph >= 2 && in->want_msa && in->want_msa != SXG_MSA_TRIMMED) h->want_block_graph = 1;
+    if (h->want_block_graph >= 2 && in->want_msa && !msa_trimmed(in->want_msa)) h->want_block_graph = 1;
     h->bg_cons_visited_only = in->bg_consensus_visited_only ? 1 : 0;
-    h->bg_done = false; h->msa_done = false;
+    h->bg_done = false; h->msa_done = false; h->msa_rows_staged = false;
     h->per_block_params = in->per_block_params;
     h->h_blk_off.assign(in->blk_off, in->blk_off + nb + 1);
     h->h_seq_off.assign(in->seq_off, in->seq_off + ns + 1);
@@ -646,7 +657,7 @@ extern "C" int sxg_poa_batch_upload(sxg_poa_handle* h, const sxg_poa_batch_in* i
         if ((rc = h->d_weights.ensure(4 * (size_t)std::max<int64_t>(ns, 1)))) return rc;
         if (ns) HIPCHK(hipMemcpyAsync(h->d_weights.p, in->weights, 4 * (size_t)ns, hipMemcpyHostToDevice, h->stream));
     }
-    if (h->want_block_graph || h->want_msa == SXG_MSA_TRIMMED) {
+    if (h->want_block_graph || msa_trimmed(h->want_msa)) {
         std::vector<int32_t> trim((size_t)std::max(nb, 1), 0);
         for (int b = 0; b < nb; ++b) {
             trim[b] = in->bg_trim ? in->bg_trim[b] : 0;
@@ -1030,6 +1041,8 @@ static int run_msa_rows(sxg_poa_handle* h, const std::vector<int32_t>& status) {
         node_o[(size_t)b + 1] = node_o[(size_t)b] + (live ? nn[b] : 0);
         if (live) work.push_back(b);
     }
+    h->msa_live_h.assign((size_t)std::max(nb, 1), 0);
+    for (int b : work) h->msa_live_h[(size_t)b] = 1;
     std::stable_sort(work.begin(), work.end(), [&](int a, int b) { return h->meta[a].sumlen > h->meta[b].sumlen; });
     const size_t NN = (size_t)std::max<int64_t>(node_o[(size_t)nb], 1), NBL = (size_t)std::max(nb, 1);
     int rc;
@@ -1111,6 +1124,120 @@ extern "C" int sxg_poa_get_msa_stats(sxg_poa_handle* h, double* cols_ms, double*
     if (cols_ms) *cols_ms = h->msa_cols_ms;
     if (rows_ms) *rows_ms = h->msa_rows_ms;
     if (msa_bytes) *msa_bytes = h->msa_done && !h->msa_off_h.empty() ? (uint64_t)h->msa_off_h.back() : 0;
+    return SXG_OK;
+}
+
+// The resident rows of the executed batch, for sxg_poa_msa_row_letters and sxg_poa_maf_text: which batch qualifies, and where
+// every row (global row index: block after block, live blocks only) starts in d_msa -- on the host for the checks, on the device
+// for the letters kernel.
+static int msa_resident_rows(sxg_poa_handle* h, const char* what) {
+    if (!h->have_batch || !h->executed || !h->msa_done || !msa_trimmed(h->want_msa))
+        return fail(SXG_E_INVALID, std::string(what) + ": the handle holds no resident trimmed MSA (want_msa = SXG_MSA_TRIMMED or SXG_MSA_TRIMMED_RESIDENT, executed, nothing uploaded since)");
+    if (h->msa_rows_staged) return SXG_OK;
+    const int nb = h->n_blocks;
+    if (h->msa_off_h.size() != (size_t)nb + 1 || h->msa_cols_h.size() < (size_t)nb) return fail(SXG_E_INVALID, std::string(what) + ": the trimmed MSA's offsets do not match the batch");
+    h->msa_row_begin_h.assign(1, 0);
+    for (int b = 0; b < nb; ++b) {
+        const int64_t cols = h->msa_cols_h[(size_t)b], bytes = h->msa_off_h[(size_t)b + 1] - h->msa_off_h[(size_t)b];
+        const int rows_all = h->meta[b].nseq + (h->want_consensus ? 1 : 0);
+        // (a live block owns rows x cols bytes, cols possibly 0; a block that is not live owns none and has no rows)
+        const bool live = (size_t)b < h->msa_live_h.size() && h->msa_live_h[(size_t)b];
+        const int rows = live ? rows_all : 0;
+        if (bytes != (int64_t)rows * cols) return fail(SXG_E_INVALID, std::string(what) + ": block " + std::to_string(b) + " of the trimmed MSA is not rows x columns");
+        for (int r = 0; r < rows; ++r) h->msa_row_begin_h.push_back(h->msa_off_h[(size_t)b] + (int64_t)(r + 1) * cols);
+    }
+    if ((uint64_t)h->msa_row_begin_h.back() > h->d_msa.cap) return fail(SXG_E_INVALID, std::string(what) + ": the trimmed MSA does not fit its buffer");
+    if (int rc = h->d_maf_rowb.ensure(8 * h->msa_row_begin_h.size())) return rc;
+    HIPCHK(hipMemcpy(h->d_maf_rowb.p, h->msa_row_begin_h.data(), 8 * h->msa_row_begin_h.size(), hipMemcpyHostToDevice));
+    h->msa_rows_staged = true;
+    return SXG_OK;
+}
+
+extern "C" int sxg_poa_msa_row_letters(sxg_poa_handle* h, int32_t* letters) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    HIPCHK(hipSetDevice(h->device));
+    const RoctxRange range_("sxg_poa_msa_row_letters");
+    if (int rc = msa_resident_rows(h, "msa_row_letters")) return rc;
+    const int64_t n_rows = (int64_t)h->msa_row_begin_h.size() - 1;
+    if (n_rows == 0) return SXG_OK;
+    if (!letters) return fail(SXG_E_INVALID, "msa_row_letters: letters is NULL");
+    // the kernel reads whole aligned 16-byte words: the last one ends at most 15 bytes behind the rows, inside the allocation
+    if ((((uint64_t)h->msa_row_begin_h.back() + 15) & ~(uint64_t)15) > h->d_msa.cap) return fail(SXG_E_INVALID, "msa_row_letters: the rows' buffer is not padded to 16 bytes");
+    if (int rc = h->d_maf_letters.ensure(4 * (size_t)n_rows)) return rc;
+    MafLettersArgs A;
+    A.rows = h->d_msa.as<uint8_t>(); A.row_begin = h->d_maf_rowb.as<int64_t>(); A.letters = h->d_maf_letters.as<int32_t>(); A.n_rows = n_rows;
+    const int64_t groups = std::min<int64_t>((n_rows + SXG_MAF_THREADS / 64 - 1) / (SXG_MAF_THREADS / 64), (int64_t)std::max(h->num_cu, 1) * 8);
+    sxg_maf_launch_letters(A, (int)groups, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(letters, h->d_maf_letters.p, 4 * (size_t)n_rows, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return SXG_OK;
+}
+
+extern "C" void sxg_poa_maf_text_geometry(int32_t* chunk_bytes) {
+    if (chunk_bytes) *chunk_bytes = SXG_MAF_CHUNK;
+}
+
+extern "C" int sxg_poa_maf_text_stats(sxg_poa_handle* h, double* kernel_ms, uint64_t* bytes) {
+    if (!h) return fail(SXG_E_INVALID, "handle is NULL");
+    if (kernel_ms) *kernel_ms = h->maf_text_ms;
+    if (bytes) *bytes = h->maf_text_bytes;
+    return SXG_OK;
+}
+
+extern "C" int sxg_poa_maf_text(sxg_poa_handle* h, const sxg_poa_maf_text_in* in, char* out, int64_t out_bytes) {
+    if (!h || !in) return fail(SXG_E_INVALID, "NULL argument");
+    HIPCHK(hipSetDevice(h->device));
+    const RoctxRange range_("sxg_poa_maf_text");
+    if (int rc = msa_resident_rows(h, "maf_text")) return rc;
+    const int64_t n = in->n_segs, n_rows = (int64_t)h->msa_row_begin_h.size() - 1;
+    if (n < 0 || (n > 0 && !in->segs) || in->literal_bytes < 0 || (in->literal_bytes > 0 && !in->literal)) return fail(SXG_E_INVALID, "maf_text: NULL arrays");
+    // every segment against its source, before anything is launched: a mistake comes back as a return code, not as a fault of the device
+    std::vector<int64_t> off((size_t)n + 1, 0), srck((size_t)std::max<int64_t>(n, 1), 0);
+    for (int64_t s = 0; s < n; ++s) {
+        const sxg_poa_maf_seg& g = in->segs[s];
+        const std::string name = "maf_text: segment " + std::to_string(s);
+        if (g.len < 0) return fail(SXG_E_INVALID, name + " has a negative length");
+        int64_t start = 0;
+        if (g.kind == SXG_MAF_LITERAL) {
+            if (g.src < 0 || g.src > in->literal_bytes || g.len > in->literal_bytes - g.src) return fail(SXG_E_INVALID, name + " lies outside the literal bytes");
+            start = g.src;
+        } else if (g.kind == SXG_MAF_ROW || g.kind == SXG_MAF_ROW_REVCOMP) {
+            if (g.src < 0 || g.src >= n_rows) return fail(SXG_E_INVALID, name + " names row " + std::to_string(g.src) + " of " + std::to_string(n_rows));
+            start = h->msa_row_begin_h[(size_t)g.src];
+            if (g.len != h->msa_row_begin_h[(size_t)g.src + 1] - start) return fail(SXG_E_INVALID, name + ": len is not the msa_cols of the row's block");
+            if ((uint64_t)(start + g.len) > h->d_msa.cap) return fail(SXG_E_INVALID, name + " reads outside the rows' buffer");
+        } else return fail(SXG_E_INVALID, name + " has kind " + std::to_string(g.kind));
+        off[(size_t)s + 1] = off[(size_t)s] + g.len;
+        srck[(size_t)s] = start * 4 + g.kind;
+    }
+    const int64_t total = off[(size_t)n];
+    if (out_bytes != total) return fail(SXG_E_INVALID, "maf_text: out_bytes is " + std::to_string(out_bytes) + ", the segments hold " + std::to_string(total));
+    if (total == 0) return SXG_OK;
+    if (!out) return fail(SXG_E_INVALID, "maf_text: out is NULL");
+    int rc;
+    const size_t padded = ((size_t)total + 15) & ~(size_t)15;   // (the last granule is stored whole)
+    if ((rc = h->d_maf_off.ensure(8 * ((size_t)n + 1))) || (rc = h->d_maf_srck.ensure(8 * (size_t)n)) || (rc = h->d_maf_lit.ensure((size_t)std::max<int64_t>(in->literal_bytes, 16))) ||
+        (rc = h->d_maf_text.ensure(padded)))
+        return rc;
+    if (!h->maf_e0.raw) HIPCHK(h->maf_e0.create());
+    if (!h->maf_e1.raw) HIPCHK(h->maf_e1.create());
+    HIPCHK(hipMemcpyAsync(h->d_maf_off.p, off.data(), 8 * ((size_t)n + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_maf_srck.p, srck.data(), 8 * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (in->literal_bytes) HIPCHK(hipMemcpyAsync(h->d_maf_lit.p, in->literal, (size_t)in->literal_bytes, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));   // (the host arrays above leave scope with this call; pageable copies may still be staged)
+    MafTextArgs A;
+    A.literal = h->d_maf_lit.as<uint8_t>(); A.rows = h->d_msa.as<uint8_t>(); A.dst = h->d_maf_text.as<uint8_t>();
+    A.dst_off = h->d_maf_off.as<int64_t>(); A.srck = h->d_maf_srck.as<int64_t>(); A.n = n; A.total = total;
+    const int64_t groups = std::min<int64_t>(sxg_maf_n_chunks(total), (int64_t)std::max(h->num_cu, 1) * 8);
+    HIPCHK(hipEventRecord(h->maf_e0, h->stream));
+    sxg_maf_launch_text(A, (int)groups, h->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->maf_e1, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, h->maf_e0, h->maf_e1)); h->maf_text_ms += ms; h->maf_text_bytes += (uint64_t)total; }
+    // (the staging of the MSA rows' download: one straight copy into the caller's memory)
+    HIPCHK(hipMemcpy(out, h->d_maf_text.p, (size_t)total, hipMemcpyDeviceToHost));
     return SXG_OK;
 }
 
@@ -1474,7 +1601,7 @@ extern "C" int sxg_poa_batch_execute(sxg_poa_handle* h) {
         if (rc) return rc;
         lap("block graphs");
     }
-    if (h->want_msa == SXG_MSA_TRIMMED) {
+    if (msa_trimmed(h->want_msa)) {
         int rc = run_msa_rows(h, status);
         if (rc) return rc;
         lap("MSA rows");
@@ -1514,14 +1641,14 @@ struct OutOwner {
 // sxg::RESULT_FAMILIES / RESULT_FLAT: the handle's buffer, the per-block offsets its entries start at there (SRC_DENSE: the
 // buffer already is the dense array), and when the array is part of the result.
 enum { SRC_DENSE, SRC_BASE /* the block's first base: the worst-case layout of the raw graphs */, SRC_NODE, SRC_EDGE /* bg_node_o, bg_edge_o */, SRC_N };
-enum { WHEN_ALWAYS, WHEN_GRAPHS, WHEN_CONS, WHEN_GRAPHS_CONS, WHEN_PATHS, WHEN_BG, WHEN_BG_CONS, WHEN_MSA_ROWS };
+enum { WHEN_ALWAYS, WHEN_GRAPHS, WHEN_CONS, WHEN_GRAPHS_CONS, WHEN_PATHS, WHEN_BG, WHEN_BG_CONS, WHEN_MSA_ROWS, WHEN_MSA_ROWS_HOST /* the rows themselves: not when they stay resident */ };
 struct DevSource { DevBuf sxg_poa_handle::*buf; int src, when; };
 struct FamilySource { int when; DevSource pay[3]; };
 static const FamilySource FAMILY_SRC[] = {
     /* node_off    */ {WHEN_ALWAYS, {{&sxg_poa_handle::d_node_code, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_node_rank, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_node_group, SRC_BASE, WHEN_GRAPHS}}},
     /* edge_off    */ {WHEN_ALWAYS, {{&sxg_poa_handle::d_edge_tail, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_edge_head, SRC_BASE, WHEN_GRAPHS}, {&sxg_poa_handle::d_edge_w, SRC_BASE, WHEN_GRAPHS}}},
     /* cons_off    */ {WHEN_CONS, {{&sxg_poa_handle::d_cons, SRC_BASE, WHEN_GRAPHS_CONS}}},
-    /* msa_off     */ {WHEN_MSA_ROWS, {{&sxg_poa_handle::d_msa, SRC_DENSE, WHEN_MSA_ROWS}}},   // (the trimmed MSA; the full one is formatted on the host)
+    /* msa_off     */ {WHEN_MSA_ROWS, {{&sxg_poa_handle::d_msa, SRC_DENSE, WHEN_MSA_ROWS_HOST}}},   // (the trimmed MSA; the full one is formatted on the host)
     /* bg_node_off */ {WHEN_BG, {{&sxg_poa_handle::d_bg_len, SRC_NODE, WHEN_BG}, {&sxg_poa_handle::d_bg_od, SRC_NODE, WHEN_BG}, {&sxg_poa_handle::d_bg_id, SRC_NODE, WHEN_BG}}},
     /* bg_seq_off  */ {WHEN_BG, {{&sxg_poa_handle::d_bg_seq, SRC_NODE, WHEN_BG}}},
     /* bg_edge_off */ {WHEN_BG, {{&sxg_poa_handle::d_bg_eto, SRC_EDGE, WHEN_BG}}},
@@ -1544,7 +1671,8 @@ static bool present(const sxg_poa_handle* h, int when) {
     case WHEN_PATHS: return !(h->want_block_graph >= 2 && h->bg_done);
     case WHEN_BG: return bg;
     case WHEN_BG_CONS: return bg && h->want_consensus;
-    case WHEN_MSA_ROWS: return h->want_msa == SXG_MSA_TRIMMED;
+    case WHEN_MSA_ROWS: return msa_trimmed(h->want_msa);
+    case WHEN_MSA_ROWS_HOST: return h->want_msa == SXG_MSA_TRIMMED;
     default: return true;
     }
 }
@@ -1561,7 +1689,7 @@ struct DenseLayout {
 static int dense_layout(sxg_poa_handle* h, DenseLayout& D) {
     const int nb = h->n_blocks;
     const int64_t ns = h->n_seqs;
-    if (h->want_msa == SXG_MSA_TRIMMED && !h->msa_done) return fail(SXG_E_INVALID, "the trimmed MSA of this batch was not built");
+    if (msa_trimmed(h->want_msa) && !h->msa_done) return fail(SXG_E_INVALID, "the trimmed MSA of this batch was not built");
     std::vector<int32_t> status(std::max(nb, 1)), nn(std::max(nb, 1)), ne(std::max(nb, 1)), nc(std::max(nb, 1));
     if (nb) {
         HIPCHK(hipMemcpy(status.data(), h->d_status.p, 4 * (size_t)nb, hipMemcpyDeviceToHost));
@@ -1693,7 +1821,7 @@ extern "C" int sxg_poa_batch_download(sxg_poa_handle* h, sxg_poa_batch_out* out)
         else if ((rc = hip(hipMemcpy(dst, (h->*FLAT_SRC[f].buf).p, bytes, hipMemcpyDeviceToHost), "download of a flat array"))) return rc;
     }
     laps.lap("download: paths");   // (and the small per-block and per-sequence arrays)
-    if (h->want_msa && h->want_msa != SXG_MSA_TRIMMED && out->seq_path_nodes) {
+    if (h->want_msa && !msa_trimmed(h->want_msa) && out->seq_path_nodes) {
         const sxg::BatchShape S{nb, h->h_blk_off.data(), h->h_seq_off.data()};
         if (!sxg::format_full_msa(S, h->want_consensus != 0, [o](size_t bytes) { return o->alloc(bytes); }, out))
             return fail(SXG_E_NOMEM, "host allocation of the MSA failed");
@@ -2046,7 +2174,7 @@ static int comm_wait(sxg_poa_handle* h, const char* what) {
 }
 
 static int check_batch(const sxg_poa_batch_in* in) {
-    if (in->want_msa == SXG_MSA_TRIMMED) return fail(SXG_E_INVALID, "the trimmed MSA (want_msa = SXG_MSA_TRIMMED) is not reassembled across ranks: use sxg_poa_batch_run");
+    if (in->want_msa == SXG_MSA_TRIMMED || in->want_msa == SXG_MSA_TRIMMED_RESIDENT) return fail(SXG_E_INVALID, "the trimmed MSA (want_msa = SXG_MSA_TRIMMED) is not reassembled across ranks: use sxg_poa_batch_run");
     if (in->n_blocks < 0 || (in->n_blocks > 0 && (!in->blk_off || !in->seq_off || !in->params || !in->bases))) return fail(SXG_E_INVALID, "batch_in has NULL arrays");
     return SXG_OK;
 }
@@ -2353,6 +2481,7 @@ extern "C" int sxg_poa_group_set_long_blocks(sxg_poa_group* g, int on) {
 extern "C" int sxg_poa_group_batch_upload(sxg_poa_group* g, const sxg_poa_batch_in* in) {
     if (!g || !in) return fail(SXG_E_INVALID, "NULL argument");
     g->have_batch = false; g->executed = false;
+    if (in->want_msa == SXG_MSA_TRIMMED_RESIDENT) return fail(SXG_E_INVALID, "resident MSA rows (want_msa = SXG_MSA_TRIMMED_RESIDENT) would lie on several members of a group: use one handle");
     const int nb = in->n_blocks, n = (int)g->members.size();
     if (nb < 0 || (nb > 0 && (!in->blk_off || !in->seq_off || !in->params))) return fail(SXG_E_INVALID, "batch_in has NULL arrays");
     // (what the deal reads is checked here; everything else by every member's own upload)

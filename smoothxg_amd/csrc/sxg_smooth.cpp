@@ -906,16 +906,18 @@ int identity_table(const sxg_graph& g, const sxg_blockset& b, int k, uint64_t ma
 
 // ---------------------------------------------------------------------------------------------
 // MSA -> MAF rows: src/smooth.cpp:782-905
-struct maf_row_t { std::string src; uint64_t start, size; bool rev; uint64_t src_size; std::string text; };
+// (row: which of the block's MSA rows the text is -- the dedup'd sequence's rank, the consensus row last)
+struct maf_row_t { std::string src; uint64_t start, size; bool rev; uint64_t src_size; std::string text; int64_t row = -1; };
 
 // :850-905 rows from the TRIMMED texts (one per dedup'd sequence, the consensus row last): a row per duplicate, names, starts,
 // sizes and strands from the collected ranges
-std::vector<maf_row_t> maf_rows_from_texts(const sxg_graph& g, const std::vector<path_range_t>& ranges, const collected_t& c,
-                                           const std::vector<std::string>& texts, const std::string& consensus_name, size_t consensus_len) {
+// first half: everything but the text (src, start, size, rev, src_size and the MSA row a text would come from), for num_seqs
+// MSA rows -- what the MAF text path formats its literals from without holding a row
+std::vector<maf_row_t> maf_rows_fields(const sxg_graph& g, const std::vector<path_range_t>& ranges, const collected_t& c, const size_t num_seqs,
+                                       const std::string& consensus_name, size_t consensus_len) {
     std::vector<maf_row_t> rows;
     const bool add_consensus = !consensus_name.empty();
     const uint64_t pad = (uint64_t)c.poa_padding;
-    const size_t num_seqs = texts.size();
     for (size_t rank = 0; rank < num_seqs; ++rank) {
         const bool is_cons = add_consensus && rank == num_seqs - 1;
         const size_t ndup = is_cons ? 1 : c.dup_rank_in_path_ranges[rank].size();  // :772-779 placeholder entry
@@ -932,10 +934,17 @@ std::vector<maf_row_t> maf_rows_from_texts(const sxg_graph& g, const std::vector
             } else {         // :881-889 (a consensus shorter than twice the padding keeps no letter: size 0, not a wrapped difference)
                 row.src = consensus_name; row.rev = false; row.src_size = consensus_len >= 2 * pad ? consensus_len - 2 * pad : 0; row.start = 0; row.size = row.src_size;
             }
-            row.text = texts[rank];
+            row.row = (int64_t)rank;
             rows.push_back(row);
         }
     }
+    return rows;
+}
+// second half: the texts attached
+std::vector<maf_row_t> maf_rows_from_texts(const sxg_graph& g, const std::vector<path_range_t>& ranges, const collected_t& c,
+                                           const std::vector<std::string>& texts, const std::string& consensus_name, size_t consensus_len) {
+    std::vector<maf_row_t> rows = maf_rows_fields(g, ranges, c, texts.size(), consensus_name, consensus_len);
+    for (auto& row : rows) row.text = texts[(size_t)row.row];
     return rows;
 }
 
@@ -999,7 +1008,7 @@ std::string maf_block_text(const std::vector<maf_row_t>& rows) {  // src/maf.hpp
 // A13 + 8f-4: MAF block merging, flip decision, flip rebuild (src/smooth.cpp:1091-1544, 1600-1919,
 // 2352-2436).  The reference keeps rows in hash maps and walks them in hash order; here every map is
 // in insertion order (first emission), by decree.  Mirrored by oracle/smooth_oracle.py.
-struct maf_prow_t { uint64_t start, size; bool rev; uint64_t plen; std::string text; };
+struct maf_prow_t { uint64_t start, size; bool rev; uint64_t plen; std::string text; int64_t row = -1; };   // (row: maf_row_t::row, kept where a row is not merged)
 struct omap_t {   // insertion-ordered string -> rows
     std::vector<std::pair<std::string, std::vector<maf_prow_t>>> items;
     std::vector<maf_prow_t>* find(const std::string& k) { for (auto& it : items) if (it.first == k) return &it.second; return nullptr; }
@@ -1012,7 +1021,7 @@ struct merge_state_t { std::vector<merged_group_info_t> groups; std::vector<char
 
 omap_t maf_block_map(const std::vector<maf_row_t>& rows) {   // what smooth_spoa hands to the writer thread (:893-905)
     omap_t m;
-    for (auto& r : rows) m.get(r.src).push_back(maf_prow_t{r.start, r.size, r.rev, r.src_size, r.text});
+    for (auto& r : rows) m.get(r.src).push_back(maf_prow_t{r.start, r.size, r.rev, r.src_size, r.text, r.row});
     return m;
 }
 std::string revcomp_gapped(const std::string& t) {   // odgi::reverse_complement_in_place: '-' stays '-' (src/dna.cpp table)
@@ -1020,7 +1029,9 @@ std::string revcomp_gapped(const std::string& t) {   // odgi::reverse_complement
     for (size_t i = 0; i < t.size(); ++i) { const char c = t[t.size() - 1 - i]; r[i] = c == '-' ? '-' : comp(c); }
     return r;
 }
-std::string write_maf_rows(const omap_t& maf) {   // src/maf.hpp:35-66 over an ordered map
+// src/maf.hpp:35-66 over an ordered map: everything of every line in front of its text, "s name start size strand srcSize ", in
+// the order the lines are written
+std::vector<std::string> maf_row_prefixes(const omap_t& maf) {
     size_t w_src = 0, w_start = 0, w_size = 0, w_ps = 0;
     for (auto& it : maf.items)
         for (auto& r : it.second) {
@@ -1030,11 +1041,19 @@ std::string write_maf_rows(const omap_t& maf) {   // src/maf.hpp:35-66 over an o
             w_ps = std::max(w_ps, std::to_string(r.plen).size());
         }
     auto setw = [](const std::string& v, size_t w) { return (v.size() < w ? std::string(w - v.size(), ' ') : std::string()) + v; };
-    std::string o;
+    std::vector<std::string> o;
     for (auto& it : maf.items)
         for (auto& r : it.second)
-            o += "s " + it.first + std::string(w_src - it.first.size(), ' ') + setw(std::to_string(r.start), w_start + 1) + setw(std::to_string(r.size), w_size + 1) +
-                 setw(r.rev ? "-" : "+", 2) + setw(std::to_string(r.plen), w_ps + 1) + " " + r.text + "\n";
+            o.push_back("s " + it.first + std::string(w_src - it.first.size(), ' ') + setw(std::to_string(r.start), w_start + 1) + setw(std::to_string(r.size), w_size + 1) +
+                        setw(r.rev ? "-" : "+", 2) + setw(std::to_string(r.plen), w_ps + 1) + " ");
+    return o;
+}
+std::string write_maf_rows(const omap_t& maf) {
+    const std::vector<std::string> prefix = maf_row_prefixes(maf);
+    std::string o;
+    size_t k = 0;
+    for (auto& it : maf.items)
+        for (auto& r : it.second) o += prefix[k++] + r.text + "\n";
     return o + "\n";
 }
 // src/smooth.cpp:1091-1310
@@ -1049,7 +1068,7 @@ void put_block_in_group(maf_group_t& grp, uint64_t block_id, omap_t& maf, const 
             for (auto& r : it.second) {
                 const uint64_t start = flip ? r.plen - (r.start + r.size) : r.start;
                 if (flip) r.text = revcomp_gapped(r.text);
-                fresh.push_back(maf_prow_t{start, r.size, (bool)(flip ^ r.rev), r.plen, on_the_left ? r.text + gaps : gaps + r.text});
+                fresh.push_back(maf_prow_t{start, r.size, (bool)(flip ^ r.rev), r.plen, on_the_left ? r.text + gaps : gaps + r.text, r.row});
             }
             grp.rows.get(it.first) = std::move(fresh);
         } else {
@@ -1086,7 +1105,7 @@ void put_block_in_group(maf_group_t& grp, uint64_t block_id, omap_t& maf, const 
                 maf_prow_t& r = it.second[rk];
                 const uint64_t start = flip ? r.plen - (r.start + r.size) : r.start;
                 if (flip) r.text = revcomp_gapped(r.text);
-                have->push_back(maf_prow_t{start, r.size, (bool)(flip ^ r.rev), r.plen, on_the_left ? r.text + gaps : gaps + r.text});
+                have->push_back(maf_prow_t{start, r.size, (bool)(flip ^ r.rev), r.plen, on_the_left ? r.text + gaps : gaps + r.text, r.row});
             }
         }
     }
@@ -1104,7 +1123,8 @@ void put_block_in_group(maf_group_t& grp, uint64_t block_id, omap_t& maf, const 
     if (on_the_left) grp.block_ids.insert(grp.block_ids.begin(), block_id); else grp.block_ids.push_back(block_id);
 }
 // src/smooth.cpp:1312-1544
-std::string write_group(maf_group_t& grp, merge_state_t& st, bool add_consensus, const std::string& base, bool below, bool preserve_unmerged) {
+// the group's "a blocks=... loops=..." line (without its newline) and, in `maf`, the rows that follow it
+std::string group_lines(maf_group_t& grp, merge_state_t& st, bool add_consensus, const std::string& base, bool below, bool preserve_unmerged, omap_t& maf) {
     const auto& ids = grp.block_ids;
     const size_t n = ids.size();
     const uint64_t lo = std::min(ids.front(), ids.back()), hi = std::max(ids.front(), ids.back());
@@ -1135,7 +1155,6 @@ std::string write_group(maf_group_t& grp, merge_state_t& st, bool add_consensus,
         st.groups.push_back(info);
     }
     bool loops = false;
-    omap_t maf;
     for (auto& it : grp.rows.items) { if (it.second.size() > 1) loops = true; maf.get(it.first) = it.second; }
     if (add_consensus) {
         const size_t length = grp.rows.items.front().second.front().text.size();
@@ -1146,7 +1165,7 @@ std::string write_group(maf_group_t& grp, merge_state_t& st, bool add_consensus,
             if (n == 1 || preserve_unmerged) {
                 std::string gapped = std::string(pos0, '-') + c.second.text;
                 if (gapped.size() < length) gapped.append(length - gapped.size(), '-');
-                maf.get(c.first).push_back(maf_prow_t{c.second.start, c.second.size, c.second.rev, c.second.plen, gapped});
+                maf.get(c.first).push_back(maf_prow_t{c.second.start, c.second.size, c.second.rev, c.second.plen, gapped, c.second.row});
                 pos0 += c.second.text.size();
             }
             if (n > 1) { m_size += c.second.size; m_plen += c.second.plen; m_text += c.second.text; }
@@ -1155,7 +1174,12 @@ std::string write_group(maf_group_t& grp, merge_state_t& st, bool add_consensus,
     }
     std::string o = "a blocks=" + full + " loops=" + (loops ? "true" : "false");
     if (n > 1) { o += " merged=true"; if (below) o += " below_thresh=true"; }
-    return o + "\n" + write_maf_rows(maf);
+    return o;
+}
+std::string write_group(maf_group_t& grp, merge_state_t& st, bool add_consensus, const std::string& base, bool below, bool preserve_unmerged) {
+    omap_t maf;
+    const std::string a_line = group_lines(grp, st, add_consensus, base, below, preserve_unmerged, maf);
+    return a_line + "\n" + write_maf_rows(maf);
 }
 // the in-order MAF consumer of smooth_and_lace, src/smooth.cpp:1600-1919
 std::string merge_maf_blocks(std::vector<omap_t>& block_mafs, const std::vector<char>& groom_flips, bool merge_blocks, double jaccard_min,
@@ -2356,8 +2380,10 @@ static void reap(std::function<void()> fn) { g_reaper.run(std::move(fn)); }
 
 static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp,
                             sxg_poa_run_fn run, sxg_poa_free_fn fre, void* ctx, sxg_identity_fn ident, void* ident_ctx, char** out_gfa,
-                            char** out_maf, int64_t* n_flipped, const bool device_rows = false, sxg_identity_ranges_fn ident_r = nullptr) {
+                            char** out_maf, int64_t* n_flipped, const bool device_rows = false, sxg_identity_ranges_fn ident_r = nullptr,
+                            const sxg_maf_text_provider* tp = nullptr) {
     if (!g || !b || !p || !run || !out_gfa) return fail(SXG_E_INVALID, "NULL argument");
+    if (tp && (!tp->letters || !tp->text)) return fail(SXG_E_INVALID, "MAF text provider without its two functions");
     if (int prc = check_params(p)) return prc;
     if (out_maf) *out_maf = nullptr;
     if (n_flipped) *n_flipped = 0;
@@ -2384,13 +2410,17 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
     // The MAF consumer without block merging decides no flip and strings no consensus paths together: asked for device rows
     // (sxg_smooth_maf_gfa_device_rows) it takes the same compact path -- the provider returns the TRIMMED rows of every block
     // (SXG_MSA_TRIMMED) next to the block graphs, the grooming orientation comes from the collected ranges.
+    // Asked for device TEXT as well (sxg_smooth_maf_gfa_device_text) the rows never leave the provider: it keeps them resident
+    // (SXG_MSA_TRIMMED_RESIDENT), and the MAF text of a chunk is laid out by the text provider from literals formatted here and
+    // those rows, in the thread that made the provider call, before the next chunk's call replaces the rows (chunk_text below).
     const bool rows_fast = device_rows && mp && mp->merge_blocks == 0 && !getenv("SXG_SMOOTH_LEGACY");
+    const bool text_fast = rows_fast && tp != nullptr;
     const bool fast = (!mp || rows_fast) && !getenv("SXG_SMOOTH_LEGACY");
     std::atomic<int64_t> rows_bad{-1};   // first block whose rows broke the contract of SXG_MSA_TRIMMED
     std::vector<collected_t> col((size_t)nb);
     std::vector<ograph_t> graphs(fast ? 0 : (size_t)nb);
     std::vector<cblock_t> cblocks(fast ? (size_t)nb : 0);
-    std::vector<omap_t> block_mafs(mp ? (size_t)nb : 0);
+    std::vector<omap_t> block_mafs(mp && !text_fast ? (size_t)nb : 0);
     std::vector<char> groom(mp ? (size_t)nb : 0, 0);
     std::unordered_map<std::string, size_t> rank_of;
     for (size_t q = 0; q < g->pname.size(); ++q) rank_of[g->pname[q]] = q;
@@ -2405,13 +2435,19 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
         sxg_poa_batch_out out;
         uint8_t dummy = 0;
         int rc = SXG_OK;
+        // the text path: the chunk's MAF text (malloc: the only chunk's buffer becomes *out_maf), how the text call ended
+        struct free_t { void operator()(char* q) const { free(q); } };
+        std::unique_ptr<char, free_t> text;
+        int64_t text_bytes = 0;
+        int text_rc = SXG_OK;
+        std::string text_msg;
     };
     int64_t chunk_blocks = 8192;   // (round 4: the host phases of a chunk now cost less than what smaller launches lose on the GPU)
     if (const char* e = getenv("SXG_SMOOTH_CHUNK_BLOCKS")) chunk_blocks = std::max<int64_t>(1, atoll(e));
     const int64_t nc = std::max<int64_t>(1, nb / chunk_blocks);
     std::vector<chunk_t> chunks((size_t)nc);
     for (int64_t c = 0; c < nc; ++c) { chunks[(size_t)c].k0 = nb * c / nc; chunks[(size_t)c].k1 = nb * (c + 1) / nc; }
-    double t_collect = 0, t_wait = 0, t_graphs = 0;
+    double t_collect = 0, t_wait = 0, t_graphs = 0, t_text = 0;
     auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
     // A14 with an identity provider: every block's estimate in ONE provider call, on this thread, BEFORE the pipeline starts --
     // the POA provider runs in a thread of its own on what is usually the same engine handle, and the two must never be in
@@ -2481,7 +2517,7 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
         C.in.bases = B.bases.empty() ? &C.dummy : B.bases.data(); C.in.weights = B.weights.data(); C.in.params = C.pps.data();
         C.in.per_block_params = p->adaptive_poa_params && n > 0 ? 1 : 0;
         C.in.want_consensus = p->add_consensus;
-        C.in.want_msa = rows_fast ? SXG_MSA_TRIMMED : mp ? SXG_MSA_FULL : 0;   // the MAF rows (and with them the merge / flip decisions) need the blocks' MSAs
+        C.in.want_msa = text_fast ? SXG_MSA_TRIMMED_RESIDENT : rows_fast ? SXG_MSA_TRIMMED : mp ? SXG_MSA_FULL : 0;   // the MAF rows (and with them the merge / flip decisions) need the blocks' MSAs
         if (fast) {   // A9 + A10 asked of the provider: trim = the block's padding, consensus filter of the abPOA path
             C.trims.resize((size_t)std::max<int64_t>(n, 1), 0);
             for (int64_t k = 0; k < n; ++k) C.trims[(size_t)k] = col[(size_t)(k0 + k)].poa_padding;
@@ -2490,7 +2526,94 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
         t_collect += since(t0);
     };
     // stage 2: ONE batched POA call per chunk (replaces src/smooth.cpp:752-786 of every block)
-    auto call = [&](chunk_t* C) { C->rc = run(ctx, &C->in, &C->out); };
+    const std::string rows_contract = ": every sequence row holds its length minus twice the padding in letters, every row is msa_cols wide";
+    // stage 2b, text path: the chunk's MAF text from the provider's resident rows.  The literals -- the "a blocks=... loops=..."
+    // line, "s name start size strand srcSize " of every row, the newlines -- come from the functions that format the rows path
+    // (maf_rows_fields, put_block_in_group for a fresh group with the grooming flip, group_lines, maf_row_prefixes), run over
+    // rows without text; a row is a segment of kind 1, or 2 where the block is groom-flipped.  Rows are numbered as the
+    // provider numbers them: block after block of the chunk, nseq (+ 1 with consensus) per block with sequences and status OK.
+    auto chunk_text = [&](chunk_t& C) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const sxg_poa_batch_out& out = C.out;
+        const int64_t k0 = C.k0, n = C.k1 - C.k0;
+        if (n > 0 && (!out.msa_off || !out.msa_cols || !out.status)) { C.text_rc = SXG_E_INVALID; C.text_msg = "POA provider returned no MSA"; return; }
+        const size_t cons_rows = p->add_consensus ? 1 : 0;
+        std::vector<int64_t> row_base((size_t)n + 1, 0);
+        for (int64_t s = 0; s < n; ++s) {
+            const collected_t& c = col[(size_t)(k0 + s)];
+            row_base[(size_t)s + 1] = row_base[(size_t)s] + (!c.seqs.empty() && out.status[s] == SXG_ST_OK ? (int64_t)(c.seqs.size() + cons_rows) : 0);
+        }
+        std::vector<int32_t> letters((size_t)std::max<int64_t>(row_base[(size_t)n], 1), 0);
+        if (row_base[(size_t)n] > 0 && tp->letters(tp->ctx, letters.data()) != SXG_OK) { C.text_rc = SXG_E_INVALID; C.text_msg = "MAF text provider failed to count the rows' letters"; return; }
+        for (int64_t s = 0; s < n; ++s) {   // the contract of the trimmed rows, as the rows path checks it
+            const collected_t& c = col[(size_t)(k0 + s)];
+            if (c.seqs.empty()) continue;
+            const int64_t nrow = (int64_t)(c.seqs.size() + cons_rows), cols = out.msa_cols[s];
+            bool ok = out.status[s] == SXG_ST_OK && cols >= 0 && out.msa_off[s + 1] - out.msa_off[s] == nrow * cols;
+            for (size_t r = 0; ok && r < c.seqs.size(); ++r)
+                ok = letters[(size_t)row_base[(size_t)s] + r] == std::max<int64_t>(0, (int64_t)c.seqs[r].size() - 2 * (int64_t)c.poa_padding);
+            if (!ok) { int64_t none = -1; rows_bad.compare_exchange_strong(none, k0 + s); return; }
+        }
+        std::string literal;
+        std::vector<sxg_poa_maf_seg> segs;
+        size_t lit_from = 0;
+        int64_t total = 0;
+        auto flush_literal = [&]() {
+            for (size_t at = lit_from; at < literal.size();) {   // (a segment's length is 32 bits)
+                const size_t len = std::min<size_t>(literal.size() - at, (size_t)1 << 30);
+                segs.push_back(sxg_poa_maf_seg{(int64_t)at, (int32_t)len, 0});
+                at += len;
+            }
+            total += (int64_t)(literal.size() - lit_from);
+            lit_from = literal.size();
+        };
+        if (k0 == 0 && mp->maf_header) literal += std::string(mp->maf_header) + "\n";
+        const std::string base = p->consensus_base_name ? p->consensus_base_name : "Consensus_";
+        merge_state_t st;   // (groups of one block leave no trace in it)
+        for (int64_t s = 0; s < n; ++s) {
+            const int64_t k = k0 + s;
+            const collected_t& c = col[(size_t)k];
+            if (c.seqs.empty()) continue;   // (a block without sequences has no rows: skipped)
+            const size_t cons_len = out.cons_off ? (size_t)(out.cons_off[s + 1] - out.cons_off[s]) : 0;
+            std::vector<maf_row_t> rows = maf_rows_fields(*g, b->blocks[(size_t)k], c, c.seqs.size() + cons_rows, cons_name(*p, k), cons_len);
+            for (auto& r : rows) r.row += row_base[(size_t)s];
+            omap_t block = maf_block_map(rows);
+            const bool flip = groom_flip_from_ranges(rank_of, *g, b->blocks[(size_t)k], c);
+            maf_group_t grp;
+            put_block_in_group(grp, (uint64_t)k, block, p->add_consensus ? base + std::to_string(k) : std::string(), false, flip);
+            omap_t maf;
+            literal += group_lines(grp, st, p->add_consensus != 0, base, false, mp->preserve_unmerged_consensus != 0, maf) + "\n";
+            const std::vector<std::string> prefix = maf_row_prefixes(maf);
+            size_t q = 0;
+            for (auto& it : maf.items)
+                for (auto& r : it.second) {
+                    literal += prefix[q++];
+                    flush_literal();
+                    segs.push_back(sxg_poa_maf_seg{r.row, out.msa_cols[s], flip ? 2 : 1});
+                    total += out.msa_cols[s];
+                    literal += "\n";
+                }
+            literal += "\n";
+        }
+        flush_literal();
+        C.text.reset((char*)malloc((size_t)total + 1));
+        if (!C.text) { C.text_rc = SXG_E_NOMEM; C.text_msg = "out of host memory for the MAF text"; return; }
+        C.text.get()[total] = 0;
+        C.text_bytes = total;
+        sxg_poa_maf_text_in in;
+        memset(&in, 0, sizeof(in));
+        in.n_segs = (int64_t)segs.size(); in.segs = segs.data(); in.literal = (const uint8_t*)literal.data(); in.literal_bytes = (int64_t)literal.size();
+        if (tp->text(tp->ctx, &in, C.text.get(), total) != SXG_OK) { C.text_rc = SXG_E_INVALID; C.text_msg = "MAF text provider failed"; }
+        t_text += since(t0);
+    };
+    auto call = [&](chunk_t* C) {
+        C->rc = run(ctx, &C->in, &C->out);
+        if (text_fast && C->rc == SXG_OK) {
+            try { chunk_text(*C); }   // (this may be a thread of its own: nothing may leave it)
+            catch (const std::bad_alloc&) { C->text_rc = SXG_E_NOMEM; C->text_msg = "out of host memory for the MAF text"; }
+            catch (const std::exception& e) { C->text_rc = SXG_E_INVALID; C->text_msg = std::string("internal error: ") + e.what(); }
+        }
+    };
     // stage 3: A9/A10 per block in parallel (the second half of the reference's loop)
     auto finish = [&](chunk_t& C) {
         const auto t0 = std::chrono::steady_clock::now();
@@ -2524,7 +2647,7 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
                 // on the next chunk: the block's share of the validation (src/main.cpp:770-810) is done here, off the serial
                 // tail behind the last chunk.  (One chunk: nothing to overlap with, lace_fast does it.)
                 if (nc > 1) Bk.validated = block_spells_its_ranges(g, b->blocks[(size_t)k], Bk) ? 1 : -1;
-                if (rows_fast) {   // the block's MAF rows straight from the provider's trimmed rows, after the contract is checked
+                if (rows_fast && !text_fast) {   // the block's MAF rows straight from the provider's trimmed rows, after the contract is checked
                     const size_t nrow = c.seqs.size() + (p->add_consensus ? 1 : 0);
                     const int64_t cols = out.msa_cols[slot];
                     bool ok = cols >= 0 && out.msa_off[slot + 1] - out.msa_off[slot] == (int64_t)nrow * cols;
@@ -2576,7 +2699,11 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
             if (c + 1 < nc) worker = std::thread(call, &chunks[(size_t)c + 1]);
             if (C.rc == SXG_NOT_ROOT) not_root = true;   // multi-GPU provider (sxg_poa_batch_run_sharded) on a rank that does not lace
             else if (C.rc != SXG_OK) { if (fail_rc == SXG_OK) { fail_rc = C.rc; fail_msg = "POA provider failed"; } }
-            else if (mp && C.k1 > C.k0 && (!C.out.msa || !C.out.msa_off || !C.out.msa_cols)) { if (fail_rc == SXG_OK) { fail_rc = SXG_E_INVALID; fail_msg = "POA provider returned no MSA"; } }
+            else if (text_fast && (C.text_rc != SXG_OK || rows_bad.load() >= 0)) {
+                if (fail_rc == SXG_OK && C.text_rc != SXG_OK) { fail_rc = C.text_rc; fail_msg = C.text_msg; }
+                else if (fail_rc == SXG_OK) { fail_rc = SXG_E_INVALID; fail_msg = "POA provider broke the contract of SXG_MSA_TRIMMED for block " + std::to_string(rows_bad.load()) + rows_contract; }
+            }
+            else if (mp && !text_fast && C.k1 > C.k0 && (!C.out.msa || !C.out.msa_off || !C.out.msa_cols)) { if (fail_rc == SXG_OK) { fail_rc = SXG_E_INVALID; fail_msg = "POA provider returned no MSA"; } }
             else if (fast && C.k1 > C.k0 && !C.out.bg_node_off && (!C.out.seq_path_nodes || !C.out.node_off || !C.out.node_code)) {
                 if (fail_rc == SXG_OK) { fail_rc = SXG_E_INVALID; fail_msg = "POA provider returned neither block graphs nor per-base paths"; }
             }
@@ -2584,8 +2711,7 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
                 finish(C);
                 if (rows_bad.load() >= 0) {
                     fail_rc = SXG_E_INVALID;
-                    fail_msg = "POA provider broke the contract of SXG_MSA_TRIMMED for block " + std::to_string(rows_bad.load()) +
-                               ": every sequence row holds its length minus twice the padding in letters, every row is msa_cols wide";
+                    fail_msg = "POA provider broke the contract of SXG_MSA_TRIMMED for block " + std::to_string(rows_bad.load()) + rows_contract;
                 }
             }
             if (fre && !C.keep_out) fre(&C.out);
@@ -2601,7 +2727,25 @@ static int smooth_iteration(const sxg_graph* g, const sxg_blockset* b, const sxg
         T0 = std::chrono::steady_clock::now();
     }
     if (fast) {
-        if (rows_fast) {   // the in-order MAF consumer (no merging: every block its own group, groomed)
+        if (text_fast) {   // the chunks' texts are the MAF: the only chunk's buffer as it is, several back to back
+            if (out_maf) {
+                if (nc == 1) *out_maf = chunks[0].text.release();
+                else {
+                    int64_t total = 0;
+                    for (auto& C : chunks) total += C.text_bytes;
+                    char* all = (char*)malloc((size_t)total + 1);
+                    if (all) {
+                        int64_t at = 0;
+                        for (auto& C : chunks) { if (C.text_bytes) memcpy(all + at, C.text.get(), (size_t)C.text_bytes); at += C.text_bytes; C.text.reset(); }
+                        all[total] = 0;
+                    }
+                    *out_maf = all;
+                }
+                if (!*out_maf) *out_maf = dup_out(std::string());   // (no block at all)
+            }
+            if (timing) fprintf(stderr, "[sxg_smooth] %-22s %.3f s  (in the provider's thread, inside the wait above)\n", "MAF text", t_text);
+            lap("MAF text handed over");
+        } else if (rows_fast) {   // the in-order MAF consumer (no merging: every block its own group, groomed)
             merge_state_t mstate;
             std::vector<char> flips;
             const std::string maf = merge_maf_blocks(block_mafs, groom, false, mp->contiguous_path_jaccard, p->add_consensus != 0,
@@ -3314,6 +3458,13 @@ int sxg_smooth_maf_gfa_device_rows(const sxg_graph* g, const sxg_blockset* b, co
                                    int64_t* n_flipped) {
     if (!mp || !out_maf) return fail(SXG_E_INVALID, "NULL argument");
     return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, ident, ident_ctx, out_gfa, out_maf, n_flipped, true); });
+}
+int sxg_smooth_maf_gfa_device_text(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
+                                   sxg_poa_free_fn fre, void* ctx, const sxg_maf_text_provider* tp, const sxg_range_providers* rp, char** out_gfa,
+                                   char** out_maf, int64_t* n_flipped) {
+    if (!mp || !out_maf) return fail(SXG_E_INVALID, "NULL argument");
+    return guarded([&] { return smooth_iteration(g, b, p, mp, run, fre, ctx, nullptr, rp ? rp->ctx : nullptr, out_gfa, out_maf, n_flipped, true,
+                                                 rp ? rp->identity : nullptr, tp); });
 }
 int sxg_smooth_maf_gfa(const sxg_graph* g, const sxg_blockset* b, const sxg_smooth_params* p, const sxg_merge_params* mp, sxg_poa_run_fn run,
                        sxg_poa_free_fn fre, void* ctx, char** out_gfa, char** out_maf, int64_t* n_flipped) {

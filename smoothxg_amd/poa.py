@@ -156,6 +156,8 @@ REPEAT_MAX_LEN = 1 << 20   # SXG_POA_REPEAT_MAX_LEN: the longest sequence the re
 MAX_SEQ_LEN_TILED = 49151  # SXG_POA_MAX_SEQ_LEN_TILED: every mode and score set, with set_long_blocks(True)
 ST_TOO_LONG = 5
 MSA_FULL, MSA_TRIMMED = 1, 2   # SXG_MSA_FULL / SXG_MSA_TRIMMED: values of want_msa (True = the full MSA)
+MSA_TRIMMED_RESIDENT = 3       # SXG_MSA_TRIMMED_RESIDENT: the trimmed rows stay on the device (msa_row_letters, maf_text)
+MAF_LITERAL, MAF_ROW, MAF_ROW_REVCOMP = 0, 1, 2   # sxg_poa_maf_seg::kind
 
 EXPORTS = ["sxg_poa_letters_upload", "sxg_poa_letters_drop", "sxg_poa_letters_resident", "sxg_poa_letters_stats", "sxg_poa_letters_geometry", "sxg_poa_range_gather",
            "sxg_poa_repeat_scan_ranges", "sxg_poa_block_identity_ranges", "sxg_poa_repeat_scan_batch", "sxg_poa_block_identity_batch", "sxg_poa_path_sgd_order", "sxg_poa_kmer_jaccard_batch", "sxg_poa_split_mash_batch", "sxg_poa_pair_identity_batch", "sxg_poa_split_batch", "sxg_poa_split_free", "sxg_poa_batch_device_view", "sxg_poa_abi_version", "sxg_poa_device_count", "sxg_poa_compute_units", "sxg_poa_last_error", "sxg_poa_create",
@@ -167,7 +169,8 @@ EXPORTS = ["sxg_poa_letters_upload", "sxg_poa_letters_drop", "sxg_poa_letters_re
            "sxg_poa_sharded_timing", "sxg_poa_measure_copy", "sxg_poa_roctx_available", "sxg_poa_get_msa_stats", "sxg_poa_msa_geometry",
            "sxg_poa_group_create", "sxg_poa_group_destroy", "sxg_poa_group_size", "sxg_poa_group_member", "sxg_poa_group_set_memory_budget",
            "sxg_poa_group_batch_run", "sxg_poa_group_batch_upload", "sxg_poa_group_batch_execute", "sxg_poa_group_batch_download",
-           "sxg_poa_group_timing", "sxg_poa_set_long_blocks", "sxg_poa_group_set_long_blocks", "sxg_poa_get_tile_stats"]
+           "sxg_poa_group_timing", "sxg_poa_set_long_blocks", "sxg_poa_group_set_long_blocks", "sxg_poa_get_tile_stats",
+           "sxg_poa_msa_row_letters", "sxg_poa_maf_text", "sxg_poa_maf_text_geometry", "sxg_poa_maf_text_stats"]
 COMM_ID_BYTES = 128
 NOT_ROOT = 1
 
@@ -249,6 +252,11 @@ def load_library(build_if_missing=True):
     L.sxg_poa_letters_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.sxg_poa_letters_geometry.argtypes = [C.POINTER(C.c_int32)]
     L.sxg_poa_letters_geometry.restype = None
+    L.sxg_poa_msa_row_letters.argtypes = [vp, _i32p]
+    L.sxg_poa_maf_text.argtypes = [vp, C.POINTER(MafTextIn), C.c_void_p, C.c_int64]
+    L.sxg_poa_maf_text_geometry.argtypes = [C.POINTER(C.c_int32)]
+    L.sxg_poa_maf_text_geometry.restype = None
+    L.sxg_poa_maf_text_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.sxg_poa_range_gather.argtypes = [vp, C.POINTER(LettersIn), C.c_uint64, C.c_int64, C.POINTER(Range), C.c_int, _u8p]
     L.sxg_poa_repeat_scan_ranges.argtypes = [vp, C.POINTER(RepeatRangesIn), _i32p, _i32p, C.POINTER(C.c_double), C.POINTER(C.c_double), _i32p, _i32p]
     L.sxg_poa_block_identity_ranges.argtypes = [vp, C.POINTER(IdentityRangesIn), _i32p, _i32p, _i32p, _i32p]
@@ -319,6 +327,19 @@ class BlockResult:
     """POA result of one block (what build_odgi_SPOA reads from spoa::Graph)."""
     __slots__ = ("status", "node_code", "node_rank", "node_group", "edge_tail", "edge_head", "edge_weight",
                  "paths", "scores", "cells", "consensus", "msa", "bg", "device_cycles")
+
+
+class MafSeg(C.Structure):
+    """sxg_poa_maf_seg"""
+    _fields_ = [("src", C.c_int64), ("len", C.c_int32), ("kind", C.c_int32)]
+
+
+class MafTextIn(C.Structure):
+    """sxg_poa_maf_text_in"""
+    _fields_ = [("n_segs", C.c_int64), ("segs", C.POINTER(MafSeg)), ("literal", C.POINTER(C.c_uint8)), ("literal_bytes", C.c_int64)]
+
+
+MAF_SEG_DTYPE = np.dtype([("src", np.int64), ("len", np.int32), ("kind", np.int32)])   # the layout of MafSeg, for numpy
 
 
 class BlockGraph:
@@ -456,6 +477,41 @@ class PoaEngine:
         self.lib.sxg_poa_get_msa_stats(self.h, C.byref(a), C.byref(b), C.byref(n))
         return a.value, b.value, n.value
 
+    def msa_row_letters(self):
+        """sxg_poa_msa_row_letters: the bytes other than '-' of every row of the resident trimmed MSA (want_msa = MSA_TRIMMED or
+        MSA_TRIMMED_RESIDENT, nothing uploaded since), rows counted block after block: nseq (+ 1 with consensus) per live block."""
+        blk_off = self._shape[0] if getattr(self, "_shape", None) is not None else np.zeros(1, np.int32)
+        room = int(blk_off[-1]) + len(blk_off)    # (at least every sequence and one consensus row per block)
+        letters = np.full(room, -1, np.int32)
+        if self.lib.sxg_poa_msa_row_letters(self.h, _p(letters, C.c_int32)):
+            raise self._err("sxg_poa_msa_row_letters")
+        return letters[:int(np.argmax(letters < 0))] if (letters < 0).any() else letters
+
+    def maf_text(self, segs, literal=b"", out=None):
+        """sxg_poa_maf_text: the segments back to back.  segs: [(src, len, kind)] or an array of MAF_SEG_DTYPE -- kind MAF_LITERAL:
+        `len` bytes of `literal` from src; MAF_ROW: row src of the resident trimmed MSA; MAF_ROW_REVCOMP: that row reversed and
+        complemented.  out: a writable uint8 array of exactly the segments' bytes to fill (default: a new one, returned as bytes)."""
+        sa = np.ascontiguousarray(segs, MAF_SEG_DTYPE) if isinstance(segs, np.ndarray) else np.array([tuple(x) for x in segs], MAF_SEG_DTYPE).reshape(-1)
+        lit = np.frombuffer(bytes(literal), np.uint8) if not isinstance(literal, np.ndarray) else np.ascontiguousarray(literal, np.uint8)
+        total = int(sa["len"].astype(np.int64).sum()) if len(sa) else 0
+        buf = np.empty(total, np.uint8) if out is None else out
+        ti = MafTextIn(len(sa), C.cast(sa.ctypes.data, C.POINTER(MafSeg)) if len(sa) else None, _p(lit, C.c_uint8) if len(lit) else None, len(lit))
+        if self.lib.sxg_poa_maf_text(self.h, C.byref(ti), buf.ctypes.data if buf.size else None, buf.size):
+            raise self._err("sxg_poa_maf_text")
+        return buf.tobytes() if out is None else out
+
+    def maf_text_geometry(self):
+        """sxg_poa_maf_text_geometry: destination bytes of one work item of the text kernel."""
+        c = C.c_int32()
+        self.lib.sxg_poa_maf_text_geometry(C.byref(c))
+        return c.value
+
+    def maf_text_stats(self):
+        """sxg_poa_maf_text_stats: (milliseconds of the text kernel, bytes it wrote), summed over the engine's calls."""
+        ms, n = C.c_double(), C.c_uint64()
+        self.lib.sxg_poa_maf_text_stats(self.h, C.byref(ms), C.byref(n))
+        return ms.value, n.value
+
     def device_view(self):
         """Raw HBM pointers of the executed batch's results (see sxg_poa_device_view)."""
         v = DeviceView()
@@ -513,7 +569,9 @@ class PoaEngine:
         msa_off = _arr(out.msa_off, nb + 1, np.int64) if out.msa_off else None
         msa_cols = _arr(out.msa_cols, nb, np.int32) if out.msa_cols else None
         msa_raw = None
-        if msa_off is not None and nb and msa_off[-1] > 0:
+        # (offsets and widths of the last result with a trimmed MSA: all there is of it when the rows stay resident)
+        self.msa_layout = (msa_off.copy(), msa_cols.copy()) if msa_off is not None and msa_cols is not None else None
+        if msa_off is not None and nb and msa_off[-1] > 0 and out.msa:
             msa_raw = C.string_at(out.msa, int(msa_off[-1]))
         res = []
         for b in range(nb):

@@ -24,6 +24,8 @@ IDENT_RANGES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.IdentityRanges
                               C.POINTER(C.c_int32))
 REPEAT_RANGES_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.RepeatRangesIn), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+MSA_LETTERS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32))
+MAF_TEXT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.MafTextIn), C.c_void_p, C.c_int64)
 SGD_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(_poa.SgdIn), C.POINTER(C.c_int32), C.POINTER(C.c_int64))
 
 
@@ -43,7 +45,7 @@ EXPORTS = ["sxg_smooth_abi_version", "sxg_smooth_default_params", "sxg_smooth_la
            "sxg_block_maf_rows", "sxg_block_maf", "sxg_blockset_from_ranges", "sxg_blockset_block_size",
            "sxg_blockset_block_ranges", "sxg_blockset_smoothable", "sxg_blockset_break", "sxg_blockset_break_ex", "sxg_blockset_break_scan", "sxg_blockset_split", "sxg_blockset_split_mash", "sxg_merge_default_params", "sxg_smooth_maf_gfa",
            "sxg_prep_default_params", "sxg_graph_prep", "sxg_blockset_identity_thresholds", "sxg_smooth_gfa_adaptive",
-           "sxg_smooth_maf_gfa_adaptive", "sxg_smooth_maf_gfa_device_rows", "sxg_graph_path_letters", "sxg_blockset_break_scan_ranges",
+           "sxg_smooth_maf_gfa_adaptive", "sxg_smooth_maf_gfa_device_rows", "sxg_smooth_maf_gfa_device_text", "sxg_graph_path_letters", "sxg_blockset_break_scan_ranges",
            "sxg_blockset_identity_thresholds_ranges", "sxg_smooth_iteration_ranges"]
 
 
@@ -62,6 +64,11 @@ class MergeParams(C.Structure):
 class RangeProviders(C.Structure):
     """sxg_range_providers: the scan provider, the identity provider and their context."""
     _fields_ = [("scan", C.c_void_p), ("identity", C.c_void_p), ("ctx", C.c_void_p)]
+
+
+class MafTextProvider(C.Structure):
+    """sxg_maf_text_provider: the letters function, the text function and their context."""
+    _fields_ = [("letters", C.c_void_p), ("text", C.c_void_p), ("ctx", C.c_void_p)]
 
 
 class RangeProvider(tuple):
@@ -118,6 +125,8 @@ def load_library():
     L.sxg_smooth_maf_gfa_adaptive.argtypes = [vp, vp, C.POINTER(SmoothParams), C.POINTER(MergeParams), vp, vp, vp, vp, vp, C.POINTER(vp),
                                               C.POINTER(vp), C.POINTER(C.c_int64)]
     L.sxg_smooth_maf_gfa_device_rows.argtypes = L.sxg_smooth_maf_gfa_adaptive.argtypes
+    L.sxg_smooth_maf_gfa_device_text.argtypes = [vp, vp, C.POINTER(SmoothParams), C.POINTER(MergeParams), vp, vp, vp, C.POINTER(MafTextProvider),
+                                                 C.POINTER(RangeProviders), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int64)]
     L.sxg_blockset_identity_thresholds.argtypes = [vp, vp, C.c_int32, C.c_uint64, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     L.sxg_graph_path_letters.argtypes = [vp, C.POINTER(_poa.LettersIn)]
     L.sxg_blockset_break_scan_ranges.argtypes = L.sxg_blockset_break_scan.argtypes
@@ -308,6 +317,60 @@ def python_range_scanner(fn):
             return -1
     cb = REPEAT_RANGES_FN(call)
     return RangeProvider((C.cast(cb, C.c_void_p), None, cb))
+
+
+class MafTexter(tuple):
+    """(letters, text, ctx[, keep-alive ...]): the MAF text provider of Smoother.smooth_maf_gfa(..., device_text=...)"""
+
+
+def gpu_maf_texter(engine):
+    """The MAF text provider backed by the GPU engine: sxg_poa_msa_row_letters and sxg_poa_maf_text of libsxgpoa.so and the engine
+    handle -- the SAME engine the POA provider of the call runs on, whose trimmed rows then stay on the device
+    (SXG_MSA_TRIMMED_RESIDENT) and leave it as MAF text.  A device group has no resident rows (they would lie on several members)."""
+    if isinstance(engine, _poa.PoaGroup):
+        raise ValueError("a device group keeps no resident MSA rows: the MAF text needs one engine")
+    L = engine.lib
+    return MafTexter((C.cast(L.sxg_poa_msa_row_letters, C.c_void_p), C.cast(L.sxg_poa_maf_text, C.c_void_p), engine.h))
+
+
+def python_maf_texter(letters_fn, text_fn):
+    """The MAF text provider around two Python functions, for CPU tests (the production provider is gpu_maf_texter):
+    letters_fn() -> the letter count of every resident row (bytes other than '-'), rows counted block after block;
+    text_fn(segs, literal) -> the text as bytes (or a uint8 array), segs a numpy array of poa.MAF_SEG_DTYPE (src, len, kind),
+    literal the literal bytes as a uint8 array.  Either may return None, or raise, to fail the call.  The tuple keeps the callbacks
+    alive."""
+    import numpy as np
+
+    def letters(ctx, out):
+        try:
+            res = letters_fn()
+            if res is None:
+                return -1
+            for k, v in enumerate(res):
+                out[k] = int(v)
+            return 0
+        except Exception:   # (an exception must not cross the C frames)
+            return -1
+
+    def text(ctx, inp, out, out_bytes):
+        try:
+            a = inp.contents
+            segs = np.zeros(a.n_segs, _poa.MAF_SEG_DTYPE)
+            if a.n_segs:
+                C.memmove(segs.ctypes.data, a.segs, a.n_segs * C.sizeof(_poa.MafSeg))
+            lit = np.ctypeslib.as_array(a.literal, shape=(a.literal_bytes,)).copy() if a.literal_bytes else np.zeros(0, np.uint8)
+            res = text_fn(segs, lit)
+            if res is None:
+                return -1
+            res = bytes(res) if not isinstance(res, np.ndarray) else res.astype(np.uint8).tobytes()
+            if len(res) != out_bytes:
+                return -1
+            C.memmove(out, res, out_bytes)
+            return 0
+        except Exception:   # (an exception must not cross the C frames)
+            return -1
+    cl, ct = MSA_LETTERS_FN(letters), MAF_TEXT_FN(text)
+    return MafTexter((C.cast(cl, C.c_void_p), C.cast(ct, C.c_void_p), None, cl, ct))
 
 
 def python_range_identifier(fn):
@@ -564,8 +627,11 @@ class Smoother:
         return thr[:n], used[:n]
 
     def smooth_maf_gfa(self, params, provider, merge_blocks=False, jaccard=1.0, preserve_unmerged=False, max_groups=50, header=None,
-                       identity=None, device_rows=False):
+                       identity=None, device_rows=False, device_text=None):
         """The iteration with the in-order MAF consumer (block merging, flips): -> (GFA text, MAF text, flipped blocks).
+        device_text=texter (gpu_maf_texter(engine), the engine of `provider`): sxg_smooth_maf_gfa_device_text -- without
+        merge_blocks the trimmed rows stay on the device and the MAF text is laid out there; identity: None or a range provider
+        (gpu_range_identifier).  With merge_blocks it is device_rows=True.  Same outputs.
         identity: as for smooth_gfa.  device_rows=True: sxg_smooth_maf_gfa_device_rows -- without merge_blocks the provider
         builds the trimmed MSA rows (SXG_MSA_TRIMMED: the GPU engine does, on the device) and the iteration laces compact
         block graphs; same outputs."""
@@ -578,7 +644,16 @@ class Smoother:
         mp.maf_header = header.encode() if header is not None else None
         gfa, maf, nf = C.c_void_p(), C.c_void_p(), C.c_int64()
         call = self.L.sxg_smooth_maf_gfa_device_rows if device_rows else self.L.sxg_smooth_maf_gfa_adaptive
-        if isinstance(ident, RangeProvider):
+        if device_text is not None:
+            if not isinstance(device_text, MafTexter):
+                raise TypeError("device_text takes gpu_maf_texter(engine) or python_maf_texter(...)")
+            if identity is not None and not isinstance(ident, RangeProvider):
+                raise ValueError("device_text takes the identity estimate over ranges (gpu_range_identifier) or none")
+            tp = MafTextProvider(device_text[0], device_text[1], device_text[2])
+            rp = RangeProviders(None, ident[0], ident[1]) if identity is not None else None
+            rc = self.L.sxg_smooth_maf_gfa_device_text(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, C.byref(tp),
+                                                       C.byref(rp) if rp is not None else None, C.byref(gfa), C.byref(maf), C.byref(nf))
+        elif isinstance(ident, RangeProvider):
             rp = RangeProviders(None, ident[0], ident[1])
             rc = self.L.sxg_smooth_iteration_ranges(self.g, self.b, C.byref(params), C.byref(mp), run, fre, ctx, C.byref(rp), int(bool(device_rows)),
                                                     C.byref(gfa), C.byref(maf), C.byref(nf))
